@@ -2,7 +2,8 @@
 """bench.py — BASELINE.json's metric on its config: decoded frames/s for data/H05.txt, 50-iteration
 sum-product BP, 1M synthetic AWGN frames per GPU (BASELINE configs[1]), 1/2/4/8 MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2                      # headline only
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full               # headline + every side leg below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          # one process per GPU
     python bench.py --inproc N --steps K --warmup W                     # one process, N GPUs, no torch.distributed
@@ -15,13 +16,23 @@ a SUM of four counters, carried by gloo on CPU tensors (no RCCL anywhere: north_
 
 Headline `value`: FIXED WORK — every frame runs all 50 flooding iterations (output latched at its first zero
 syndrome), nothing is skipped.  The reference's own stopping rule (bp.h:195-196) is timed under "early_exit".
+`ms_per_step` is the wall time of one of the `--steps` timed steps.
+
+A plain run sets up, warms up, times the `--steps` headline steps and prints the result; its roofline uses the committed
+counter passes when they were taken from the same kernel sources.  Everything else (side legs, live counter passes,
+CPU baselines) runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last step returned to its caller is written as DIR/<name>.npy
+(float32 / float64, < 64 MB in all; inputs are seeded, so two builds can be compared output for output).  Per shard
+(names prefixed "shard<s>_" when the job has several): ok and iters of every frame (or of the sampled frames when the
+shard is too large), bits = the hard decisions of a fixed, seeded sample of frames, frames = their global indices.
 
 OUTPUT.  The LAST stdout line is a compact JSON object (< 4 KB: `compact_line`) with the headline, its roofline, the CPU
 baselines and one {value, frac, bound} triple per side leg — what the driver's record keeps.  The full object (every leg
 with its layout, counters and notes, ~25 KB) is written to ./bench_detail.json and printed on an EARLIER stdout line
 prefixed "BENCH_DETAIL ".  Nothing is printed after the compact line.
 
-Side legs (N = 1, or any N with --all; N > 1 runs headline + early exit + Monte-Carlo only):
+Side legs (--full only; N = 1, or any N with --all; N > 1 runs headline + early exit + Monte-Carlo only):
   "streamed"      the HBM-resident engine north_star sketches (messages [edge][frame] in HBM): real HBM roofline
   "minsum_0.75"   north_star's named variant (not in the reference: parity unpinned)
   "configs[2]"    H05 QP-ADMM(1.95, 0.5) fp64, 100 sweeps, 1M frames — with its own roofline (LDS array)
@@ -446,6 +457,42 @@ def decode_leg(rig, batch, ctor, snr, steps, warmup, frames=None, noise_seed=1):
             "mean_iters": q["mean_iters"], "layout": lay, "instance": desc,
             "per_shard_ms_per_step": info["per_shard_ms_per_step"], "per_shard_kernel_ms": info["per_shard_kernel_ms"],
             "kernel_ms_per_launch": info["kernel_ms_per_launch"]}
+
+
+DUMP_LIMIT = 60 << 20      # bytes over all shards of the job (the contract: at most 64 MB)
+DUMP_SAMPLE = 16384        # frames per shard whose hard decisions are written
+
+
+def dump_outputs(batch, out_dir, frames=None):
+    """what the last step left in (bits, ok, its) of every shard of this process -> out_dir/<name>.npy.
+    ok / iters (float32) of every frame when they fit half of the shard's share of DUMP_LIMIT, else of the sample;
+    bits (float32 0/1, [S, n]) of a fixed, seeded sample of S frames; frames (float64) = their global indices."""
+    import numpy as np
+    torch = batch.rig.torch
+    F = batch.F if frames is None else frames
+    n = batch.n
+    os.makedirs(out_dir, exist_ok=True)
+    nshards = batch.rig.nshards
+    budget = DUMP_LIMIT // nshards
+    full = 8 * F <= budget // 2
+    left = budget - (8 * F if full else 0)
+    S = max(1, min(F, DUMP_SAMPLE, left // (4 * n + 8 + (0 if full else 8))))
+    written = 0
+    for d in batch.rig.devs:
+        s = d.shard
+        idx = np.sort(np.random.default_rng(239 + s).choice(F, S, replace=False))
+        ti = torch.from_numpy(idx).to(batch.bits[s].device)
+        words = batch.bits[s][ti].cpu().numpy()
+        bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :n].astype(np.float32)
+        ok, its = batch.ok[s][:F].cpu().numpy(), batch.its[s][:F].cpu().numpy()
+        if not full:
+            ok, its = ok[idx], its[idx]
+        pre = "shard%d_" % s if nshards > 1 else ""
+        for name, arr in (("bits", bits), ("frames", (idx + s * batch.F).astype(np.float64)),
+                          ("ok", ok.astype(np.float32)), ("iters", its.astype(np.float32))):
+            np.save(os.path.join(out_dir, pre + name + ".npy"), arr)
+            written += arr.nbytes
+    return written
 
 
 def mc_leg(rig, H, cws, ctor, snr, F, steps, noise="device"):
@@ -899,12 +946,16 @@ def main():
     ap.add_argument("--mu", type=float, default=0.5)
     ap.add_argument("--side-steps", type=int, default=3, help="timed steps of every side measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline and CPU baselines only")
     ap.add_argument("--all", action="store_true", help="N > 1: run every side leg too (default at N > 1: headline, early exit, Monte-Carlo)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (default: on at N=1)")
+    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (default: on at N=1 with --full)")
     ap.add_argument("--write-pmc", default=None, help="also store this run's counter passes here (profiles/pmc_rNN.json)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time target of each CPU baseline sample")
     ap.add_argument("--detail-out", default="bench_detail.json", help="where the full object goes (default: cwd)")
+    ap.add_argument("--full", action="store_true", help="also run the side legs, the live counter passes and the CPU "
+                                                        "baselines (default: the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (bits / ok / iters) as DIR/<name>.npy")
     ap.add_argument("--pmc-probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--probe-items", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -924,11 +975,13 @@ def main():
     single = rig.nshards == 1
     # N > 1 is the scaling curve of the METRIC: headline + early exit + Monte-Carlo legs.  The other legs (streamed engine,
     # QP-ADMM, configs[4] with its 5.3 GB of slabs per rank) are single-GPU characterisations and only run with --all.
-    core_legs = not a.no_extras
+    core_legs = a.full and not a.no_extras
     side_legs = core_legs and (single or a.all)
 
     # ---- headline: fixed 50 iterations, SNR a.snr -------------------------------------------------------
     head = decode_leg(rig, batch, T["bp_fused"], a.snr, a.steps, a.warmup)
+    if a.dump_outputs:   # before any other leg reuses the batch's output buffers
+        dump_outputs(batch, a.dump_outputs)
     bpf = bp_bytes_per_frame(n, E, a.iters)
     out = {
         "metric": "decoded frames/sec (+ FER@SNR) for H05.txt 50-iter BP", "value": head["value"], "unit": "frames/s",
@@ -951,7 +1004,7 @@ def main():
 
     # ---- counter passes of this run (N = 1 only) --------------------------------------------------------
     pmc = None
-    if single and not a.no_pmc and not a.no_extras:
+    if single and a.full and not a.no_pmc and not a.no_extras:
         rig.sync_local()
         pmc = pmc_collect(a, budget_s=300)
         if a.write_pmc and "error" not in pmc:
@@ -1068,7 +1121,7 @@ def main():
         out["legs_note"] = "N > 1: headline, early-exit and Monte-Carlo legs only (the metric's scaling curve); --all runs the single-GPU characterisation legs too"
 
     # ---- CPU baselines (rank 0, N = 1 only) -------------------------------------------------------------
-    if single and not a.no_cpu_baseline:
+    if single and a.full and not a.no_cpu_baseline:
         import multiprocessing as mp
         Hd = H.dense()
         cores, core_info = usable_cores(mp.get_context("spawn"))

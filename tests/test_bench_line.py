@@ -123,6 +123,81 @@ def test_probe_patterns_name_kernels_of_the_built_library():
         assert any(q in k for q in pats for k in names), (item, pats)
 
 
+def _fake_batch(F, n, nshards, own):
+    """bench.Batch's output buffers on the CPU: frame f of shard s decodes to the bits of (s*F + f) * 2654435761"""
+    import torch
+    nw = (n + 31) // 32
+    rig = types.SimpleNamespace(torch=torch, nshards=nshards, devs=[types.SimpleNamespace(shard=s) for s in own])
+    b = types.SimpleNamespace(rig=rig, F=F, n=n, bits={}, ok={}, its={})
+    for s in own:
+        g = (np.arange(F, dtype=np.uint64) + s * F) * np.uint64(2654435761)
+        words = np.zeros((F, nw), dtype=np.uint32)
+        words[:, 0] = (g & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        b.bits[s] = torch.from_numpy(words.view(np.int32))
+        b.ok[s] = torch.from_numpy((np.arange(F) % 3 != 0).astype(np.uint8))
+        b.its[s] = torch.from_numpy((np.arange(F) % 51).astype(np.int32))
+    return b
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    import bench
+    F, n = 1 << 20, 280
+    b = _fake_batch(F, n, 1, [0])
+    w1 = bench.dump_outputs(b, str(tmp_path / "a"))
+    w2 = bench.dump_outputs(b, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bits.npy", "frames.npy", "iters.npy", "ok.npy"]
+    size = sum(os.path.getsize(tmp_path / "a" / f) for f in names)
+    assert w1 == w2 and size < 64 << 20
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and (x == y).all(), f
+    ok, its, frames, bits = (np.load(tmp_path / "a" / (k + ".npy")) for k in ("ok", "iters", "frames", "bits"))
+    assert ok.shape == its.shape == (F,) and (ok == (np.arange(F) % 3 != 0)).all() and (its == np.arange(F) % 51).all()
+    assert bits.shape == (len(frames), n) and len(frames) > 1000 and (np.diff(frames) > 0).all()
+    g = (frames.astype(np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    want = (g[:, None] >> np.arange(32, dtype=np.uint64)[None, :]) & np.uint64(1)      # bit j of frame f = bit j of word 0
+    assert (bits[:, :32] == want).all() and (bits[:, 32:] == 0).all()
+
+
+def test_dump_outputs_of_many_shards_stay_bounded(tmp_path):
+    import bench
+    F, n, world = 1 << 20, 280, 8
+    for s in range(world):        # each rank of the job writes its own shard into the same directory
+        bench.dump_outputs(_fake_batch(F, n, world, [s]), str(tmp_path))
+    names = os.listdir(tmp_path)
+    assert len(names) == 4 * world and all(f.startswith("shard") for f in names)
+    assert sum(os.path.getsize(tmp_path / f) for f in names) < 64 << 20
+    frames = np.load(tmp_path / "shard5_frames.npy")
+    assert frames.min() >= 5 * F and frames.max() < 6 * F
+    assert np.load(tmp_path / "shard5_ok.npy").shape in ((F,), frames.shape)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain run times the headline alone (no side leg, no CPU baseline); --dump-outputs writes the last step's words"""
+    import subprocess
+    F = 1 << 14
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", str(F),
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().split("\n")[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["dtype"] == "f32"
+    assert abs(line["value"] - F / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    assert "legs" not in line and line["cpu_baseline"] is None
+    ok, its, frames, bits = (np.load(tmp_path / "out" / (k + ".npy")) for k in ("ok", "iters", "frames", "bits"))
+    assert ok.shape == its.shape == (F,) and 0 <= its.min() and its.max() <= 50
+    assert abs((1 - ok.mean()) - line["fer"]) < 0.05
+    import acg_alp_ldpc_amd as A
+    H = A.read_pcm(os.path.join(ROOT, "data", "H05.txt"))
+    G, _ = H.get_orthogonal()
+    cws = A.gen_random_codewords(G, 8192, 239239239)
+    sel = ok[frames.astype(np.int64)] == 1
+    same = (bits[sel] == cws[frames.astype(np.int64)[sel] % len(cws)]).all(axis=1)
+    assert sel.sum() > 0.5 * len(frames) and same.mean() > 0.99
+
+
 def test_usable_cores_reads_affinity_not_cpu_count(monkeypatch):
     import bench
     monkeypatch.setattr(os, "cpu_count", lambda: 256)
