@@ -837,6 +837,13 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     }
     d->L = L;
     if (!bp_layout_build(c, L, d->lay)) return 3;
+    // fp32 sum-product wave-group kernels with register LLRs: degree-1 variables absorbed into their checks
+    // (BpLayout::n_apass, BpPass::check_abs); taken when the absorbed layout runs that kernel variant
+    if (!blockmode && !pair && !d->f64 && d->p.algo != ACG_LDPC_BP_MINSUM && d->maxd <= 8 && getenv("ACG_BP_NO_ABSORB") == nullptr) {
+        BpLayout la;
+        if (!bp_layout_build(c, L, la, BP_MAX_APASS)) return 3;
+        if (la.n_apass > 0 && la.n_vpass <= 12 && (size_t) std::max(la.a_words, (c.n + 3) & ~3) * 4 <= 65535) d->lay = std::move(la);
+    }
     BpLayout &lay = d->lay;
     const int nwords = (c.n + 31) / 32;
     // the MC path stages n symbols in the message array before clearing it
@@ -876,6 +883,9 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     UP32(v_pass, v_pass)
     UP32(v_cnt, v_cnt_ge)
     UP32(lay.v_var, v_var)
+    if (lay.n_apass > 0) {
+        UP32(lay.a_var, a_var)
+    }
 #undef UP32
     if (upload<uint16_t>(lay.v_apos, &p16)) return 10;
     d->dev_allocs.push_back(p16);
@@ -896,6 +906,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     t.nwords = nwords;
     t.llr_words = llr_words;
     t.lds_bytes_per_frame = (int) per_frame;
+    t.n_apass = lay.n_apass;
 
     if (blockmode) {
         if (per_frame + t.idx_lds_bytes > 160 * 1024) {
@@ -1804,8 +1815,9 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
         }
         if (d->lds_block > 64 * 1024) (void) hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block);
         d->kernel[0] = kp;
-        wc = (size_t) frames * d->tab.a_words;
-        wp = (size_t) frames * d->lay.n_vpass * d->L;
+        // absorbed degree-1 variables: their edge words and LLRs follow the message array / the slot-order LLRs
+        wc = (size_t) frames * (d->tab.a_words + d->lay.n_apass * d->L);
+        wp = (size_t) frames * (d->lay.n_vpass + d->lay.n_apass) * d->L;
     }
     void *dc = nullptr, *dv = nullptr, *dp = nullptr;
     int rc = 0;
@@ -1858,14 +1870,22 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
                 const int chk = lay.c_chk[sl];
                 if (chk < 0) continue;
                 const int pss = sl / lay.L, l = sl % lay.L;
-                for (int j = 0; j < d->c.row_ptr[chk + 1] - d->c.row_ptr[chk]; j++)
-                    epos[(size_t) d->c.row_ptr[chk] + j] = (size_t) lay.c_off[pss] + (size_t) j * lay.L + l;
+                const int q = pss - (lay.n_cpass - lay.n_apass);  // >= 0: absorbed pass, its last edge is the register word
+                const int deg = d->c.row_ptr[chk + 1] - d->c.row_ptr[chk];
+                for (int j = 0; j < deg; j++)
+                    epos[(size_t) d->c.row_ptr[chk] + j] = (q >= 0 && j == deg - 1)
+                                                               ? (size_t) d->tab.a_words + (size_t) q * lay.L + l
+                                                               : (size_t) lay.c_off[pss] + (size_t) j * lay.L + l;
             }
             for (int sl = 0; sl < lay.n_vpass * lay.L; sl++)
                 if (lay.v_var[sl] >= 0) vslot[lay.v_var[sl]] = (size_t) sl;
+            for (int sl = 0; sl < lay.n_apass * lay.L; sl++)
+                if (lay.a_var[sl] >= 0) vslot[lay.a_var[sl]] = (size_t) lay.n_vpass * lay.L + sl;
         }
+        const size_t cstride = (size_t) d->tab.a_words + (size_t) d->lay.n_apass * d->L;
+        const size_t pstride = (size_t) (d->lay.n_vpass + d->lay.n_apass) * d->L;
         for (int f = 0; f < frames; f++) {
-            auto eidx = [&](int e) { return fused ? (size_t) f * d->tab.a_words + epos[e] : (size_t) e * 64 + f; };
+            auto eidx = [&](int e) { return fused ? (size_t) f * cstride + epos[e] : (size_t) e * 64 + f; };
             for (int e = 0; e < E; e++) {
                 c2v[(size_t) f * E + e] = get(hc, eidx(e));
                 const double w = get_v2c(eidx(e));
@@ -1881,7 +1901,7 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
                 // and channel LLR (slot order dump), checks ascending
                 double sum = 0;
                 for (int k = d->c.col_ptr[v]; k < d->c.col_ptr[v + 1]; k++) sum += c2v[(size_t) f * E + d->c.col_edge[k]];
-                post[(size_t) f * n + v] = get(hp, (size_t) f * d->lay.n_vpass * d->L + vslot[v]) + sum;
+                post[(size_t) f * n + v] = get(hp, (size_t) f * pstride + vslot[v]) + sum;
             }
         }
     } while (0);

@@ -163,6 +163,17 @@ struct BpPass {
         return S;
     }
 
+    // the same for a pass with an absorbed variable (BpLayout::n_apass): D - 1 rows of words, then the register word aw
+    static __device__ __forceinline__ U syn_abs(const T *__restrict__ Ap, U aw) {
+        T x[D];
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j) x[j] = Ap[j * L];
+        U S = aw;
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j) S ^= B::to(x[j]);
+        return S;
+    }
+
     // check -> variable (bp.h:171-181 / CNode::message bp.h:49-57), in place.  cnt[j] = number of
     // checks of degree >= j: slot < cnt[j+1] <=> edge j of this lane's check exists.
     // Returns the XOR of the incoming words: its LSB is the syndrome bit of this lane's check (padding words are +0).
@@ -231,6 +242,50 @@ struct BpPass {
             // upper or lower 32 lanes are all masked off issues in one pass on the SIMD-32 — measured faster
             // than a branch-free variant that stores padding to a dump word
             if (write && slot < cnt[j + 1]) Ap[j * L] = B::from(ob);
+        }
+        return S;
+    }
+
+    // Sum-product check sweep of a pass whose edge D - 1 is an absorbed degree-1 variable (BpLayout::n_apass): edges
+    // 0 .. D-2 are message words as in check() (a check of lower degree has padding rows before the absorbed edge: +0
+    // added to the non-negative phi sums changes no bit, so every sum is the one check() forms), edge D - 1 is the
+    // variable's v->c word aw, held in a register.  That word never changes but for its LSB: the variable has no other
+    // check, so its v->c message is llr + (empty sum), i.e. F(|llr|) with the sign of llr <= 0 (bp.h:78-82), built once per
+    // frame.  The c->v word R of edge D - 1 is not stored; it gives the variable's posterior hard decision llr + R <= 0
+    // (bp.h:85-90,193, NaN -> 0), which becomes the LSB of aw, exactly as the variable sweep would have set it.  Lanes
+    // without a check (slot >= cnt[1]) keep aw = +0.  r_out: R (debug trace).
+    static __device__ __forceinline__ U check_abs(T *__restrict__ Ap, int slot, const int *cnt, bool write, U &aw, T allr, T &r_out) {
+        T x[D];
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j) x[j] = Ap[j * L];
+        x[D - 1] = B::from(aw);
+        U S = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) S ^= B::to(x[j]);
+        T out[D];
+        T mag[D], pre[D];
+        T s = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            mag[j] = B::from(B::to(x[j]) & ~SIGN & ~ONE);
+            pre[j] = s;
+            s += mag[j];
+        }
+        T suf = 0;
+#pragma unroll
+        for (int j = D - 1; j >= 0; --j) {
+            out[j] = Dom<T>::phi(pre[j] + suf);
+            suf += mag[j];
+        }
+#pragma unroll
+        for (int j = 0; j < D - 1; ++j) {
+            const U ob = (B::to(out[j]) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN);
+            if (write && slot < cnt[j + 2]) Ap[j * L] = B::from(ob);  // edge j is a message word of checks of degree >= j + 2
+        }
+        if (write && slot < cnt[1]) {
+            const T R = B::from((B::to(out[D - 1]) & ~SIGN) | ((S ^ aw) & SIGN));
+            r_out = R;
+            aw = (aw & ~ONE) | ((allr + R <= (T) 0) ? ONE : (U) 0);
         }
         return S;
     }
@@ -346,6 +401,20 @@ struct BpCore {
     // would push the whole object into scratch); it is handed to the sweeps by reference
     using LlrRegs = T[NVP > 0 ? NVP : 1];
     using VarIds = int[NVP > 0 ? NVP : 1];  // variable id of (pass, this lane): frame independent, loaded once per kernel
+    // absorbed degree-1 variables (BpPass::check_abs): per absorbed pass q, the variable's channel LLR and its v->c word
+    // (hard decision in the LSB) in registers of its check's lane.  Instances with register LLRs, fp32 sum-product only
+    // (the host absorbs nothing for the others) and wave-group kernels (L <= 64).
+    static constexpr int NAP = (NVP > 0 && ALGO == 0 && sizeof(T) == 4 && MAXD <= 8 && L <= 64) ? BP_MAX_APASS : 0;
+    using AbsLlr = T[NAP > 0 ? NAP : 1];
+    using AbsWord = U[NAP > 0 ? NAP : 1];
+    __device__ __forceinline__ int n_apass() const { return NAP > 0 ? t.n_apass : 0; }
+    __device__ __forceinline__ int abs_var(int q) const { return t.a_var[q * L + l]; }
+    // the constant v->c word of an absorbed variable: var_init's word (its first sweep) for a variable of degree 1
+    static __device__ __forceinline__ U abs_word(T llr) {
+        const T ax = B::from(B::to(llr) & ~SIGN);
+        const T mg = Dom<T>::phi(ax);
+        return (B::to(mg) & ~SIGN & ~ONE) | ((llr <= (T) 0) ? (ONE | SIGN) : (U) 0);
+    }
     __device__ __forceinline__ int var_id(const VarIds &vi, int p) const { return NVP > 0 ? vi[p] : t.v_var[p * L + l]; }
     __device__ __forceinline__ T get_llr(const LlrRegs &lr, int p, int slot) const { return NVP > 0 ? lr[p] : LLR[slot]; }
     __device__ __forceinline__ void set_llr(LlrRegs &lr, int p, int slot, T v) {
@@ -363,9 +432,20 @@ struct BpCore {
     }
 
     // XOR of the hard-decision bits of each check's variables -> true if any check of this lane fails
-    __device__ __forceinline__ bool syndrome_bad() const {
+    __device__ __forceinline__ bool syndrome_bad(const AbsWord &aw) const {
         U acc = 0;
-        for (int p = 0; p < t.n_cpass; ++p) {
+        const int nc = t.n_cpass - n_apass();
+#pragma unroll
+        for (int q = 0; q < NAP; ++q) {
+            if (q < n_apass()) {
+                const int md = sload(t.c_pass, 2 * (nc + q));
+                const T *Ap = A + sload(t.c_pass, 2 * (nc + q) + 1) + l;
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::syn_abs(Ap, aw[q])
+                ACG_PASS_SWITCH(md, ACG_CALL)
+#undef ACG_CALL
+            }
+        }
+        for (int p = 0; p < nc; ++p) {
             const int md = sload(t.c_pass, 2 * p);
             const T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
             if (MAXD <= 8 || md <= 8) {
@@ -383,9 +463,11 @@ struct BpCore {
 
     // Returns the OR over this lane's checks of the XOR of the incoming words: bit 0 set <=> one of them fails the syndrome of
     // the hard decisions that ride in the v->c words (the estimate of the previous variable sweep).
-    __device__ __forceinline__ U check_phase(bool write) {
+    // aw / al / ar: the absorbed variables' words, LLRs and (debug trace) c->v messages, see BpPass::check_abs
+    __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar) {
         U acc = 0;
-        for (int p = 0; p < t.n_cpass; ++p) {
+        const int nc = t.n_cpass - n_apass();
+        for (int p = 0; p < nc; ++p) {
             const int md = sload(t.c_pass, 2 * p);
             T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
             const int slot = p * L + l;
@@ -397,7 +479,29 @@ struct BpCore {
                 acc |= check_generic(Ap, slot, md, write);
             }
         }
+        // the absorbed passes (the last ones) with their register operands addressed directly: unrolled over q
+#pragma unroll
+        for (int q = 0; q < NAP; ++q) {
+            if (q < n_apass()) {
+                const int p = nc + q;
+                const int md = sload(t.c_pass, 2 * p);
+                T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
+                const int slot = p * L + l;
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q])
+                ACG_PASS_SWITCH(md, ACG_CALL)
+#undef ACG_CALL
+            }
+        }
         return acc;
+    }
+    __device__ __forceinline__ bool syndrome_bad() const {
+        AbsWord aw = {};
+        return syndrome_bad(aw);
+    }
+    __device__ __forceinline__ U check_phase(bool write) {
+        AbsWord aw = {};
+        AbsLlr al = {}, ar = {};
+        return check_phase(write, aw, al, ar);
     }
 
     __device__ __forceinline__ void var_phase(const LlrRegs &lr, bool write) {
@@ -676,14 +780,25 @@ struct BpCore {
     }
 
     // pack the frame's hard decisions into OB[0..nwords)
-    __device__ __forceinline__ void pack_bits(const LlrRegs &lr, const VarIds &vi) {
+    __device__ __forceinline__ void pack_bits(const LlrRegs &lr, const VarIds &vi, const AbsWord &aw) {
         for (int w = l; w < t.nwords; w += L) OB[w] = 0u;
         group_sync<L>();
         for (int p = 0; p < t.n_vpass; ++p) {
             const int v = var_id(vi, p);
             if (v >= 0 && hard_bit(lr, p)) atomicOr(&OB[v >> 5], 1u << (v & 31));
         }
+#pragma unroll
+        for (int q = 0; q < NAP; ++q) {
+            if (q < n_apass()) {
+                const int v = abs_var(q);
+                if (v >= 0 && (aw[q] & ONE)) atomicOr(&OB[v >> 5], 1u << (v & 31));
+            }
+        }
         group_sync<L>();
+    }
+    __device__ __forceinline__ void pack_bits(const LlrRegs &lr, const VarIds &vi) {
+        AbsWord aw = {};
+        pack_bits(lr, vi, aw);
     }
 };
 
@@ -745,6 +860,15 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
         lr[p] = (T) 0;
         vi[p] = (NVP > 0 && p < t.n_vpass) ? t.v_var[p * L + l] : -1;
     }
+    // absorbed degree-1 variables (BpPass::check_abs): LLR, v->c word, c->v word (debug trace only) per absorbed pass
+    typename Core::AbsLlr al, ar;
+    typename Core::AbsWord aw;
+#pragma unroll
+    for (int q = 0; q < (Core::NAP > 0 ? Core::NAP : 1); ++q) {
+        al[q] = (T) 0;
+        ar[q] = (T) 0;
+        aw[q] = 0;
+    }
 
     // Frames are handed out dynamically: a wavefront draws chunks of CHUNK consecutive frame indices from one
     // global counter (one atomic per CHUNK frames) and deals them to its groups as they become free.  With early
@@ -783,7 +907,7 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
         if (__ballot(out_now || fail_now) != 0ull) {
             if (out_now) {
                 if (MERGED) core.pack_bits_mask(hard, vi);
-                else core.pack_bits(lr, vi);
+                else core.pack_bits(lr, vi, aw);
             }
             else if (fail_now) {
                 for (int w = l; w < t.nwords; w += L) OB[w] = 0u;  // reference returns an empty vector, bp.h:198
@@ -874,9 +998,7 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
             int my_ham = 0;
             if (need_init) {
                 // channel LLRs (channel.h:14-16) into slot order
-                for (int p = 0; p < t.n_vpass; ++p) {
-                    const int slot = p * L + l;
-                    const int v = core.var_id(vi, p);
+                auto chan_llr = [&](const int v) -> T {
                     T llr = (T) 0;
                     if (v >= 0) {
                         if (MC) {
@@ -896,7 +1018,17 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
                             llr = (T) ((double) yv * (a.inv_var2 * Dom<T>::scale));
                         }
                     }
-                    core.set_llr(lr, p, slot, llr);
+                    return llr;
+                };
+                for (int p = 0; p < t.n_vpass; ++p) core.set_llr(lr, p, p * L + l, chan_llr(core.var_id(vi, p)));
+                // absorbed variables: LLR and the constant v->c word (+0 for a lane without one)
+#pragma unroll
+                for (int q = 0; q < Core::NAP; ++q) {
+                    if (q < core.n_apass()) {
+                        const int v = core.abs_var(q);
+                        al[q] = chan_llr(v);
+                        aw[q] = v >= 0 ? Core::abs_word(al[q]) : 0;
+                    }
                 }
             }
             wave_sync();  // all reads of the staged symbols are done before A is cleared
@@ -957,7 +1089,9 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
     for (;;) {
         // ---- syndrome of the estimate produced by the previous variable phase -----------------
         // (a group that has not been initialised yet has it == 0 and ignores the result)
-        const bool bad = group_any<L>(core.syndrome_bad(), g);
+        // fixed work: once every group of the wave has latched its output (or is idle) the syndrome feeds nothing
+        const bool pend = active && !latched && it > 0;
+        const bool bad = __ballot(pend) != 0ull ? group_any<L>(core.syndrome_bad(aw), g) : true;
         const bool conv = active && it > 0 && it <= a.max_iter && !bad;     // bp.h:195 (max_iter = 0: never)
         const bool out_now = conv && !latched;
         const bool finish = active && ((a.early_exit && conv) || it >= a.max_iter);
@@ -971,16 +1105,27 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
         if (__ballot(active) == 0ull) break;
         init_frames();
         // ---- one flooding iteration (bp.h:186-188) -------------------------------------------
-        core.check_phase(active);
+        core.check_phase(active, aw, al, ar);
         wave_sync();
-        if (DBG && active && it == a.max_iter - 1 && a.dbg_c2v)
-            for (int w = l; w < t.a_words; w += L) reinterpret_cast<T *>(a.dbg_c2v)[(size_t) frame * t.a_words + w] = A[w];
+        // debug dumps: per frame the message array, then the absorbed edges' words (absorbed pass q, lane l at a_words + q*L + l);
+        // LLRs in slot order, then the absorbed variables' (n_vpass*L + q*L + l)
+        const int dbg_cw = t.a_words + core.n_apass() * L, dbg_pw = (t.n_vpass + core.n_apass()) * L;
+        if (DBG && active && it == a.max_iter - 1 && a.dbg_c2v) {
+            for (int w = l; w < t.a_words; w += L) reinterpret_cast<T *>(a.dbg_c2v)[(size_t) frame * dbg_cw + w] = A[w];
+            for (int q = 0; q < Core::NAP; ++q)
+                if (q < core.n_apass()) reinterpret_cast<T *>(a.dbg_c2v)[(size_t) frame * dbg_cw + t.a_words + q * L + l] = ar[q];
+        }
         core.var_phase(lr, active);
         wave_sync();
         if (DBG && active && it == a.max_iter - 1 && a.dbg_v2c) {
-            for (int w = l; w < t.a_words; w += L) reinterpret_cast<T *>(a.dbg_v2c)[(size_t) frame * t.a_words + w] = A[w];
+            for (int w = l; w < t.a_words; w += L) reinterpret_cast<T *>(a.dbg_v2c)[(size_t) frame * dbg_cw + w] = A[w];
             for (int p = 0; p < t.n_vpass; ++p)
-                reinterpret_cast<T *>(a.dbg_post)[(size_t) frame * (t.n_vpass * L) + p * L + l] = core.get_llr(lr, p, p * L + l);
+                reinterpret_cast<T *>(a.dbg_post)[(size_t) frame * dbg_pw + p * L + l] = core.get_llr(lr, p, p * L + l);
+            for (int q = 0; q < Core::NAP; ++q)
+                if (q < core.n_apass()) {
+                    reinterpret_cast<T *>(a.dbg_v2c)[(size_t) frame * dbg_cw + t.a_words + q * L + l] = FpBits<T>::from(aw[q]);
+                    reinterpret_cast<T *>(a.dbg_post)[(size_t) frame * dbg_pw + (t.n_vpass + q) * L + l] = al[q];
+                }
         }
         it += 1;
     }

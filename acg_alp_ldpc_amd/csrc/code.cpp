@@ -182,7 +182,7 @@ bool code_generator(const Code &c, uint8_t *G) {
 }
 
 // ---------------------------------------------------------------- BP LDS layout
-bool bp_layout_build(const Code &c, int L, BpLayout &o) {
+bool bp_layout_build(const Code &c, int L, BpLayout &o, int max_apass) {
     o = BpLayout();
     o.L = L;
     o.max_cdeg = c.max_cdeg;
@@ -217,16 +217,64 @@ bool bp_layout_build(const Code &c, int L, BpLayout &o) {
     }
 
     o.n_cpass = (m + L - 1) / L;
-    o.n_vpass = (n + L - 1) / L;
+    // Absorbed degree-1 variables: a check whose LAST edge (highest column) is its only degree-1 variable may keep that
+    // variable in registers of its own lane (BpPass::check_abs).  The variable's v->c word never changes (llr + empty
+    // sum) but for its hard-decision LSB, so it needs neither a message word, nor an index entry, nor a variable pass.
+    // Only whole check passes at the END of the pass list are absorbed (at most max_apass): inside the stable
+    // by-degree order, candidates go behind the other checks of their degree (padding and message values do not
+    // depend on the order within a degree), and the trailing passes whose every check is a candidate are taken.
+    if (max_apass > 0 && L < 256) {
+        std::vector<int> deg1_of(m, -1), n_deg1(m, 0);
+        for (int j = 0; j < n; j++)
+            if (vdeg(j) == 1) {
+                const int e = c.col_edge[c.col_ptr[j]];
+                const int chk = (int) (std::upper_bound(c.row_ptr.begin(), c.row_ptr.end(), e) - c.row_ptr.begin()) - 1;
+                deg1_of[chk] = j;
+                n_deg1[chk]++;
+            }
+        std::vector<char> cand(m, 0);
+        for (int i = 0; i < m; i++)
+            cand[i] = n_deg1[i] == 1 && cdeg(i) >= 1 && c.edge_var[c.row_ptr[i + 1] - 1] == deg1_of[i];
+        std::vector<int> aorder(corder);
+        std::stable_sort(aorder.begin(), aorder.end(), [&](int a, int b) {
+            return cdeg(a) != cdeg(b) ? cdeg(a) > cdeg(b) : (!cand[a] && cand[b]);
+        });
+        int na = 0;
+        while (na < max_apass && na < o.n_cpass) {
+            const int p = o.n_cpass - 1 - na;
+            bool all = true;
+            for (int s = p * L; s < std::min(m, (p + 1) * L) && all; s++) all = cand[aorder[s]];
+            if (!all) break;
+            na++;
+        }
+        if (na > 0) {
+            corder = aorder;
+            o.n_apass = na;
+            o.a_var.assign((size_t) na * L, -1);
+            std::vector<char> gone(n, 0);
+            for (int s = (o.n_cpass - na) * L; s < m; s++) {
+                const int v = deg1_of[corder[s]];
+                o.a_var[(size_t) s - (size_t) (o.n_cpass - na) * L] = v;
+                gone[v] = 1;
+                o.n_absorbed++;
+            }
+            std::vector<int> rest;
+            for (int v : vorder)
+                if (!gone[v]) rest.push_back(v);
+            vorder = rest;
+        }
+    }
+    const int nv = (int) vorder.size();  // variables that take part in the variable sweep
+    o.n_vpass = (nv + L - 1) / L;
     o.c_chk.assign((size_t) o.n_cpass * L, -1);
     o.v_var.assign((size_t) o.n_vpass * L, -1);
     for (int s = 0; s < m; s++) o.c_chk[s] = corder[s];
-    for (int s = 0; s < n; s++) o.v_var[s] = vorder[s];
+    for (int s = 0; s < nv; s++) o.v_var[s] = vorder[s];
     o.c_cnt_ge.assign(c.max_cdeg + 2, 0);
     o.v_cnt_ge.assign(c.max_vdeg + 2, 0);
     for (int i = 0; i < m; i++)
         for (int d = 0; d <= cdeg(i); d++) o.c_cnt_ge[d]++;
-    for (int j = 0; j < n; j++)
+    for (int j : vorder)
         for (int d = 0; d <= vdeg(j); d++) o.v_cnt_ge[d]++;
 
     // A layout
@@ -236,15 +284,18 @@ bool bp_layout_build(const Code &c, int L, BpLayout &o) {
     o.c_off.resize(o.n_cpass);
     for (int p = 0; p < o.n_cpass; p++) {
         int md = cdeg(corder[(size_t) p * L]);  // sorted descending: first slot of the pass is the max
+        // absorbed pass: edge md-1 of every lane is the register word; a check of lower degree has padding rows
+        // between its last message word and it (adding +0 to the non-negative phi sums changes no bit)
+        const bool absorbed = p >= o.n_cpass - o.n_apass;
         o.c_maxdeg[p] = md;
         o.c_off[p] = off;
         for (int l = 0; l < L; l++) {
             int s = p * L + l;
             if (s >= m) break;
             int chk = corder[s];
-            for (int j = 0; j < cdeg(chk); j++) edge_pos[c.row_ptr[chk] + j] = off + j * L + l;
+            for (int j = 0; j < cdeg(chk) - (absorbed ? 1 : 0); j++) edge_pos[c.row_ptr[chk] + j] = off + j * L + l;
         }
-        off += md * L;
+        off += (absorbed ? md - 1 : md) * L;
     }
     o.zero_pos = off;
     o.a_words = (off + 1 + 3) & ~3;
@@ -267,7 +318,7 @@ bool bp_layout_build(const Code &c, int L, BpLayout &o) {
     for (int p = 0; p < o.n_vpass; p++)
         for (int l = 0; l < L; l++) {
             int s = p * L + l;
-            if (s >= n) break;
+            if (s >= nv) break;
             int v = vorder[s];
             for (int k = 0; k < vdeg(v); k++)
                 o.v_apos[(size_t) o.v_idx_off[p] + (size_t) k * L + l] = (uint16_t) edge_pos[c.col_edge[c.col_ptr[v] + k]];

@@ -20,7 +20,13 @@ struct BpTables {
     int32_t m, n, nwords;      // nwords = (n+31)/32 packed output words per frame
     int32_t llr_words;         // n_vpass * L
     int32_t lds_bytes_per_frame;
+    // absorbed degree-1 variables (BpLayout::n_apass): the last n_apass check passes; 0 = none
+    const int32_t *a_var;      // [n_apass*L] variable id per (absorbed pass, lane), -1 none
+    int32_t n_apass;
 };
+
+// most absorbed check passes a fused kernel keeps in registers (two VGPRs per pass and lane)
+constexpr int BP_MAX_APASS = 2;
 
 // per-launch MC statistics (one row per launch; experiment.h:25-68)
 enum { MC_CORRECT = 0, MC_PSEUDO, MC_TOTAL, MC_HAM, MC_HAM_OK, MC_HAM_WRONG, MC_ITERS, MC_NCOUNTERS };

@@ -38,6 +38,12 @@ struct BpLayout {
     std::vector<int32_t> v_var;             // [n_vpass*L] variable id per slot, -1 = none
     std::vector<uint16_t> v_apos;           // [sum_p v_maxdeg[p]*L]
     int v_apos_len = 0;
+    // Absorbed degree-1 variables (bp_layout_build with max_apass > 0): the last n_apass check passes hold checks whose
+    // last edge is their only degree-1 variable.  That edge lives in registers of the check's lane (edge index
+    // c_maxdeg[p] - 1 of the pass), not in A; the pass has c_maxdeg[p] - 1 rows of message words.  Absorbed variables
+    // are in no variable pass (v_var, v_apos, v_cnt_ge count the others only).
+    int n_apass = 0, n_absorbed = 0;
+    std::vector<int32_t> a_var;             // [n_apass*L] absorbed variable of (absorbed pass, lane), -1 = none
 };
 
 // QP-ADMM problem structure (qp_admm.h:13-102) regrouped by "constraint group": one group per
@@ -69,7 +75,7 @@ bool code_read_txt(const char *path, std::vector<uint8_t> &H, int &m, int &n);
 bool code_write_txt(const Code &c, const char *path);
 bool code_generator(const Code &c, uint8_t *G);
 bool code_is_codeword(const Code &c, const uint8_t *bits);
-bool bp_layout_build(const Code &c, int L, BpLayout &out);
+bool bp_layout_build(const Code &c, int L, BpLayout &out, int max_apass = 0);
 void admm_layout_build(Code &c);
 
 // Static placement against LDS bank conflicts.  A wave64 LDS access is served in fixed lane groups and takes as many
