@@ -29,8 +29,9 @@ void set_error(const std::string &msg) { g_err = msg; }
 
 hipError_t bp_launch(const void *kernel, const BpTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
                      hipStream_t s);
-const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant);
+const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat);
 hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s);
+hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s);
 hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,
                        const uint32_t *cw_packed, int64_t n_cw, float sigma, hipStream_t s);
 
@@ -988,10 +989,13 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     d->frames_per_block = waves * fpw;
     d->lds_block = per_frame * fpw * waves + t.idx_lds_bytes;
     const int algo = (d->p.algo == ACG_LDPC_BP_MINSUM) ? 1 : 0;
+    // fixed-work decoders: the instances with the phi fast path (BpCore::SATSKIP; fp32 sum-product, degree <= 8, register
+    // LLRs); ACG_BP_NO_SATSKIP=1 keeps the plain instances (A/B runs)
+    const bool sat = !d->p.early_exit && getenv("ACG_BP_NO_SATSKIP") == nullptr;
     for (int mc = 0; mc < 2; mc++) {
         const int variant = idxlds ? ((llr_regs) ? 2 : 1) : 0;
         d->variant = variant;
-        const void *kp = bp_kernel_ptr(algo, d->f64, d->maxd, L, mc != 0, variant);
+        const void *kp = bp_kernel_ptr(algo, d->f64, d->maxd, L, mc != 0, variant, sat);
         if (!kp) {
             set_error("no kernel instance for this configuration");
             return 3;
@@ -1976,6 +1980,24 @@ static int acg_ldpc_debug_phi_impl(const void *x_host, void *out_host, int32_t n
 
 int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f64) {
     return guarded([&] { return acg_ldpc_debug_phi_impl(x_host, out_host, n, f64); });
+}
+
+static int acg_ldpc_debug_phi_sat_impl(const void *x_host, void *out_host, int32_t n) {
+    float *dx = nullptr;
+    uint32_t *dout = nullptr;
+    HIP_OK(hipMalloc(&dx, 4 * (size_t) n));
+    HIP_OK(hipMalloc(&dout, 12 * (size_t) n));
+    HIP_OK(hipMemcpy(dx, x_host, 4 * (size_t) n, hipMemcpyHostToDevice));
+    HIP_OK(phi_sat_debug_launch(dx, dout, n, nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out_host, dout, 12 * (size_t) n, hipMemcpyDeviceToHost));
+    (void) hipFree(dx);
+    (void) hipFree(dout);
+    return 0;
+}
+
+int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n) {
+    return guarded([&] { return acg_ldpc_debug_phi_sat_impl(x_host, out_host, n); });
 }
 
 }  // extern "C"

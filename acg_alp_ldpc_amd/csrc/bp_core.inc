@@ -145,12 +145,61 @@ __device__ __forceinline__ int sload(const int32_t *p, int i) { return ((sconst_
 // One pass = the L nodes dealt to the L lanes of a frame group.  D (the largest degree in the
 // pass) is a compile-time constant: the D LDS reads are issued back to back, then everything is
 // straight-line register code, then the D LDS writes.  Dispatch on D is a wave-uniform switch.
-template <typename T, int D, int L, int ALGO>
+// SAT: the phi fast path (phi_c / phi_v) in check, check_abs and var_at, for fp32 sum-product (BpCore::SATSKIP)
+template <typename T, int D, int L, int ALGO, bool SAT = false>
 struct BpPass {
     using B = FpBits<T>;
     using U = typename B::U;
     static constexpr U SIGN = B::SIGN;
     static constexpr U ONE = (U) 1;
+
+    // phi where its value is fixed, without evaluating it (in fixed-work runs most frames have converged and their messages
+    // saturated long before the last sweep).  The test sits under the lane's store predicate, so phi runs under
+    // EXEC = (store && not saturated): a 32-lane half of the wavefront with no such lane issues it in one pass, or none.
+    //   check side: an exclude-self sum (>= 0) that is exactly +0 (integer test: NaN and denormals fail) -> +inf
+    //   variable side: a magnitude ax >= 66 (the saturation point, +inf included; NaN fails) -> +0
+    static __device__ __forceinline__ T phi_c(T s) {
+        T o = (T) INFINITY;
+        if (B::to(s) != 0) o = Dom<T>::phi(s);
+        return o;
+    }
+    static __device__ __forceinline__ T phi_v(T ax) {
+        T o = (T) 0;
+        if (!(ax >= (T) 66)) o = Dom<T>::phi(ax);
+        return o;
+    }
+
+    // check(), sum-product with the fast path: the exclude-self sums first, phi per edge under its store predicate
+    static __device__ __forceinline__ U check_sat(T *__restrict__ Ap, int slot, const int *cnt, bool write) {
+        T x[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
+        U S = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) S ^= B::to(x[j]);
+        T mag[D], pre[D], es[D];
+        T s = 0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            mag[j] = B::from(B::to(x[j]) & ~SIGN & ~ONE);
+            pre[j] = s;
+            s += mag[j];
+        }
+        T suf = 0;
+#pragma unroll
+        for (int j = D - 1; j >= 0; --j) {
+            es[j] = pre[j] + suf;
+            suf += mag[j];
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            if (write && slot < cnt[j + 1]) {
+                const T o = phi_c(es[j]);
+                Ap[j * L] = B::from((B::to(o) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN));
+            }
+        }
+        return S;
+    }
 
     // syndrome contribution of the checks in this pass (LSB of the XOR of the v->c words)
     static __device__ __forceinline__ U syn(const T *__restrict__ Ap) {
@@ -181,6 +230,7 @@ struct BpPass {
     // pass instead of one compare + EXEC mask + branch per edge
     template <bool UNI = false>
     static __device__ __forceinline__ U check(T *__restrict__ Ap, int slot, const int *cnt, bool write, T ms_scale) {
+        if constexpr (SAT && ALGO == 0 && !UNI) return check_sat(Ap, slot, cnt, write);
         T x[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
@@ -272,6 +322,26 @@ struct BpPass {
             s += mag[j];
         }
         T suf = 0;
+        if constexpr (SAT) {  // exclude-self sums; phi (fast path) per edge under its store predicate
+#pragma unroll
+            for (int j = D - 1; j >= 0; --j) {
+                out[j] = pre[j] + suf;
+                suf += mag[j];
+            }
+#pragma unroll
+            for (int j = 0; j < D - 1; ++j) {
+                if (write && slot < cnt[j + 2]) {
+                    const T o = phi_c(out[j]);
+                    Ap[j * L] = B::from((B::to(o) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN));
+                }
+            }
+            if (write && slot < cnt[1]) {
+                const T R = B::from((B::to(phi_c(out[D - 1])) & ~SIGN) | ((S ^ aw) & SIGN));
+                r_out = R;
+                aw = (aw & ~ONE) | ((allr + R <= (T) 0) ? ONE : (U) 0);
+            }
+            return S;
+        }
 #pragma unroll
         for (int j = D - 1; j >= 0; --j) {
             out[j] = Dom<T>::phi(pre[j] + suf);
@@ -324,6 +394,22 @@ struct BpPass {
         const U hard = (total <= (T) 0) ? ONE : (U) 0;      // bp.h:193 (NaN -> 0)
         const U hard_neg = hard | SIGN;
         T suf = 0;
+        if constexpr (SAT && ALGO == 0 && !UNI) {  // phi (fast path) per edge under its store predicate
+            T xs[D];
+#pragma unroll
+            for (int k = D - 1; k >= 0; --k) {
+                xs[k] = llr + (pre[k] + suf);
+                suf += c[k];
+            }
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                if (write && slot < cnt[k + 1]) {
+                    const T mg = phi_v(B::from(B::to(xs[k]) & ~SIGN));
+                    at<BYTES>(A, pos[k]) = B::from((B::to(mg) & ~SIGN & ~ONE) | ((xs[k] <= (T) 0) ? hard_neg : hard));
+                }
+            }
+            return hard;
+        }
         U ob[D];
 #pragma unroll
         for (int k = D - 1; k >= 0; --k) {
@@ -382,7 +468,8 @@ struct BpPass {
 // pass index -> s_set_gpr_idx), which takes them out of LDS: 4.8 -> 3.6 KB per frame for H05 at L=32, i.e. 5 instead
 // of 4 resident workgroups per CU.  NVP = 0 (more than NVP variable passes): LLRs in LDS.
 // IDXB: the table behind IDX holds byte offsets into A (see BpPass::at)
-template <typename T, int MAXD, int L, int ALGO, bool IDXLDS, int NVP, bool IDXB = false>
+// SAT: the phi fast path in the sweeps, see SATSKIP
+template <typename T, int MAXD, int L, int ALGO, bool IDXLDS, int NVP, bool IDXB = false, bool SAT = false>
 struct BpCore {
     using B = FpBits<T>;
     using U = typename B::U;
@@ -415,6 +502,10 @@ struct BpCore {
         const T mg = Dom<T>::phi(ax);
         return (B::to(mg) & ~SIGN & ~ONE) | ((llr <= (T) 0) ? (ONE | SIGN) : (U) 0);
     }
+    // phi fast path (BpPass::phi_c / phi_v) of the fp32 sum-product wave-group sweeps.  Its own instances, which the host
+    // takes for fixed-work decoders only: with early exit few frames stay long enough to saturate, and the test and its
+    // EXEC-mask branch per edge (2 vector + 3 scalar instructions) would cost more than the skipped phi evaluations save
+    static constexpr bool SATSKIP = SAT && ALGO == 0 && sizeof(T) == 4 && L <= 64;
     __device__ __forceinline__ int var_id(const VarIds &vi, int p) const { return NVP > 0 ? vi[p] : t.v_var[p * L + l]; }
     __device__ __forceinline__ T get_llr(const LlrRegs &lr, int p, int slot) const { return NVP > 0 ? lr[p] : LLR[slot]; }
     __device__ __forceinline__ void set_llr(LlrRegs &lr, int p, int slot, T v) {
@@ -472,7 +563,7 @@ struct BpCore {
             T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
             const int slot = p * L + l;
             if (MAXD <= 8 || md <= 8) {
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::check(Ap, slot, ccnt, write, ms_scale)
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check(Ap, slot, ccnt, write, ms_scale)
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             } else {
@@ -487,7 +578,7 @@ struct BpCore {
                 const int md = sload(t.c_pass, 2 * p);
                 T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
                 const int slot = p * L + l;
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q])
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q])
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             }
@@ -512,7 +603,7 @@ struct BpCore {
             const T llr = get_llr(lr, p, slot);
             const uint16_t *ip = IDX + ioff + l;
             if (MAXD <= 8 || md <= 8) {
-#define ACG_CALL(D) BpPass<T, D, L, ALGO>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write)
+#define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write)
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             } else {
@@ -830,10 +921,11 @@ constexpr int bp_min_waves() {
 // DBG (tests only, acg_ldpc_debug_bp_trace): the raw message words of a frame are copied out of LDS after the check
 // sweep and after the variable sweep of its LAST iteration (a.dbg_c2v / a.dbg_v2c: [frame][a_words]) together with the
 // channel LLRs in slot order (a.dbg_post: [frame][n_vpass * L]); the product instances are compiled with DBG = false.
-template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>
-__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {
+// SAT: the phi fast path of the sweeps (BpCore::SATSKIP; fixed-work decoders), see sat::bp_fused_kernel
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG, bool SAT>
+__device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using Core = BpCore<T, MAXD, L, ALGO, IDXLDS, NVP, IDXLDS && ACG_IDX_BYTES>;  // the LDS copy of the index table is in byte offsets
+    using Core = BpCore<T, MAXD, L, ALGO, IDXLDS, NVP, IDXLDS && ACG_IDX_BYTES, SAT>;  // the LDS copy of the index table is in byte offsets
     constexpr int FPW = 64 / L;  // frames in flight per wavefront
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -1141,3 +1233,16 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
     }
 }
 
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>
+__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {
+    bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, false>(t, a);
+}
+
+// the same kernel with the phi fast path (BpCore::SATSKIP), for fixed-work decoders.  Same name and template arguments in a
+// namespace of its own: profiles and tools that look a kernel up by "bp_fused_kernel<...>" find either instance.
+namespace sat {
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>
+__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {
+    bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, true>(t, a);
+}
+}  // namespace sat

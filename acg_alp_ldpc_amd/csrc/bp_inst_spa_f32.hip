@@ -10,8 +10,12 @@ constexpr int BP_NVP = 12;  // register-resident LLRs for codes with <= 12 varia
 
 // variant: 0 = index table read from global, LLR in LDS; 1 = index table in LDS, LLR in LDS;
 //          2 = index table in LDS, LLR in registers (degree <= 8 kernels only)
+// sat: the phi fast path (BpCore::SATSKIP), instantiated for variant 2
 template <int MAXD, int L>
-static const void *kptr(bool mc, int variant) {
+static const void *kptr(bool mc, int variant, bool sat) {
+    if (MAXD <= 8 && variant == 2 && sat)
+        return mc ? (const void *) sat::bp_fused_kernel<float, MAXD, L, 0, true, true, (MAXD <= 8 ? BP_NVP : 0)>
+                  : (const void *) sat::bp_fused_kernel<float, MAXD, L, 0, false, true, (MAXD <= 8 ? BP_NVP : 0)>;
     if (MAXD <= 8 && variant == 2)
         return mc ? (const void *) bp_fused_kernel<float, MAXD, L, 0, true, true, (MAXD <= 8 ? BP_NVP : 0)>
                   : (const void *) bp_fused_kernel<float, MAXD, L, 0, false, true, (MAXD <= 8 ? BP_NVP : 0)>;
@@ -23,20 +27,20 @@ static const void *kptr(bool mc, int variant) {
 }
 
 template <int MAXD>
-static const void *kptr_l(int L, bool mc, int variant) {
+static const void *kptr_l(int L, bool mc, int variant, bool sat) {
     switch (L) {
-        case 64: return kptr<MAXD, 64>(mc, variant);
-        case 32: return kptr<MAXD, 32>(mc, variant);
-        case 16: return kptr<MAXD, 16>(mc, variant);
+        case 64: return kptr<MAXD, 64>(mc, variant, sat);
+        case 32: return kptr<MAXD, 32>(mc, variant, sat);
+        case 16: return kptr<MAXD, 16>(mc, variant, sat);
         default: return nullptr;
     }
 }
 
-const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant) {
-    if (maxd <= 8) return kptr_l<8>(L, mc, variant);
+const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat) {
+    if (maxd <= 8) return kptr_l<8>(L, mc, variant, sat);
 #ifndef ACG_FAST_BUILD
-    if (maxd <= 16) return kptr_l<16>(L, mc, variant);
-    if (maxd <= 32) return kptr_l<32>(L, mc, variant);
+    if (maxd <= 16) return kptr_l<16>(L, mc, variant, sat);
+    if (maxd <= 32) return kptr_l<32>(L, mc, variant, sat);
 #endif
     return nullptr;
 }

@@ -33,7 +33,7 @@
 namespace acg {
 #include "bp_core.inc"
 
-const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant);
+const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat);
 const void *bp_kernel_ptr_spa_f64(int maxd, int L, bool mc, int variant);
 const void *bp_kernel_ptr_ms_f32(int maxd, int L, bool mc, int variant);
 const void *bp_kernel_ptr_ms_f64(int maxd, int L, bool mc, int variant);
@@ -48,13 +48,13 @@ const void *bp_kernel_ptr_dbg(int f64, int L) {
 #endif
 }
 
-// algo: 0 sum-product, 1 min-sum; f64: 0/1
-const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant) {
+// algo: 0 sum-product, 1 min-sum; f64: 0/1; sat: the phi fast path where an instance has it (fp32 sum-product)
+const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat) {
 #ifdef ACG_FAST_BUILD
     if (f64 || algo) return nullptr;
-    return bp_kernel_ptr_spa_f32(maxd, L, mc, variant);
+    return bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat);
 #else
-    if (algo == 0) return f64 ? bp_kernel_ptr_spa_f64(maxd, L, mc, variant) : bp_kernel_ptr_spa_f32(maxd, L, mc, variant);
+    if (algo == 0) return f64 ? bp_kernel_ptr_spa_f64(maxd, L, mc, variant) : bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat);
     return f64 ? bp_kernel_ptr_ms_f64(maxd, L, mc, variant) : bp_kernel_ptr_ms_f32(maxd, L, mc, variant);
 #endif
 }
@@ -77,6 +77,23 @@ __global__ void phi_debug_kernel(const float *x, float *out, int n) {
 __global__ void phi_debug_kernel_f64(const double *x, double *out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = phi_f(x[i]);
+}
+
+// the phi fast path of the fp32 sum-product sweeps against the full evaluation, raw bits in the scaled domain:
+// out[3i] = Dom<float>::phi(x), out[3i+1] = BpPass::phi_c(x) (check side), out[3i+2] = BpPass::phi_v(|x|) (variable side)
+__global__ void phi_sat_debug_kernel(const float *x, uint32_t *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    using P = BpPass<float, 1, 64, 0, true>;
+    if (i < n) {
+        out[3 * i] = __float_as_uint(Dom<float>::phi(x[i]));
+        out[3 * i + 1] = __float_as_uint(P::phi_c(x[i]));
+        out[3 * i + 2] = __float_as_uint(P::phi_v(__builtin_fabsf(x[i])));
+    }
+}
+
+hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s) {
+    hipLaunchKernelGGL(phi_sat_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, out, n);
+    return hipGetLastError();
 }
 
 hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s) {

@@ -230,6 +230,9 @@ int acg_ldpc_awgn_dev(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, float *
 /* diagnostics (used by tests/): evaluates the device phi(x) = -log(tanh(x/2)) (bp.h:34) of the BP kernels
  * on n host values; f64 selects the double variant. */
 int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f64);
+/* diagnostics: the phi fast path of the fp32 sum-product sweeps on n float inputs in the kernels' log2(e)-scaled domain;
+ * out: 3n uint32 = per input the bits of the full phi, of the check-side path and of the variable-side path (on |x|). */
+int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n);
 /* diagnostics: soft state of the device sum-product decoder after `iters` full iterations of bp.h:183-199 without
  * the exit test, for 1..64 frames (y: frames*n doubles).  Outputs are frames*E (edge order: check-major, variables
  * ascending) / frames*n doubles: c2v = messages check->variable, (v2c_mag, v2c_sgn) = the (phi(|x|), sign) pairs
