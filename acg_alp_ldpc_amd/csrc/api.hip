@@ -324,6 +324,7 @@ struct acg_ldpc_decoder {
     const void *kernel[2] = {nullptr, nullptr};
     size_t lds_block = 0;
     int variant = -1;       // wave-group kernels: 0 / 1 / 2 (see bp_inst_*.hip); -1 = workgroup-per-frame
+    bool phi_memo = false;  // DecodeArgs::phi_memo (the SAT instances read it)
     bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
     bool blk_idxlds = false, blk_idxreg = false;
     // layered min-sum (bp_layered.hip)
@@ -992,6 +993,8 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     // fixed-work decoders: the instances with the phi fast path (BpCore::SATSKIP; fp32 sum-product, degree <= 8, register
     // LLRs); ACG_BP_NO_SATSKIP=1 keeps the plain instances (A/B runs)
     const bool sat = !d->p.early_exit && getenv("ACG_BP_NO_SATSKIP") == nullptr;
+    // the phi memo of the absorbed check passes in those instances (BpPass::phi_c); ACG_BP_NO_PHIMEMO=1 turns it off (A/B runs)
+    d->phi_memo = sat && getenv("ACG_BP_NO_PHIMEMO") == nullptr;
     for (int mc = 0; mc < 2; mc++) {
         const int variant = idxlds ? ((llr_regs) ? 2 : 1) : 0;
         d->variant = variant;
@@ -1180,6 +1183,7 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
     a.max_iter = d->p.max_iter;
     a.early_exit = d->p.early_exit;
     a.ms_scale = (float) d->p.ms_scale;
+    a.phi_memo = d->phi_memo ? 1 : 0;
     if (a.frames <= 0) return 0;
     // this launch's own work counter (see acg_ldpc_decoder::work_ring)
     const int slot = (int) (d->launch_seq++ % acg_ldpc_decoder::WORK_RING);

@@ -158,11 +158,14 @@ struct BpPass {
     // EXEC = (store && not saturated): a 32-lane half of the wavefront with no such lane issues it in one pass, or none.
     //   check side: an exclude-self sum (>= 0) that is exactly +0 (integer test: NaN and denormals fail) -> +inf
     //   variable side: a magnitude ax >= 66 (the saturation point, +inf included; NaN fails) -> +0
-    static __device__ __forceinline__ T phi_c(T s) {
-        T o = (T) INFINITY;
-        if (B::to(s) != 0) o = Dom<T>::phi(s);
+    // The check side is a one-entry memo: an input whose bits are mb gives G = phi(mb), computed once per frame (mb = +0,
+    // G = +inf is the rule above).  Bit-identical by construction: phi would see the same bits.
+    static __device__ __forceinline__ T phi_c(T s, U mb, T G) {
+        T o = G;
+        if (B::to(s) != mb) o = Dom<T>::phi(s);
         return o;
     }
+    static __device__ __forceinline__ T phi_c(T s) { return phi_c(s, (U) 0, (T) INFINITY); }
     static __device__ __forceinline__ T phi_v(T ax) {
         T o = (T) 0;
         if (!(ax >= (T) 66)) o = Dom<T>::phi(ax);
@@ -304,7 +307,12 @@ struct BpPass {
     // frame.  The c->v word R of edge D - 1 is not stored; it gives the variable's posterior hard decision llr + R <= 0
     // (bp.h:85-90,193, NaN -> 0), which becomes the LSB of aw, exactly as the variable sweep would have set it.  Lanes
     // without a check (slot >= cnt[1]) keep aw = +0.  r_out: R (debug trace).
-    static __device__ __forceinline__ U check_abs(T *__restrict__ Ap, int slot, const int *cnt, bool write, U &aw, T allr, T &r_out) {
+    // SAT: the exclude-self sum of every edge but D - 1 contains aw's magnitude m, and once the check's other inputs have
+    // saturated to +0 (or fall below half an ulp of m) it IS m, in every sweep that follows: the memo of phi_c holds m's
+    // bits (aw & am; am = the magnitude mask, or 0 to turn the memo off) and ag = phi(m), built with aw (BpCore::abs_phi).
+    // Edge D - 1 keeps the +0 rule.
+    static __device__ __forceinline__ U check_abs(T *__restrict__ Ap, int slot, const int *cnt, bool write, U &aw, T allr, T &r_out,
+                                                  T ag = (T) INFINITY, U am = 0) {
         T x[D];
 #pragma unroll
         for (int j = 0; j < D - 1; ++j) x[j] = Ap[j * L];
@@ -328,10 +336,11 @@ struct BpPass {
                 out[j] = pre[j] + suf;
                 suf += mag[j];
             }
+            const U mb = aw & am;
 #pragma unroll
             for (int j = 0; j < D - 1; ++j) {
                 if (write && slot < cnt[j + 2]) {
-                    const T o = phi_c(out[j]);
+                    const T o = phi_c(out[j], mb, ag);
                     Ap[j * L] = B::from((B::to(o) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN));
                 }
             }
@@ -502,6 +511,10 @@ struct BpCore {
         const T mg = Dom<T>::phi(ax);
         return (B::to(mg) & ~SIGN & ~ONE) | ((llr <= (T) 0) ? (ONE | SIGN) : (U) 0);
     }
+    // the memo of the absorbed pass's phi_c (SATSKIP, BpPass::check_abs): phi of the word's magnitude, once per frame; memo
+    // mask am = 0 (off) -> +inf, the +0 rule
+    static __device__ __forceinline__ T abs_phi(U aw, U am) { return am != 0 ? Dom<T>::phi(B::from(aw & am)) : (T) INFINITY; }
+    static constexpr U MEMO_MASK = ~SIGN & ~ONE;
     // phi fast path (BpPass::phi_c / phi_v) of the fp32 sum-product wave-group sweeps.  Its own instances, which the host
     // takes for fixed-work decoders only: with early exit few frames stay long enough to saturate, and the test and its
     // EXEC-mask branch per edge (2 vector + 3 scalar instructions) would cost more than the skipped phi evaluations save
@@ -554,8 +567,9 @@ struct BpCore {
 
     // Returns the OR over this lane's checks of the XOR of the incoming words: bit 0 set <=> one of them fails the syndrome of
     // the hard decisions that ride in the v->c words (the estimate of the previous variable sweep).
-    // aw / al / ar: the absorbed variables' words, LLRs and (debug trace) c->v messages, see BpPass::check_abs
-    __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar) {
+    // aw / al / ar: the absorbed variables' words, LLRs and (debug trace) c->v messages, see BpPass::check_abs; ag / am: the
+    // phi memo of the SATSKIP sweeps (abs_phi, wave-uniform mask am)
+    __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar, const AbsLlr &ag, U am) {
         U acc = 0;
         const int nc = t.n_cpass - n_apass();
         for (int p = 0; p < nc; ++p) {
@@ -578,7 +592,7 @@ struct BpCore {
                 const int md = sload(t.c_pass, 2 * p);
                 T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
                 const int slot = p * L + l;
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q])
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am)
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             }
@@ -591,8 +605,10 @@ struct BpCore {
     }
     __device__ __forceinline__ U check_phase(bool write) {
         AbsWord aw = {};
-        AbsLlr al = {}, ar = {};
-        return check_phase(write, aw, al, ar);
+        AbsLlr al = {}, ar = {}, ag;
+#pragma unroll
+        for (int q = 0; q < (NAP > 0 ? NAP : 1); ++q) ag[q] = (T) INFINITY;
+        return check_phase(write, aw, al, ar, ag, 0);
     }
 
     __device__ __forceinline__ void var_phase(const LlrRegs &lr, bool write) {
@@ -953,12 +969,15 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
         vi[p] = (NVP > 0 && p < t.n_vpass) ? t.v_var[p * L + l] : -1;
     }
     // absorbed degree-1 variables (BpPass::check_abs): LLR, v->c word, c->v word (debug trace only) per absorbed pass
-    typename Core::AbsLlr al, ar;
+    // and, in the SATSKIP instances, the phi memo of its check's other edges (Core::abs_phi; memo off: am = 0, ag = +inf)
+    typename Core::AbsLlr al, ar, ag;
     typename Core::AbsWord aw;
+    const typename Core::U am = (Core::SATSKIP && a.phi_memo) ? Core::MEMO_MASK : 0;
 #pragma unroll
     for (int q = 0; q < (Core::NAP > 0 ? Core::NAP : 1); ++q) {
         al[q] = (T) 0;
         ar[q] = (T) 0;
+        ag[q] = (T) INFINITY;
         aw[q] = 0;
     }
 
@@ -1120,6 +1139,7 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                         const int v = core.abs_var(q);
                         al[q] = chan_llr(v);
                         aw[q] = v >= 0 ? Core::abs_word(al[q]) : 0;
+                        if constexpr (Core::SATSKIP) ag[q] = Core::abs_phi(aw[q], am);
                     }
                 }
             }
@@ -1197,7 +1217,7 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
         if (__ballot(active) == 0ull) break;
         init_frames();
         // ---- one flooding iteration (bp.h:186-188) -------------------------------------------
-        core.check_phase(active, aw, al, ar);
+        core.check_phase(active, aw, al, ar, ag, am);
         wave_sync();
         // debug dumps: per frame the message array, then the absorbed edges' words (absorbed pass q, lane l at a_words + q*L + l);
         // LLRs in slot order, then the absorbed variables' (n_vpass*L + q*L + l)

@@ -46,6 +46,7 @@ struct DecodeArgs {
     int32_t max_iter;
     int32_t early_exit;
     float ms_scale;
+    int32_t phi_memo;   // fused fixed-work sum-product sweeps: the phi memo of the absorbed check passes (BpPass::phi_c); 0 = off
     // Monte-Carlo mode
     int32_t mc;          // 0 = decode y; 1 = generate y on device + classify
     uint64_t seed;
