@@ -109,6 +109,12 @@ struct AdmmDevTables {
 
 struct AdmmDevice;
 void admm_device_destroy(AdmmDevice *d);
+// streamed engine (admm_streamed.hip)
+struct AdmmStream;
+AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
+void admm_stream_destroy(AdmmStream *s);
+void admm_stream_info(const AdmmStream *s, int *slabs, int64_t *slab_bytes, int *f32);
+hipError_t admm_stream_launch(AdmmStream *s, const DecodeArgs &a, hipStream_t st);
 
 struct AdmmDevice {
     AdmmDevTables t{};
@@ -122,6 +128,7 @@ struct AdmmDevice {
     bool guard = false;  // e_min*mu <= alpha  (qp_admm.h:108-114)
     bool budget0 = false;  // max_iter == 0: handled by admm_budget0_kernel
     double alpha = 0, mu = 0, eps = 0;
+    AdmmStream *st = nullptr;  // streamed engine (state in HBM); null = the LDS kernels above
 };
 
 // NGP = 0: row state w in LDS (any code size).  NGP > 0 (requires n_gpass <= NGP): every lane keeps the w of its own
@@ -961,7 +968,9 @@ static void *upload_vec(const std::vector<T> &h, std::vector<void *> &allocs, st
     return d;
 }
 
-AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
+static const char *const ADMM_NO_FIT = "QP-ADMM frame state does not fit in LDS (160 KiB per CU)";
+
+static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
     const AdmmLayout &A = c.admm;
     auto *d = new AdmmDevice();
     d->alpha = p.alpha;
@@ -1213,7 +1222,7 @@ AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_c
         d->frames_per_block = 1;
         d->lds_block = per_frame;
         if (per_frame > 160 * 1024) {
-            err = "QP-ADMM frame state does not fit in LDS (160 KiB per CU)";
+            err = ADMM_NO_FIT;
             admm_device_destroy(d);
             return nullptr;
         }
@@ -1249,7 +1258,7 @@ AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_c
         }
     }
     if (per_frame * fpw * waves > 160 * 1024) {
-        err = "QP-ADMM frame state does not fit in LDS (160 KiB per CU)";
+        err = ADMM_NO_FIT;
         admm_device_destroy(d);
         return nullptr;
     }
@@ -1276,8 +1285,67 @@ AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_c
     return d;
 }
 
+// streamed engine: the guard, budget-0 and classification paths need only the CSR and the shape; the sweeps are
+// admm_streamed.hip's
+static AdmmDevice *admm_device_create_streamed(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
+    auto *d = new AdmmDevice();
+    d->alpha = p.alpha;
+    d->mu = p.mu;
+    d->eps = p.eps_stop;
+    d->f32 = (p.precision == ACG_LDPC_PREC_F32) ? 1 : 0;
+    double e_min = 1e9;  // qp_admm.h:108-111
+    for (double e : c.admm.e) e_min = std::min(e_min, e);
+    d->guard = (e_min * p.mu <= p.alpha);
+    d->budget0 = (p.max_iter == 0);
+    d->L = 1;
+    d->block = 256;
+    d->frames_per_block = 64;
+    d->t.n = c.n;
+    d->t.m = c.m;
+    d->t.n_var = c.admm.n_var;
+    d->t.n_grp = c.admm.n_grp;
+    d->t.nwords = (c.n + 31) / 32;
+    d->t.lds_bytes_per_frame = 0;
+    d->t.row_ptr = (const int32_t *) upload_vec(c.row_ptr, d->allocs, err);
+    d->t.edge_var = (const int32_t *) upload_vec(c.edge_var, d->allocs, err);
+    if (!d->t.row_ptr || !d->t.edge_var) {
+        admm_device_destroy(d);
+        return nullptr;
+    }
+    d->st = admm_stream_create(c, p, cu_count, err);
+    if (!d->st) {
+        admm_device_destroy(d);
+        return nullptr;
+    }
+    int slabs = 0;
+    admm_stream_info(d->st, &slabs, nullptr, nullptr);
+    d->grid_cap = slabs;
+    return d;
+}
+
+// engine selection (acg_ldpc.h): AUTO keeps the LDS kernels wherever they accept the code and takes the streamed engine
+// only where they refuse it for want of LDS; STREAMED always takes it; FUSED or an explicit lanes_per_frame never does
+AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
+    if (p.precision == ACG_LDPC_PREC_F16) {
+        err = "ACG_LDPC_PREC_F16 exists for the fused min-sum decoder only";
+        return nullptr;
+    }
+    if (p.engine == ACG_LDPC_ENGINE_STREAMED) {
+        if (p.lanes_per_frame != 0) {
+            err = "the streamed QP-ADMM engine runs one lane per frame: lanes_per_frame must be 0 with ACG_LDPC_ENGINE_STREAMED";
+            return nullptr;
+        }
+        return admm_device_create_streamed(c, p, cu_count, err);
+    }
+    AdmmDevice *d = admm_device_create_lds(c, p, cu_count, err);
+    if (d || p.engine != ACG_LDPC_ENGINE_AUTO || p.lanes_per_frame != 0 || err != ADMM_NO_FIT) return d;
+    err.clear();
+    return admm_device_create_streamed(c, p, cu_count, err);
+}
+
 void admm_device_destroy(AdmmDevice *d) {
     if (!d) return;
+    admm_stream_destroy(d->st);
     for (void *p : d->allocs) (void) hipFree(p);
     delete d;
 }
@@ -1286,7 +1354,13 @@ void admm_device_destroy(AdmmDevice *d) {
 bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var) {
     if (row_ptr) *row_ptr = d->t.row_ptr;
     if (edge_var) *edge_var = d->t.edge_var;
-    return (d->blockmode || d->budget0) && !d->guard;
+    return d->st != nullptr || ((d->blockmode || d->budget0) && !d->guard);
+}
+
+bool admm_device_streamed(const AdmmDevice *d, int *slabs, int64_t *slab_bytes, int *f32) {
+    if (!d->st) return false;
+    admm_stream_info(d->st, slabs, slab_bytes, f32);
+    return true;
 }
 
 void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int *frames_per_block, int *grid) {
@@ -1326,6 +1400,15 @@ hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::s
         int grid = (int) std::min<int64_t>((total + 255) / 256, 8192);
         if (d->f32) hipLaunchKernelGGL(admm_budget0_kernel<float>, dim3(grid), dim3(256), 0, s, a, d->t.n, d->t.nwords);
         else hipLaunchKernelGGL(admm_budget0_kernel<double>, dim3(grid), dim3(256), 0, s, a, d->t.n, d->t.nwords);
+        return hipGetLastError();
+    }
+    if (d->st) {
+        if (a.mc) {
+            err = "internal: the streamed QP-ADMM engine has no fused Monte-Carlo mode (use AWGN kernel -> decode -> classify)";
+            return hipErrorInvalidValue;
+        }
+        const hipError_t e = admm_stream_launch(d->st, a, s);
+        if (e != hipSuccess) return e;
         return hipGetLastError();
     }
     if (d->blockmode && a.mc) {

@@ -58,6 +58,7 @@ void admm_device_destroy(AdmmDevice *d);
 hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::string &err);
 void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int *frames_per_block, int *grid);
 bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var);
+bool admm_device_streamed(const AdmmDevice *d, int *slabs, int64_t *slab_bytes, int *f32);
 
 #define HIP_OK(expr)                                                                            \
     do {                                                                                        \
@@ -1128,7 +1129,13 @@ void acg_ldpc_decoder_layout(const acg_ldpc_decoder *d, int32_t *lds_bytes_per_f
 static std::string describe(const acg_ldpc_decoder *d) {
     char b[512];
     const char *algo = d->p.algo == ACG_LDPC_QPADMM ? "qpadmm" : (d->p.algo == ACG_LDPC_BP_MINSUM ? "minsum" : "sum-product");
-    if (d->admm) {
+    int slabs = 0, f32 = 0;
+    int64_t slab = 0;
+    if (d->admm && admm_device_streamed(d->admm, &slabs, &slab, &f32)) {
+        snprintf(b, sizeof b, "%s engine=streamed kernel=admm_streamed_kernel<%s> f64=%d slab_bytes=%lld slabs=%d workspace_bytes=%lld "
+                               "workspace=hipMalloc",
+                 algo, f32 ? "float" : "double", f32 ? 0 : 1, (long long) slab, slabs, (long long) slab * slabs);
+    } else if (d->admm) {
         int lds = 0, L = 0, fpb = 0, grid = 0;
         admm_device_layout(d->admm, &lds, &L, &fpb, &grid);
         snprintf(b, sizeof b, "%s engine=lds lanes_per_frame=%d frames_per_block=%d lds_bytes_per_frame=%d grid_cap=%d", algo, L, fpb, lds, grid);
@@ -1188,7 +1195,9 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
     // this launch's own work counter (see acg_ldpc_decoder::work_ring)
     const int slot = (int) (d->launch_seq++ % acg_ldpc_decoder::WORK_RING);
     if (d->ring_used[slot]) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[slot], 0));
-    if (d->streamed && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
+    // engines whose HBM workspace belongs to the handle (streamed BP, streamed QP-ADMM): a launch on another stream waits
+    const bool owns_ws = d->streamed || (d->admm && admm_device_streamed(d->admm, nullptr, nullptr, nullptr));
+    if (owns_ws && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
     a.work_counter = d->work_ring + slot;
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
 #ifdef ACG_BLOCK_STAMPS

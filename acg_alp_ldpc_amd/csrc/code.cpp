@@ -394,6 +394,41 @@ void admm_layout_build(Code &c) {
     if (a.n_var == 0) a.e_min = a.e_max = 0;
 }
 
+bool admm_stream_tables_build(const Code &c, AdmmStreamTables &o) {
+    const AdmmLayout &A = c.admm;
+    o = AdmmStreamTables();
+    o.n = A.n;
+    o.n_var = A.n_var;
+    o.n_grp = A.n_grp;
+    std::vector<int64_t> first(A.n_grp);
+    int64_t rows = 0;
+    for (int g = 0; g < A.n_grp; g++) {
+        first[g] = rows;
+        rows += admm_group_rows(A.grp_type[g]);
+    }
+    if (rows >= (int64_t) 1 << 28 || A.n_var >= (1 << 30)) {
+        set_error("code too large for the streamed QP-ADMM engine (2^28 constraint rows, 2^30 variables)");
+        return false;
+    }
+    o.n_con = (int) rows;
+    o.var_ptr = A.var_ptr;
+    o.var_ent.resize(A.var_grp.size());
+    for (size_t k = 0; k < A.var_grp.size(); k++) {
+        const int g = A.var_grp[k] >> 2, wpos = A.var_grp[k] & 3;
+        o.var_ent[k] = (uint32_t) first[g] | ((uint32_t) wpos << 28) | ((uint32_t) A.grp_type[g] << 30);
+    }
+    o.grp.assign((size_t) A.n_grp * 4, 0xFFFFFFFFu);
+    for (int g = 0; g < A.n_grp; g++) {
+        const int ty = A.grp_type[g];
+        o.grp[(size_t) g * 4] = (uint32_t) first[g] | ((uint32_t) ty << 30);
+        int order[3] = {0, 1, 2};
+        std::sort(order, order + ty, [&](int x, int y) { return A.grp_var[(size_t) g * 3 + x] < A.grp_var[(size_t) g * 3 + y]; });
+        for (int k = 0; k < ty; k++)
+            o.grp[(size_t) g * 4 + 1 + k] = (uint32_t) A.grp_var[(size_t) g * 3 + order[k]] | ((uint32_t) order[k] << 30);
+    }
+    return true;
+}
+
 long placement_optimise(std::vector<int> &pos_of_item, const int n_pos, const std::vector<PlacementSet> &sets,
                                const int rounds, std::vector<long> *per_set_max) {
     const int n_items = (int) pos_of_item.size();

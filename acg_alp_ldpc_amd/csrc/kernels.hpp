@@ -63,6 +63,19 @@ struct DecodeArgs {
     void *dbg_post;
 };
 
+// ---- QP-ADMM constraint rows (qp_admm.h:34-83), shared by the streamed engine (admm_streamed.hip) and host checks ----
+// A constraint group of type 3 (three variables, qp_admm.h:34-57) owns 4 consecutive rows, type 2 (:75-83) 2 rows, type 1
+// (:70-74) 1 row.  Member `wpos` (its position in the group's construction, 0..2) has coefficient +1 in row `wpos` and in
+// row 3, -1 in the other rows; b is 2 in row 3 of a type-3 group, 0 everywhere else.
+#ifdef __HIP__
+#define ACG_HD __host__ __device__
+#else
+#define ACG_HD
+#endif
+ACG_HD inline int admm_group_rows(int type) { return type == 3 ? 4 : type; }
+ACG_HD inline bool admm_row_plus(int type, int row, int wpos) { return (type == 3 && row == 3) || row == wpos; }
+ACG_HD inline double admm_row_b(int type, int row) { return (type == 3 && row == 3) ? 2.0 : 0.0; }
+
 // Layered min-sum (bp_layered.hip; LayeredLayout in ldpc_internal.hpp)
 struct LayerTables {
     const int32_t *layer;    // [n_layers][4] = {degree, message offset (words), checks, first proto entry | first row << 16}

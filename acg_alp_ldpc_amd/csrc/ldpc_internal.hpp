@@ -61,6 +61,21 @@ struct AdmmLayout {
     std::vector<int32_t> var_grp;   // [sum] group*4 + position
 };
 
+// Tables of the streamed QP-ADMM engine (admm_streamed.hip), derived from AdmmLayout.  Constraint rows are numbered in
+// construction order (group g owns rows first(g) .. first(g) + admm_group_rows(type) - 1).  Row coefficients and b follow
+// from (type, row, wpos) (admm_row_plus / admm_row_b in kernels.hpp), so one entry per (variable, group) is enough:
+//   var_ent[var_ptr[i] .. var_ptr[i+1])  first row | wpos << 28 | type << 30, in AdmmLayout::var_grp order — expanded row
+//                                        by row this is A[i] of ConstructADMMProblem, in order (qp_admm.h:134-138)
+//   grp[4g]                              first row | type << 30
+//   grp[4g + 1 + k]                      k-th member in ASCENDING variable id: id | wpos << 30 (0xFFFFFFFF = none), the order
+//                                        in which qp_admm.h:147-151 subtracts the terms of a row
+struct AdmmStreamTables {
+    int n = 0, n_var = 0, n_con = 0, n_grp = 0;
+    std::vector<int32_t> var_ptr;   // [n_var+1]
+    std::vector<uint32_t> var_ent;  // [sum of list lengths]
+    std::vector<uint32_t> grp;      // [n_grp*4]
+};
+
 struct Code {
     int m = 0, n = 0, E = 0;
     std::vector<uint8_t> H;          // dense m*n
@@ -77,6 +92,8 @@ bool code_generator(const Code &c, uint8_t *G);
 bool code_is_codeword(const Code &c, const uint8_t *bits);
 bool bp_layout_build(const Code &c, int L, BpLayout &out, int max_apass = 0);
 void admm_layout_build(Code &c);
+// false (message via set_error) when the code exceeds the packing: >= 2^28 constraint rows or >= 2^30 variables
+bool admm_stream_tables_build(const Code &c, AdmmStreamTables &out);
 
 // Static placement against LDS bank conflicts.  A wave64 LDS access is served in fixed lane groups and takes as many
 // LDS cycles as the busiest bank has distinct addresses (MI355X_MICROARCH.md, LDS).  Which group slot / variable cell a

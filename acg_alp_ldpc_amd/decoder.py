@@ -221,7 +221,11 @@ class MinSumDecoder(Decoder):
 
 
 class QPADMMDecoder(Decoder):
-    """algo/qp_admm.h:180-194 (same defaults: max_iter=2000, eps_stop=1e-5)"""
+    """algo/qp_admm.h:180-194 (same defaults: max_iter=2000, eps_stop=1e-5).
+
+    engine=ENGINE_AUTO: the LDS kernels wherever they accept the code, the streamed engine (state in HBM, one lane per
+    frame, any code size) where a frame's state does not fit in LDS; ENGINE_STREAMED forces it (lanes_per_frame must be
+    0); ENGINE_FUSED never takes it.  See acg_ldpc.h for the streamed engine's workspace."""
     _algo = _lib.ALGO_QPADMM
 
     def __init__(self, alpha, mu, max_iter=2000, eps_stop=1e-5, **kw):

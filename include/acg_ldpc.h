@@ -19,7 +19,8 @@
  * DIFFERENT streams may overlap on the device: each launch owns its work counter (a ring of 32 per handle,
  * a slot is reused only behind the launch that held it).  The streamed BP engine keeps its message slabs
  * in the handle, so its launches are ordered on the device (a launch on another stream waits for the
- * previous one through an event) — correct, not concurrent; use one handle per stream to overlap those.
+ * previous one through an event) — correct, not concurrent; use one handle per stream to overlap those.  The same holds
+ * for the streamed QP-ADMM engine.
  */
 #ifndef ACG_LDPC_H
 #define ACG_LDPC_H
@@ -50,11 +51,21 @@ enum {
                                   the LDS of a CU (check degree <= 8, variable degree <= 4, n <= 12288) */
 };
 
-/* BP engine selector */
+/* engine selector (BP and QP-ADMM) */
 enum {
-    ACG_LDPC_ENGINE_AUTO = 0,     /* fused when a frame's messages fit in LDS, else streamed */
-    ACG_LDPC_ENGINE_FUSED = 1,    /* messages resident in LDS for the whole decode (HBM: symbols in, bits out) */
-    ACG_LDPC_ENGINE_STREAMED = 2  /* messages [edge][frame] in HBM, one lane per frame, coalesced sweeps (any code size) */
+    ACG_LDPC_ENGINE_AUTO = 0,     /* fused when a frame's state fits in LDS, else streamed.  QP-ADMM: the LDS kernels for every
+                                     code they accept (lanes_per_frame 0); the streamed engine only where they refuse the code
+                                     because its frame state does not fit in LDS */
+    ACG_LDPC_ENGINE_FUSED = 1,    /* state resident in LDS for the whole decode (HBM: symbols in, bits out); a code too
+                                     large for it is refused */
+    ACG_LDPC_ENGINE_STREAMED = 2  /* state [row][frame] in HBM, one lane per frame, coalesced sweeps (any code size).
+                                     BP: messages per edge.  QP-ADMM: w per constraint row, v, and the channel term; needs
+                                     lanes_per_frame = 0.  Workspace: one slab of (C + n_var + n) x 64 words (8 bytes fp64, 4
+                                     fp32; C constraint rows and n_var variables of acg_ldpc_code_admm_shape) per
+                                     workgroup, min(2 x CU count, slabs fitting in a quarter of the free device memory,
+                                     at least one) slabs, hipMalloc'ed when the decoder is created (configs[4], 5000 x 10000
+                                     (3,6)-regular, fp64: 58.9 MB per slab, 512 slabs = 30.1 GB on an MI355X).  Creation
+                                     fails when not even one slab fits. */
 };
 
 /* BP message schedule */
@@ -92,7 +103,7 @@ typedef struct acg_ldpc_params {
     int32_t device;     /* HIP device ordinal; -1 = current device */
     int32_t lanes_per_frame; /* 0 = auto; 16/32/64: that many lanes of a wavefront cooperate on one frame; 256 (BP also
                                 1024): one workgroup per frame (QP-ADMM then picks 128, 192 or 256 threads itself) */
-    int32_t engine;     /* ACG_LDPC_ENGINE_* (BP only) */
+    int32_t engine;     /* ACG_LDPC_ENGINE_* (BP and QP-ADMM) */
     int32_t fast_setup; /* 0 = default: spend up to ~1 s per decoder on the static LDS placement of the QP-ADMM kernel
                            (bank-conflict search; cached per parity-check matrix inside the process);
                            1 = skip that search (throw-away decoders, e.g. one per proposal of the check-matrix local
@@ -174,7 +185,8 @@ int acg_ldpc_decoder_sync(acg_ldpc_decoder *dec);
  * launch recorded on its own stream (every launch owns a pair: launches of one handle overlapping on two streams never
  * pair each other's events); synchronises on the stop event */
 float acg_ldpc_decoder_last_kernel_ms(acg_ldpc_decoder *dec);
-/* bytes of LDS per frame, frames resident per CU, lanes per frame chosen for this code (diagnostics) */
+/* bytes of LDS per frame, frames resident per CU, lanes per frame chosen for this code (diagnostics).  Streamed engines:
+ * 0 bytes of LDS per frame, 1 lane per frame, 64 frames per block; QP-ADMM's grid_blocks = the number of slabs */
 void acg_ldpc_decoder_layout(const acg_ldpc_decoder *dec, int32_t *lds_bytes_per_frame, int32_t *lanes_per_frame,
                              int32_t *frames_per_block, int32_t *grid_blocks);
 
