@@ -346,8 +346,9 @@ def test_mc_host_noise_known_answers(A, matrices, pcm, idx):
 
 
 def test_mc_device_noise_statistics(A, matrices, pcm):
-    """Philox AWGN is validated statistically only: raw BER = Q(1/sigma), FER inside the
-    99% binomial interval around the reference's 1000-frame estimate, shard-count invariance."""
+    """Philox AWGN through the Monte-Carlo loop (the generator itself is pinned sample for sample in test_awgn_exact_gpu.py):
+    raw BER = Q(1/sigma), FER inside the 99% binomial interval around the reference's 1000-frame estimate, shard-count
+    invariance."""
     from math import erfc, sqrt
     H = pcm["H05"]
     G, _ = H.get_orthogonal()

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+from awgn_ref import classify, sent_words
 from minsum_ref import Graph, flooding_minsum
 
 pytestmark = pytest.mark.gpu
@@ -320,11 +321,7 @@ def _mc_exact(A, dec, H, Hm, cws, F, snr, dt):
     y = yd.cpu().numpy()
     r = A.run_experiment(dec, cws, H, snr, frames=F, first_frame=first, noise="device", seed=seed)
     rb, rok, rit = flooding_minsum(Hm, y, snr, dec.max_iter, dec.scale, dt)
-    sent = cws[(first + np.arange(F)) % cws.shape[0]]
-    correct = (rok == 1) & (rb == sent).all(axis=1)
-    ham = np.where(sent == 1, y > 0, y <= 0).sum(axis=1)
-    want = dict(correct=int(correct.sum()), pseudo=int(((rok == 1) & ~correct).sum()), total=F, sum_iters=int(rit.sum()),
-                sum_hamming=int(ham.sum()), sum_hamming_ok=int(ham[correct].sum()), sum_hamming_wrong=int(ham[~correct].sum()))
+    want = classify(y, rb, rok, rit, sent_words(first, F, H.n, cws))
     got = {k: getattr(r, k) for k in want}
     assert got == want, (got, want)
     return want
