@@ -114,6 +114,7 @@ struct AdmmStream;
 AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
 void admm_stream_destroy(AdmmStream *s);
 void admm_stream_info(const AdmmStream *s, int *slabs, int64_t *slab_bytes, int *f32);
+bool admm_stream_set_point(AdmmStream *s, double alpha, double mu);
 hipError_t admm_stream_launch(AdmmStream *s, const DecodeArgs &a, hipStream_t st);
 
 struct AdmmDevice {
@@ -129,6 +130,12 @@ struct AdmmDevice {
     bool budget0 = false;  // max_iter == 0: handled by admm_budget0_kernel
     double alpha = 0, mu = 0, eps = 0;
     AdmmStream *st = nullptr;  // streamed engine (state in HBM); null = the LDS kernels above
+    // parameter grid (acg_ldpc_mc_run_grid)
+    double e_min = 1e9;              // min over e (qp_admm.h:108-111)
+    std::vector<double> e_of_slot;   // [n_vpass*L] e of the variable in that thread slot (LDS kernels); < 0 = no variable
+    const void *kernel_grid[2] = {nullptr, nullptr};  // grid instances of admm_block_kernel; null = points run one after another
+    const void *grid_pt = nullptr, *grid_inv = nullptr;  // bound tables: the next admm_launch is a grid launch
+    uint32_t grid_fpp = 0;
 };
 
 // NGP = 0: row state w in LDS (any code size).  NGP > 0 (requires n_gpass <= NGP): every lane keeps the w of its own
@@ -681,16 +688,33 @@ __device__ __forceinline__ void admm_group_update(unsigned char *smem, const uin
     *reinterpret_cast<T *>(smem + (u3_addr + lds0)) = u[3];
 }
 
+// Parameter grid (acg_ldpc_mc_run_grid): one launch decodes the same `frames_per_point` frames once per (alpha, mu) point.
+// Virtual frame g of the launch belongs to point g / frames_per_point, reads the channel symbols of frame
+// g % frames_per_point and writes its outputs at index g.  Everything structural is the same for every point; what
+// differs is alpha, mu and the table inv_coef, which the host builds per point exactly as admm_device_create_lds does.
+struct AdmmGridArgs {
+    const void *pt;        // [points][2] T = {alpha, mu}
+    const void *inv_coef;  // [points][n_vpass*L] T
+    uint32_t frames_per_point;
+};
+__device__ __forceinline__ const AdmmGridArgs &admm_grid_args(const AdmmGridArgs &g) { return g; }
+
 // BP = passes (of blockDim.x constraint groups / variables) the register-resident structure is sized for; fewer passes
 // = fewer registers = more wavefronts per SIMD (launch bound: 4, 5, 6 workgroups of 4 wavefronts per CU for BP = 4, 3, 2).
 // LEAN: the instance for problems that need none of the general paths inside the sweep — no one-/two-variable checks, every
 // list within the register-resident entries of its pass, V cell = thread slot (all true for the quasi-cyclic tuple placement
 // of H05 / optimalH).  The wavefronts of this kernel are bound by how many instructions they have to get through per sweep,
 // scalar tests and branches included, so the paths are compiled out, not branched around.
-template <typename T, bool EE, int BP, bool LEAN>
-__global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? ADMM_OCC_F32 : 0)) admm_block_kernel(const AdmmDevTables t, const DecodeArgs a, const T alpha,
-                                                              const T mu, const T eps_stop) {
+// GRID: empty (the decode kernel: its parameter list and code are exactly those of the kernel without this pack) or one
+// AdmmGridArgs (the parameter-grid instance: alpha_in / mu_in are ignored, every point brings its own).
+template <typename T, bool EE, int BP, bool LEAN, typename... GRID>
+__global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? ADMM_OCC_F32 : 0)) admm_block_kernel(const AdmmDevTables t, const DecodeArgs a, const T alpha_in,
+                                                              const T mu_in, const T eps_stop, const GRID... grid) {
     using X = AdmmVec<T>;
+    constexpr bool IS_GRID = sizeof...(GRID) != 0;
+    static_assert(sizeof...(GRID) <= 1, "GRID is empty or one AdmmGridArgs");
+    T alpha = alpha_in, mu = mu_in;
+    uint32_t cur_point = 0xFFFFFFFFu;  // (grid) point whose alpha, mu, inv[] are loaded
     extern __shared__ __attribute__((aligned(32))) unsigned char smem[];
     const int L = blockDim.x;  // 128, 192 or 256 threads = one frame
     __builtin_amdgcn_s_setreg((0 << 11) | (8 << 6) | 1, 0);  // hwreg(HW_REG_MODE, offset 8, width 1) = DX10_CLAMP := 0: the clamp modifier passes NaN (see the v-update)
@@ -753,8 +777,25 @@ __global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? AD
         __syncthreads();
         if (l == 0) fr_lds = atomicAdd(a.work_counter, 1ull);  // dynamic frame hand-out
         __syncthreads();
-        const int64_t frame = (int64_t) fr_lds;
+        const int64_t frame = (int64_t) fr_lds;  // index of the outputs
         if (frame >= a.frames) break;
+        int64_t yframe = frame;                   // index of the channel symbols
+        if constexpr (IS_GRID) {
+            // (the host keeps a grid launch below 2^31 virtual frames; hand-outs are consecutive, so a workgroup changes
+            // point about once per frames_per_point / workgroups frames and the reload below is rare)
+            const AdmmGridArgs &gr = admm_grid_args(grid...);
+            const uint32_t point = (uint32_t) __builtin_amdgcn_readfirstlane((int) ((uint32_t) frame / gr.frames_per_point));
+            yframe = (int64_t) ((uint32_t) frame - point * gr.frames_per_point);
+            if (point != cur_point) {
+                cur_point = point;
+                alpha = reinterpret_cast<const T *>(gr.pt)[2 * point];
+                mu = reinterpret_cast<const T *>(gr.pt)[2 * point + 1];
+                const T *gi = reinterpret_cast<const T *>(gr.inv_coef) + (size_t) point * (size_t) (t.n_vpass * L);
+#pragma unroll
+                for (int p = 0; p < BP; ++p)
+                    if (p < t.n_vpass) inv[p] = gi[p * L + l];
+            }
+        }
         // ---- start of a frame --------------------------------------------------------------------------------
 #pragma unroll
         for (int p = 0; p < BP; ++p) {
@@ -762,8 +803,8 @@ __global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? AD
             if (p < t.n_vpass) {
                 const int i = t.var_of_slot[p * L + l];
                 if (i >= 0 && i < t.n) {
-                    if (a.y_is_f64) q = (T) (2 * reinterpret_cast<const double *>(a.y)[(size_t) frame * t.n + i] / a.var);
-                    else q = (T) (2 * (double) reinterpret_cast<const float *>(a.y)[(size_t) frame * t.n + i] / a.var);
+                    if (a.y_is_f64) q = (T) (2 * reinterpret_cast<const double *>(a.y)[(size_t) yframe * t.n + i] / a.var);
+                    else q = (T) (2 * (double) reinterpret_cast<const float *>(a.y)[(size_t) yframe * t.n + i] / a.var);
                 }
             }
             qreg[p] = q + (alpha / 2);  // CalculateCoef, algo/algo.h:13-20; the v-update starts from q_i + alpha/2 (qp_admm.h:133)
@@ -936,20 +977,21 @@ static const void *admm_kernel_ptr(int f32, int L, bool mc, bool reg) {
     return admm_ptr<double, 16, 0>(mc);
 }
 
-template <typename T, bool EE, bool LEAN>
+template <typename T, bool EE, bool LEAN, typename... GRID>
 static const void *admm_block_ptr_t(int passes) {
-    if (passes <= 2) return (const void *) admm_block_kernel<T, EE, 2, LEAN>;
-    if (passes == 3) return (const void *) admm_block_kernel<T, EE, 3, LEAN>;
-    return (const void *) admm_block_kernel<T, EE, 4, LEAN>;
+    if (passes <= 2) return (const void *) admm_block_kernel<T, EE, 2, LEAN, GRID...>;
+    if (passes == 3) return (const void *) admm_block_kernel<T, EE, 3, LEAN, GRID...>;
+    return (const void *) admm_block_kernel<T, EE, 4, LEAN, GRID...>;
 }
 
+template <typename... GRID>
 static const void *admm_block_ptr(int f32, bool ee, int passes, bool lean) {
     if (lean) {
-        if (f32) return ee ? admm_block_ptr_t<float, true, true>(passes) : admm_block_ptr_t<float, false, true>(passes);
-        return ee ? admm_block_ptr_t<double, true, true>(passes) : admm_block_ptr_t<double, false, true>(passes);
+        if (f32) return ee ? admm_block_ptr_t<float, true, true, GRID...>(passes) : admm_block_ptr_t<float, false, true, GRID...>(passes);
+        return ee ? admm_block_ptr_t<double, true, true, GRID...>(passes) : admm_block_ptr_t<double, false, true, GRID...>(passes);
     }
-    if (f32) return ee ? admm_block_ptr_t<float, true, false>(passes) : admm_block_ptr_t<float, false, false>(passes);
-    return ee ? admm_block_ptr_t<double, true, false>(passes) : admm_block_ptr_t<double, false, false>(passes);
+    if (f32) return ee ? admm_block_ptr_t<float, true, false, GRID...>(passes) : admm_block_ptr_t<float, false, false, GRID...>(passes);
+    return ee ? admm_block_ptr_t<double, true, false, GRID...>(passes) : admm_block_ptr_t<double, false, false, GRID...>(passes);
 }
 
 template <typename T>
@@ -1022,6 +1064,7 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
     // guard: double e_min = 1e9; min over e (qp_admm.h:108-111)
     double e_min = 1e9;
     for (double e : A.e) e_min = std::min(e_min, e);
+    d->e_min = e_min;
     d->guard = (e_min * p.mu <= p.alpha);
     d->budget0 = (p.max_iter == 0);
 
@@ -1092,9 +1135,11 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
     }
     std::vector<uint32_t> v_list((size_t) std::max(off, 1), (uint32_t) A.n_grp);  // padding: slot n_grp of the wavefront kernels, type 0, wpos 0 -> adds 0
     std::vector<double> inv64((size_t) t.n_vpass * L, 0.0);
+    d->e_of_slot.assign((size_t) t.n_vpass * L, -1.0);
     for (int sidx = 0; sidx < t.n_vpass * L; sidx++) {
         const int i = var_of_slot[sidx];
         if (i < 0) continue;
+        d->e_of_slot[sidx] = A.e[i];
         const int p_ = sidx / L, l = sidx % L;
         for (int k = 0; k < llen(i); k++) {
             const int ent = A.var_grp[A.var_ptr[i] + k];
@@ -1230,10 +1275,13 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         for (int ee = 0; ee < 2; ee++) {  // kernel[0]: fixed sweep count, kernel[1]: with the residual stopping rule
             const int mc = ee;
             const int passes = std::max(std::max(t.n_gpass, t.n_vpass), 2);
-            const void *kp = admm_block_ptr(d->f32, ee != 0, passes, d->blk_lean);
+            const void *kp = admm_block_ptr<>(d->f32, ee != 0, passes, d->blk_lean);
+            const void *kg = admm_block_ptr<AdmmGridArgs>(d->f32, ee != 0, passes, d->blk_lean);
             d->kernel[mc] = kp;
+            d->kernel_grid[mc] = kg;
             if (d->lds_block > 64 * 1024 &&
-                hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block) != hipSuccess) {
+                (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block) != hipSuccess ||
+                 hipFuncSetAttribute(kg, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block) != hipSuccess)) {
                 err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
                 admm_device_destroy(d);
                 return nullptr;
@@ -1295,6 +1343,7 @@ static AdmmDevice *admm_device_create_streamed(const Code &c, const acg_ldpc_par
     d->f32 = (p.precision == ACG_LDPC_PREC_F32) ? 1 : 0;
     double e_min = 1e9;  // qp_admm.h:108-111
     for (double e : c.admm.e) e_min = std::min(e_min, e);
+    d->e_min = e_min;
     d->guard = (e_min * p.mu <= p.alpha);
     d->budget0 = (p.max_iter == 0);
     d->L = 1;
@@ -1370,6 +1419,85 @@ void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int
     if (grid) *grid = d->grid_cap;
 }
 
+// ---- parameter grid (acg_ldpc_mc_run_grid) ----------------------------------------------------------------------------
+double admm_device_e_min(const AdmmDevice *d) { return d->e_min; }
+
+// true: this handle has grid instances of admm_block_kernel (the workgroup-per-frame kernel with a sweep budget > 0);
+// every other QP-ADMM decoder runs the points of a grid one after another through admm_device_set_point
+bool admm_device_has_grid_kernel(const AdmmDevice *d) { return d->blockmode && !d->budget0 && !d->st && d->kernel_grid[0] && d->kernel_grid[1]; }
+
+template <typename T>
+static void admm_inv_table(const AdmmDevice *d, double alpha, double mu, T *out) {
+    for (size_t sidx = 0; sidx < d->e_of_slot.size(); sidx++) {
+        double inv = 0.0;
+        if (d->e_of_slot[sidx] >= 0) {
+            const double Acoef = (mu * d->e_of_slot[sidx] - alpha) / 2;  // qp_admm.h:125, as in admm_device_create_lds
+            inv = -1.0 / (2 * Acoef);                                    // qp_admm.h:126
+        }
+        out[sidx] = (T) inv;
+    }
+}
+
+// host images of AdmmGridArgs::pt and ::inv_coef for `np` points, in the kernel's precision
+void admm_grid_tables(const AdmmDevice *d, const double *alpha, const double *mu, int np, std::vector<unsigned char> &pt,
+                      std::vector<unsigned char> &inv) {
+    const size_t ts = d->f32 ? 4 : 8, slots = d->e_of_slot.size();
+    pt.resize((size_t) np * 2 * ts);
+    inv.resize((size_t) np * slots * ts);
+    for (int k = 0; k < np; k++) {
+        if (d->f32) {
+            reinterpret_cast<float *>(pt.data())[2 * k] = (float) alpha[k];
+            reinterpret_cast<float *>(pt.data())[2 * k + 1] = (float) mu[k];
+            admm_inv_table(d, alpha[k], mu[k], reinterpret_cast<float *>(inv.data()) + (size_t) k * slots);
+        } else {
+            reinterpret_cast<double *>(pt.data())[2 * k] = alpha[k];
+            reinterpret_cast<double *>(pt.data())[2 * k + 1] = mu[k];
+            admm_inv_table(d, alpha[k], mu[k], reinterpret_cast<double *>(inv.data()) + (size_t) k * slots);
+        }
+    }
+}
+
+// device tables for the NEXT admm_launch, which then covers a.frames = points * frames_per_point virtual frames with the grid
+// instance; (null, null, 0) unbinds
+void admm_grid_bind(AdmmDevice *d, const void *pt_dev, const void *inv_dev, uint32_t frames_per_point) {
+    d->grid_pt = pt_dev;
+    d->grid_inv = inv_dev;
+    d->grid_fpp = frames_per_point;
+}
+
+// Re-parameterise the handle in place (no launch of this handle may be in flight): alpha, mu, the guard flag and the
+// inv_coef table — everything admm_device_create derives from (alpha, mu).
+bool admm_device_set_point(AdmmDevice *d, double alpha, double mu, std::string &err) {
+    d->alpha = alpha;
+    d->mu = mu;
+    d->guard = (d->e_min * mu <= alpha);
+    if (d->st) {
+        if (!admm_stream_set_point(d->st, alpha, mu)) {
+            err = "hipMemcpy of the streamed QP-ADMM inv_coef table failed";
+            return false;
+        }
+        return true;
+    }
+    std::vector<unsigned char> pt, inv;
+    admm_grid_tables(d, &alpha, &mu, 1, pt, inv);
+    if (!inv.empty() && hipMemcpy(const_cast<void *>(d->t.inv_coef), inv.data(), inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        err = "hipMemcpy of the QP-ADMM inv_coef table failed";
+        return false;
+    }
+    return true;
+}
+
+template <typename T>
+static hipError_t admm_launch_grid_t(AdmmDevice *d, const DecodeArgs &a, int grid, hipStream_t s) {
+    AdmmDevTables tt = d->t;
+    DecodeArgs aa = a;
+    T alpha = (T) 0, mu = (T) 0, eps = (T) d->eps;  // (alpha, mu: every point brings its own)
+    AdmmGridArgs g{d->grid_pt, d->grid_inv, d->grid_fpp};
+    void *args[6] = {&tt, &aa, &alpha, &mu, &eps, &g};
+    const int which = (a.early_exit && d->eps > 0) ? 1 : 0;  // as admm_launch_t
+    return hipLaunchKernel(d->kernel_grid[which], dim3(grid), dim3(d->block), args, d->lds_block, s);
+}
+
 template <typename T>
 static hipError_t admm_launch_t(AdmmDevice *d, const DecodeArgs &a, int grid, hipStream_t s) {
     AdmmDevTables tt = d->t;
@@ -1382,6 +1510,16 @@ static hipError_t admm_launch_t(AdmmDevice *d, const DecodeArgs &a, int grid, hi
 }
 
 hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::string &err) {
+    if (d->grid_pt) {  // parameter grid: the handle's own alpha, mu and guard flag do not apply
+        if (!admm_device_has_grid_kernel(d) || a.mc || a.max_iter == 0 || d->grid_fpp == 0 || a.frames >= ((int64_t) 1 << 31)) {
+            err = "internal: bad QP-ADMM grid launch";
+            return hipErrorInvalidValue;
+        }
+        const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap);
+        const hipError_t e = d->f32 ? admm_launch_grid_t<float>(d, a, grid, s) : admm_launch_grid_t<double>(d, a, grid, s);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
     if (d->guard) {
         if (a.mc) {
             err = "QP-ADMM guard e_min*mu <= alpha fires: every frame fails (qp_admm.h:112-114); Monte-Carlo run refused";

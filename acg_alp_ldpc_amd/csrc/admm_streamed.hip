@@ -192,6 +192,7 @@ struct AdmmStream {
     unsigned char *ws = nullptr;
     int slabs = 0, f32 = 0;
     double alpha = 0, mu = 0, eps = 0;
+    std::vector<double> e;  // [n_var] (admm_stream_set_point)
 };
 
 void admm_stream_destroy(AdmmStream *s) {
@@ -225,6 +226,7 @@ AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_c
     s->alpha = p.alpha;
     s->mu = p.mu;
     s->eps = p.eps_stop;
+    s->e = c.admm.e;
     AdmmStreamDev &t = s->t;
     t.n = h.n;
     t.n_var = h.n_var;
@@ -274,6 +276,25 @@ AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_c
         return nullptr;
     }
     return s;
+}
+
+// Re-parameterise in place (parameter grids, acg_ldpc_mc_run_grid): alpha, mu and the inv_coef table, built as in
+// admm_stream_create.  No launch of this engine may be in flight.
+bool admm_stream_set_point(AdmmStream *s, double alpha, double mu) {
+    s->alpha = alpha;
+    s->mu = mu;
+    std::vector<double> inv64(s->e.size());
+    for (size_t i = 0; i < s->e.size(); i++) {
+        const double Acoef = (mu * s->e[i] - alpha) / 2;  // qp_admm.h:125
+        inv64[i] = -1.0 / (2 * Acoef);                    // qp_admm.h:126
+    }
+    if (inv64.empty()) return true;
+    void *dst = const_cast<void *>(s->t.inv_coef);
+    if (s->f32) {
+        const std::vector<float> inv32(inv64.begin(), inv64.end());
+        return hipMemcpy(dst, inv32.data(), inv32.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    return hipMemcpy(dst, inv64.data(), inv64.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
 }
 
 void admm_stream_info(const AdmmStream *s, int *slabs, int64_t *slab_bytes, int *f32) {

@@ -59,6 +59,17 @@ hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::s
 void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int *frames_per_block, int *grid);
 bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var);
 bool admm_device_streamed(const AdmmDevice *d, int *slabs, int64_t *slab_bytes, int *f32);
+// parameter grid (acg_ldpc_mc_run_grid)
+double admm_device_e_min(const AdmmDevice *d);
+bool admm_device_has_grid_kernel(const AdmmDevice *d);
+void admm_grid_tables(const AdmmDevice *d, const double *alpha, const double *mu, int np, std::vector<unsigned char> &pt,
+                      std::vector<unsigned char> &inv);
+void admm_grid_bind(AdmmDevice *d, const void *pt_dev, const void *inv_dev, uint32_t frames_per_point);
+bool admm_device_set_point(AdmmDevice *d, double alpha, double mu, std::string &err);
+hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                int64_t frames, int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
+                                int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                hipStream_t s);
 
 #define HIP_OK(expr)                                                                            \
     do {                                                                                        \
@@ -313,7 +324,7 @@ struct acg_ldpc_decoder {
     int cu_count = 256;
     hipStream_t stream = nullptr;
     bool ev_valid = false;
-    std::mutex mu;
+    std::recursive_mutex mu;  // (recursive: acg_ldpc_mc_run_grid holds it across the per-point runs of its sequential path)
     std::string name;
     // BP
     BpLayout lay;
@@ -361,6 +372,11 @@ struct acg_ldpc_decoder {
     int64_t cw_count = 0;
     uint64_t cw_hash = 0;
     unsigned long long *counters = nullptr;
+    // parameter grid (acg_ldpc_mc_run_grid): counters[point][MC_NCOUNTERS] and the per-point tables of the chunk in flight
+    unsigned long long *grid_counters = nullptr;
+    int64_t grid_counters_rows = 0;
+    unsigned char *grid_tab = nullptr;
+    size_t grid_tab_bytes = 0;
     // Per-launch work counters: every launch takes the next slot of a small ring of device words (the dynamic frame /
     // tile hand-out of the kernels), so launches of one handle that overlap on different streams never share one.
     // ring_ev[k] is recorded behind the launch that used slot k; the next user of the slot — and, for the streamed
@@ -1101,6 +1117,8 @@ void acg_ldpc_decoder_destroy(acg_ldpc_decoder *d) {
     if (d->st_iters) (void) hipFree(d->st_iters);
     delete d->pipe;
     if (d->cw_dev) (void) hipFree(d->cw_dev);
+    if (d->grid_counters) (void) hipFree(d->grid_counters);
+    if (d->grid_tab) (void) hipFree(d->grid_tab);
     if (d->counters) (void) hipFree(d->counters);
     if (d->work_ring) (void) hipFree(d->work_ring);
     for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++) {
@@ -1133,12 +1151,13 @@ static std::string describe(const acg_ldpc_decoder *d) {
     int64_t slab = 0;
     if (d->admm && admm_device_streamed(d->admm, &slabs, &slab, &f32)) {
         snprintf(b, sizeof b, "%s engine=streamed kernel=admm_streamed_kernel<%s> f64=%d slab_bytes=%lld slabs=%d workspace_bytes=%lld "
-                               "workspace=hipMalloc",
+                               "workspace=hipMalloc mc_grid=per-point",
                  algo, f32 ? "float" : "double", f32 ? 0 : 1, (long long) slab, slabs, (long long) slab * slabs);
     } else if (d->admm) {
         int lds = 0, L = 0, fpb = 0, grid = 0;
         admm_device_layout(d->admm, &lds, &L, &fpb, &grid);
-        snprintf(b, sizeof b, "%s engine=lds lanes_per_frame=%d frames_per_block=%d lds_bytes_per_frame=%d grid_cap=%d", algo, L, fpb, lds, grid);
+        snprintf(b, sizeof b, "%s engine=lds lanes_per_frame=%d frames_per_block=%d lds_bytes_per_frame=%d grid_cap=%d mc_grid=%s", algo, L, fpb, lds, grid,
+                 admm_device_has_grid_kernel(d->admm) ? "single-launch" : "per-point");
     } else if (d->streamed) {
         const size_t slab = (size_t) d->stab.ws_words_per_wave * 4;
         snprintf(b, sizeof b, "%s engine=streamed kernel=%s%s f64=%d slab_bytes=%zu slabs=%d workspace_bytes=%zu workspace_base=%p "
@@ -1278,7 +1297,7 @@ static int acg_ldpc_decode_batch_dev_impl(acg_ldpc_decoder *d, const void *y_dev
         set_error("bad frames / y");
         return 1;
     }
-    std::lock_guard<std::mutex> lk(d->mu);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     DecodeArgs a{};
     a.y = y_dev;
@@ -1465,7 +1484,7 @@ static int acg_ldpc_decode_batch_impl(acg_ldpc_decoder *d, const double *y, int6
         return 1;
     }
     if (frames == 0) return 0;
-    std::lock_guard<std::mutex> lk(d->mu);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     return decode_batch_host(d, y, 8, frames, snr, bits, ok, iters);
 }
@@ -1486,7 +1505,7 @@ static int acg_ldpc_decode_batch_f32_impl(acg_ldpc_decoder *d, const float *y, i
         return 1;
     }
     if (frames == 0) return 0;
-    std::lock_guard<std::mutex> lk(d->mu);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     return decode_batch_host(d, y, 4, frames, snr, bits, ok, iters);
 }
@@ -1507,7 +1526,7 @@ float acg_ldpc_decoder_last_kernel_ms(acg_ldpc_decoder *d) {
     if (!d) return -1.0f;
     int slot;
     {
-        std::lock_guard<std::mutex> lk(d->mu);
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
         if (!d->ev_valid || d->last_slot < 0) return -1.0f;
         slot = d->last_slot;
     }
@@ -1649,7 +1668,7 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
         // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
         if (d->admm) (void) admm_device_unfused_mc(d->admm, &csr_row, &csr_col);
-        std::lock_guard<std::mutex> lk(d->mu);
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
         HIP_OK(hipSetDevice(d->device));
         if ((rc = ensure_codewords(d, cfg))) return rc;
         const int n = d->c.n, nwords = (n + 31) / 32;
@@ -1696,7 +1715,7 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
         res->sum_iters = (int64_t) h[MC_ITERS];
         res->kernel_ms = kms;
     } else {
-        std::lock_guard<std::mutex> lk(d->mu);
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
         HIP_OK(hipSetDevice(d->device));
         if ((rc = ensure_codewords(d, cfg))) return rc;
         HIP_OK(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
@@ -1732,12 +1751,202 @@ int acg_ldpc_mc_run(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc
     return guarded([&] { return acg_ldpc_mc_run_impl(d, cfg, res); });
 }
 
+// ---------------------------------------------------------------- Monte-Carlo over a QP-ADMM parameter grid
+// virtual frames (points x frames) one launch of the grid path covers, and so the size of its per-frame outputs: the
+// staging of a 65536-frame decode.  ACG_MC_GRID_BUDGET: developer / test override (README, developer variables).
+static int64_t mc_grid_budget() {
+    const char *e = getenv("ACG_MC_GRID_BUDGET");
+    const int64_t v = e ? atoll(e) : 0;
+    return v > 0 ? std::min<int64_t>(v, (int64_t) 1 << 30) : 65536;
+}
+
+// channel symbols of global frames [first, first + fc) into d->st_y: doubles from mt19937 (experiment.h:90-99, as
+// mc_run_host_noise) or floats from the device generator (as the unfused path of acg_ldpc_mc_run).  Caller holds d->mu.
+static int mc_grid_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, std::vector<double> &yh) {
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    const double var = std::pow(10, -(cfg->snr / 10)) / 2;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
+        const double sigma = std::sqrt(var);
+        yh.resize((size_t) fc * n);
+        for (int64_t f = 0; f < fc; f++) {
+            const int64_t gidx = first + f;
+            const uint8_t *cw = cfg->codewords ? cfg->codewords + (size_t) (gidx % cfg->n_codewords) * n : nullptr;
+            std::mt19937 rnd((uint32_t) (gidx + 1));
+            std::normal_distribution<double> dst(0, sigma);
+            for (int i = 0; i < n; i++) yh[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + dst(rnd);
+        }
+        HIP_OK(hipMemcpyAsync(d->st_y, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    } else {
+        HIP_OK(awgn_launch((float *) d->st_y, fc, n, nwords, first, cfg->seed, cfg->codewords ? d->cw_dev : nullptr,
+                           cfg->codewords ? cfg->n_codewords : 1, (float) std::sqrt(var), d->stream));
+    }
+    return 0;
+}
+
+static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
+                                     int32_t n_points, acg_ldpc_mc_result *res) {
+    if (!d || !cfg) {
+        set_error("null argument");
+        return 1;
+    }
+    if (!d->admm) {
+        set_error("acg_ldpc_mc_run_grid needs a QP-ADMM decoder");
+        return 1;
+    }
+    if (n_points < 1) {
+        set_error("acg_ldpc_mc_run_grid: n_points must be >= 1");
+        return 1;
+    }
+    if (!alpha || !mu || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    if (cfg->frames < 0 || (cfg->codewords && cfg->n_codewords <= 0)) {
+        set_error("bad mc cfg");
+        return 1;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::memset(res, 0, sizeof(*res) * (size_t) n_points);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    const double e_min = admm_device_e_min(d->admm);
+    std::vector<int32_t> run;  // the points that decode; the others are guard points (qp_admm.h:108-114)
+    for (int32_t k = 0; k < n_points; k++)
+        if (!(e_min * mu[k] <= alpha[k])) run.push_back(k);
+    const int64_t n_run = (int64_t) run.size();
+    const bool any_guard = n_run < n_points;
+    const bool single_launch = admm_device_has_grid_kernel(d->admm);
+    int rc = 0;
+    if (cfg->frames > 0 && (any_guard || (single_launch && n_run > 0))) {
+        if ((rc = ensure_codewords(d, cfg))) return rc;
+        const int n = d->c.n, nwords = (n + 31) / 32;
+        const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+        const int32_t *csr_row = nullptr, *csr_col = nullptr;
+        (void) admm_device_unfused_mc(d->admm, &csr_row, &csr_col);
+        const uint32_t *cw_dev = cfg->codewords ? d->cw_dev : nullptr;
+        const int64_t n_cw = cfg->codewords ? cfg->n_codewords : 1;
+        // frames in blocks of fb, points in chunks of npc: one launch covers npc * fb <= budget virtual frames (or one
+        // point's fb frames); its outputs use the handle's staging buffers
+        const int64_t budget = mc_grid_budget();
+        const int64_t fb = std::min<int64_t>(cfg->frames, budget);
+        const int64_t npc = single_launch ? std::max<int64_t>(1, std::min<int64_t>(budget / fb, std::max<int64_t>(n_run, 1))) : 1;
+        if ((rc = ensure_staging(d, npc * fb))) return rc;
+        // counters: row j < n_run = point run[j], row n_run = every guard point
+        if (n_run + 1 > d->grid_counters_rows) {
+            if (d->grid_counters) (void) hipFree(d->grid_counters);
+            d->grid_counters = nullptr;
+            d->grid_counters_rows = 0;
+            HIP_OK(hipMalloc((void **) &d->grid_counters, (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long)));
+            d->grid_counters_rows = n_run + 1;
+        }
+        HIP_OK(hipMemsetAsync(d->grid_counters, 0, (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long), d->stream));
+        std::vector<double> yh, ca, cm;
+        std::vector<unsigned char> pt, inv;
+        for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
+            const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
+            if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
+            if (any_guard)
+                HIP_OK(classify_grid_launch(d->st_y, host, nullptr, nullptr, nullptr, fc, 1, n, nwords, first, cw_dev, n_cw,
+                                            d->grid_counters + (size_t) n_run * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+            for (int64_t c0 = 0; single_launch && c0 < n_run; c0 += npc) {
+                const int64_t np = std::min(npc, n_run - c0);
+                ca.resize((size_t) np);
+                cm.resize((size_t) np);
+                for (int64_t j = 0; j < np; j++) {
+                    ca[(size_t) j] = alpha[run[(size_t) (c0 + j)]];
+                    cm[(size_t) j] = mu[run[(size_t) (c0 + j)]];
+                }
+                admm_grid_tables(d->admm, ca.data(), cm.data(), (int) np, pt, inv);
+                const size_t pt_bytes = (pt.size() + 255) & ~(size_t) 255;
+                if (pt_bytes + inv.size() > d->grid_tab_bytes) {
+                    if (d->grid_tab) (void) hipFree(d->grid_tab);
+                    d->grid_tab = nullptr;
+                    d->grid_tab_bytes = 0;
+                    HIP_OK(hipMalloc((void **) &d->grid_tab, pt_bytes + inv.size()));
+                    d->grid_tab_bytes = pt_bytes + inv.size();
+                }
+                // (the stream is idle here: the previous chunk ended with a synchronisation, so pt / inv may be rewritten)
+                HIP_OK(hipMemcpyAsync(d->grid_tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(hipMemcpyAsync(d->grid_tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
+                DecodeArgs a{};
+                a.y = d->st_y;
+                a.y_is_f64 = host;
+                a.frames = np * fc;
+                fill_channel(a, cfg->snr);
+                a.out_bits = d->st_bits;
+                a.out_ok = d->st_ok;
+                a.out_iters = d->st_iters;
+                admm_grid_bind(d->admm, d->grid_tab, d->grid_tab + pt_bytes, (uint32_t) fc);
+                rc = launch_decode(d, a, d->stream);
+                admm_grid_bind(d->admm, nullptr, nullptr, 0);
+                if (rc) return rc;
+                const int slot = d->last_slot;
+                HIP_OK(classify_grid_launch(d->st_y, host, d->st_bits, d->st_ok, d->st_iters, fc, np, n, nwords, first, cw_dev, n_cw,
+                                            d->grid_counters + (size_t) c0 * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+                HIP_OK(hipStreamSynchronize(d->stream));
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess)
+                    for (int64_t j = 0; j < np; j++) res[run[(size_t) (c0 + j)]].kernel_ms += (double) ms / (double) np;
+            }
+            HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
+        }
+        std::vector<unsigned long long> h((size_t) (n_run + 1) * MC_NCOUNTERS);
+        HIP_OK(hipMemcpy(h.data(), d->grid_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        auto fill = [&](acg_ldpc_mc_result &r, const unsigned long long *c) {
+            r.correct = (int64_t) c[MC_CORRECT];
+            r.pseudo = (int64_t) c[MC_PSEUDO];
+            r.total = (int64_t) c[MC_TOTAL];
+            r.sum_hamming = (int64_t) c[MC_HAM];
+            r.sum_hamming_ok = (int64_t) c[MC_HAM_OK];
+            r.sum_hamming_wrong = (int64_t) c[MC_HAM_WRONG];
+            r.sum_iters = (int64_t) c[MC_ITERS];
+        };
+        std::vector<char> is_run((size_t) n_points, 0);
+        for (int64_t j = 0; j < n_run; j++) {
+            is_run[(size_t) run[(size_t) j]] = 1;
+            if (single_launch) fill(res[run[(size_t) j]], &h[(size_t) j * MC_NCOUNTERS]);
+        }
+        for (int32_t k = 0; k < n_points; k++)
+            if (!is_run[(size_t) k]) fill(res[k], &h[(size_t) n_run * MC_NCOUNTERS]);
+    }
+    if (!single_launch && n_run > 0) {
+        // one point after another on this handle: acg_ldpc_mc_run with the handle re-parameterised in place
+        HIP_OK(hipStreamSynchronize(d->stream));
+        const double alpha0 = d->p.alpha, mu0 = d->p.mu;
+        std::string err;
+        for (int64_t j = 0; j < n_run && !rc; j++) {
+            const int32_t k = run[(size_t) j];
+            if (!admm_device_set_point(d->admm, alpha[k], mu[k], err)) {
+                set_error(err);
+                rc = 10;
+                break;
+            }
+            rc = acg_ldpc_mc_run_impl(d, cfg, &res[k]);  // (synchronises the stream before it returns)
+        }
+        const std::string first_err = rc ? g_err : std::string();
+        if (!admm_device_set_point(d->admm, alpha0, mu0, err) && !rc) {
+            set_error(err);
+            rc = 10;
+        } else if (rc) {
+            set_error(first_err);
+        }
+    }
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int32_t k = 0; k < n_points; k++) res[k].time_sec = wall;
+    return rc;
+}
+
+int acg_ldpc_mc_run_grid(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu, int32_t n_points,
+                         acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_grid_impl(d, cfg, alpha, mu, n_points, res); });
+}
+
 static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
     if (!d || !cfg || !y_dev) {
         set_error("null argument");
         return 1;
     }
-    std::lock_guard<std::mutex> lk(d->mu);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     if (int rc = ensure_codewords(d, cfg)) return rc;
     const double var = std::pow(10, -(cfg->snr / 10)) / 2;

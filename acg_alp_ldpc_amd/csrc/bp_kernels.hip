@@ -130,8 +130,41 @@ __global__ void awgn_kernel(float *y, int64_t frames, int n, int nwords, int64_t
     }
 }
 
+// Classification of ONE frame by one wavefront (experiment.h:109-120): raw-channel Hamming count from y, and
+// correct <=> ok and the word equals the sent one.  bits == null stands for the all-zero word.
+template <typename Y>
+__device__ __forceinline__ void classify_frame(const Y *y, const uint32_t *bits, bool okf, const uint32_t *cw, int n, int nwords,
+                                               const int32_t *row_ptr, const int32_t *edge_var, int m, int lane, int &ham,
+                                               bool &correct, bool &pseudo) {
+    ham = 0;
+    for (int v = lane; v < n; v += 64) {
+        const uint32_t bit = cw ? ((cw[v >> 5] >> (v & 31)) & 1u) : 0u;
+        const Y yv = y[v];
+        ham += ((!bit && yv <= (Y) 0) || (bit && yv > (Y) 0)) ? 1 : 0;
+    }
+    bool neq = false;
+    for (int w = lane; w < nwords; w += 64) neq |= ((bits ? bits[w] : 0u) != (cw ? cw[w] : 0u));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ham += __shfl_xor(ham, o, 64);
+    const bool differ = __ballot(neq) != 0ull;
+    if (row_ptr) {  // decoders that always report ok (QP-ADMM, qp_admm.h:177): IsCodeword here (experiment.h:111)
+        bool sbad = false;
+        for (int c = lane; c < m; c += 64) {
+            uint32_t sy = 0;
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
+                const int v = edge_var[e];
+                sy ^= bits ? (bits[v >> 5] >> (v & 31)) & 1u : 0u;
+            }
+            sbad |= (sy != 0u);
+        }
+        okf = okf && (__ballot(sbad) == 0ull);
+    }
+    correct = okf && !differ;
+    pseudo = okf && differ;
+}
+
 // Per-frame classification of exp() (experiment.h:109-120) for engines without an in-kernel generator:
-// one wavefront per frame; correct <=> ok and bits == sent word; raw-channel Hamming count from y.
+// one wavefront per frame.
 __global__ void classify_kernel(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
                                 int64_t frames, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
                                 int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr,
@@ -142,33 +175,12 @@ __global__ void classify_kernel(const float *y, const uint32_t *bits, const uint
     unsigned long long c_ok = 0, c_ps = 0, c_tot = 0, c_h = 0, c_hok = 0, c_hw = 0, c_it = 0;
     for (int64_t f = wid; f < frames; f += nw) {
         const uint32_t *cw = cw_packed ? cw_packed + (size_t) ((first_frame + f) % n_cw) * nwords : nullptr;
-        int ham = 0;
-        for (int v = lane; v < n; v += 64) {
-            const uint32_t bit = cw ? ((cw[v >> 5] >> (v & 31)) & 1u) : 0u;
-            const float yv = y[(size_t) f * n + v];
-            ham += ((!bit && yv <= 0.0f) || (bit && yv > 0.0f)) ? 1 : 0;
-        }
-        bool neq = false;
-        for (int w = lane; w < nwords; w += 64) neq |= (bits[(size_t) f * nwords + w] != (cw ? cw[w] : 0u));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ham += __shfl_xor(ham, o, 64);
-        const bool differ = __ballot(neq) != 0ull;
-        bool okf = ok[f] != 0;
-        if (row_ptr) {  // decoders that always report ok (QP-ADMM, qp_admm.h:177): IsCodeword here (experiment.h:111)
-            bool sbad = false;
-            for (int c = lane; c < m; c += 64) {
-                uint32_t sy = 0;
-                for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
-                    const int v = edge_var[e];
-                    sy ^= (bits[(size_t) f * nwords + (v >> 5)] >> (v & 31)) & 1u;
-                }
-                sbad |= (sy != 0u);
-            }
-            okf = okf && (__ballot(sbad) == 0ull);
-        }
-        const bool correct = okf && !differ;
+        int ham;
+        bool correct, pseudo;
+        classify_frame(y + (size_t) f * n, bits + (size_t) f * nwords, ok[f] != 0, cw, n, nwords, row_ptr, edge_var, m, lane, ham,
+                       correct, pseudo);
         c_ok += correct;
-        c_ps += (okf && differ);
+        c_ps += pseudo;
         c_tot += 1;
         c_h += ham;
         c_hok += correct ? ham : 0;
@@ -184,6 +196,71 @@ __global__ void classify_kernel(const float *y, const uint32_t *bits, const uint
         atomicAdd(&counters[MC_HAM_WRONG], c_hw);
         atomicAdd(&counters[MC_ITERS], c_it);
     }
+}
+
+// The same for a parameter grid (acg_ldpc_mc_run_grid): virtual frame g = point * frames + f carries the outputs of frame
+// f decoded with the parameters of `point`; its symbols and sent word are those of frame f, its counters row is
+// counters[point].  bits == null (then ok and iters are null too): guard points — all-zero words, ok = false, no sweeps.
+// A wavefront takes a contiguous run of virtual frames, so it changes point (and flushes its sums) rarely.
+template <typename Y>
+__global__ void classify_grid_kernel(const Y *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
+                                     int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
+                                     unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t) gridDim.x * (blockDim.x >> 6);
+    const int64_t total = frames * points, per = (total + nw - 1) / nw;
+    const int64_t g0 = wid * per, g1 = g0 + per < total ? g0 + per : total;
+    unsigned long long c_ok = 0, c_ps = 0, c_tot = 0, c_h = 0, c_hok = 0, c_hw = 0, c_it = 0;
+    auto flush = [&](int64_t point) {
+        if (lane == 0 && c_tot) {
+            unsigned long long *row = counters + (size_t) point * MC_NCOUNTERS;
+            atomicAdd(&row[MC_CORRECT], c_ok);
+            atomicAdd(&row[MC_PSEUDO], c_ps);
+            atomicAdd(&row[MC_TOTAL], c_tot);
+            atomicAdd(&row[MC_HAM], c_h);
+            atomicAdd(&row[MC_HAM_OK], c_hok);
+            atomicAdd(&row[MC_HAM_WRONG], c_hw);
+            atomicAdd(&row[MC_ITERS], c_it);
+        }
+        c_ok = c_ps = c_tot = c_h = c_hok = c_hw = c_it = 0;
+    };
+    int64_t point = g0 < g1 ? g0 / frames : 0;
+    for (int64_t g = g0; g < g1; ++g) {
+        if (g >= (point + 1) * frames) {
+            flush(point);
+            point = g / frames;
+        }
+        const int64_t f = g - point * frames;
+        const uint32_t *cw = cw_packed ? cw_packed + (size_t) ((first_frame + f) % n_cw) * nwords : nullptr;
+        int ham;
+        bool correct, pseudo;
+        classify_frame(y + (size_t) f * n, bits ? bits + (size_t) g * nwords : nullptr, bits ? ok[g] != 0 : false, cw, n, nwords, row_ptr,
+                       edge_var, m, lane, ham, correct, pseudo);
+        c_ok += correct;
+        c_ps += pseudo;
+        c_tot += 1;
+        c_h += ham;
+        c_hok += correct ? ham : 0;
+        c_hw += correct ? 0 : ham;
+        c_it += (bits && iters) ? iters[g] : 0;
+    }
+    flush(point);
+}
+
+hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                int64_t frames, int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
+                                int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                hipStream_t s) {
+    int grid = (int) std::min<int64_t>((frames * points + 3) / 4, 256 * 8);
+    if (grid < 1) grid = 1;
+    if (y_is_f64)
+        hipLaunchKernelGGL(classify_grid_kernel<double>, dim3(grid), dim3(256), 0, s, (const double *) y, bits, ok, iters, frames, points,
+                           n, nwords, first_frame, cw_packed, n_cw, counters, row_ptr, edge_var, m);
+    else
+        hipLaunchKernelGGL(classify_grid_kernel<float>, dim3(grid), dim3(256), 0, s, (const float *) y, bits, ok, iters, frames, points, n,
+                           nwords, first_frame, cw_packed, n_cw, counters, row_ptr, edge_var, m);
+    return hipGetLastError();
 }
 
 hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,

@@ -102,6 +102,41 @@ def run_experiment(decoder, codewords, H, snr, frames=None, first_frame=0, noise
                             kernel_ms=res.kernel_ms)
 
 
+def run_experiment_grid(decoder, codewords, H, snr, alphas, mus, frames=None, first_frame=0, noise="host", seed=1):
+    """The (alpha, mu) loop of qpadmm_params.cpp:64-77 in one call on one handle (acg_ldpc_mc_run_grid): point k decodes
+    the same frames as every other point with (alphas[k], mus[k]) in place of the decoder's own alpha and mu.
+
+    decoder: a QPADMMDecoder; its max_iter, eps_stop, early_exit, precision and engine apply.  Returns one
+    ExperimentResult per point, equal to run_experiment on QPADMMDecoder(alphas[k], mus[k], ...) except that guard
+    points (e_min*mu <= alpha) are counted as failures instead of refused, time_sec is the wall time of the whole call
+    and kernel_ms the point's share of device time.  Other arguments as run_experiment."""
+    a = np.ascontiguousarray(alphas, dtype=np.float64).ravel()
+    m = np.ascontiguousarray(mus, dtype=np.float64).ravel()
+    if a.shape != m.shape:
+        raise _lib.LdpcError("run_experiment_grid: alphas and mus must have the same length (%d != %d)" % (a.size, m.size))
+    with decoder._lease(H) as (h, code):
+        cfg = McCfg()
+        cw = None
+        if codewords is not None:
+            cw = np.ascontiguousarray(codewords, dtype=np.uint8)
+            assert cw.ndim == 2 and cw.shape[1] == code.n
+            cfg.codewords = cw.ctypes.data
+            cfg.n_codewords = cw.shape[0]
+        if frames is None:
+            if cw is None:
+                raise ValueError("frames required without codewords")
+            frames = cw.shape[0]
+        cfg.frames = int(frames)
+        cfg.first_frame = int(first_frame)
+        cfg.snr = float(snr)
+        cfg.seed = int(seed)
+        cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
+        res = (McResult * max(1, a.size))()
+        check(lib().acg_ldpc_mc_run_grid(h, C.byref(cfg), a.ctypes.data, m.ctypes.data, int(a.size), res))
+    return [ExperimentResult(**{f: getattr(r, f) for f in ExperimentResult.FIELDS}, time_sec=r.time_sec,
+                             kernel_ms=r.kernel_ms) for r in res[:a.size]]
+
+
 def run_experiment_sharded(decoder, codewords, H, snr, frames, rank=0, world=1, noise="device", seed=1, group=None):
     """One rank's shard + host-side sum of the counters across ranks.
 

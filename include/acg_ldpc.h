@@ -222,6 +222,28 @@ int acg_ldpc_mc_run(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, acg_ldpc_
 /* merge_exp_results (experiment.h:70-78): a += b (used to combine per-GPU shards on the host) */
 void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b);
 
+/* replaces the double loop of qpadmm_params.cpp:64-77: acg_ldpc_mc_run for n_points parameter pairs (alpha[k], mu[k]) of
+ * a QP-ADMM decoder on ONE handle.  dec's own alpha and mu are ignored in this call; its max_iter, eps_stop, early_exit,
+ * precision, engine and device apply.  Every point simulates the same global frames [first_frame, first_frame + frames)
+ * with the same codewords and the same noise, generated once.  res[k] (n_points entries) holds, field for field, what
+ * acg_ldpc_mc_run returns on a decoder created with (alpha[k], mu[k]) and the same remaining parameters, except:
+ *   time_sec   of EVERY entry is the wall time of the whole call (not a per-point time: do not add them up);
+ *   kernel_ms  of an entry is the point's share of device time: the device time of the launch (chunk of points) it ran
+ *              in divided by the number of points in that chunk.
+ * Guard points, e_min*mu <= alpha (qp_admm.h:108-114), are not an error here (acg_ldpc_mc_run refuses them): no sweep
+ * runs and they return what the reference's loop computes — correct = pseudo = 0, total = frames, sum_iters = 0 and the
+ * raw-channel Hamming sums, all of them in sum_hamming_wrong (experiment.h:109-120).
+ * Sharding by first_frame / frames and acg_ldpc_mc_merge per point work as for acg_ldpc_mc_run.
+ * Single launch: decoders on the workgroup-per-frame kernel (lanes_per_frame 0 or 256 on a code it accepts, max_iter > 0;
+ * acg_ldpc_decoder_describe says mc_grid=single-launch) decode a chunk of points x frames per launch; the chunk is sized
+ * so that its per-frame outputs are those of a 65536-frame decode.  Every other QP-ADMM decoder (lanes_per_frame
+ * 16/32/64, the streamed engine, max_iter = 0; mc_grid=per-point) runs the points one after another on this handle,
+ * re-parameterised in place — same results, no handle created or destroyed.
+ * Errors (non-zero, message in acg_ldpc_last_error, nothing launched): a decoder that is not QP-ADMM, n_points < 1,
+ * null pointers. */
+int acg_ldpc_mc_run_grid(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
+                         int32_t n_points, acg_ldpc_mc_result *res);
+
 /* ---- host-side generators used by the reference's drivers (bit-exact, libstdc++) ----------- */
 
 /* replaces gen_random_codewords (utils/channel.h:28-44) with std::mt19937(seed): row i of G (k x n bytes)
