@@ -25,12 +25,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "../../include/acg_ldpc.h"
-#include "kernels.hpp"
-#include "ldpc_internal.hpp"
+#include "device_mem.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 
@@ -107,19 +107,9 @@ struct AdmmDevTables {
     int32_t lds_bytes_per_frame;
 };
 
-struct AdmmDevice;
-void admm_device_destroy(AdmmDevice *d);
-// streamed engine (admm_streamed.hip)
-struct AdmmStream;
-AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
-void admm_stream_destroy(AdmmStream *s);
-void admm_stream_info(const AdmmStream *s, int *slabs, int64_t *slab_bytes, int *f32);
-bool admm_stream_set_point(AdmmStream *s, double alpha, double mu);
-hipError_t admm_stream_launch(AdmmStream *s, const DecodeArgs &a, hipStream_t st);
-
 struct AdmmDevice {
     AdmmDevTables t{};
-    std::vector<void *> allocs;
+    std::vector<DeviceBuf> allocs;
     int L = 64, f32 = 0, block = 256, frames_per_block = 4, grid_cap = 256;
     bool reg = false;  // row state in registers (ADMM_NGP variant)
     bool blockmode = false;  // workgroup-per-frame kernel
@@ -129,7 +119,8 @@ struct AdmmDevice {
     bool guard = false;  // e_min*mu <= alpha  (qp_admm.h:108-114)
     bool budget0 = false;  // max_iter == 0: handled by admm_budget0_kernel
     double alpha = 0, mu = 0, eps = 0;
-    AdmmStream *st = nullptr;  // streamed engine (state in HBM); null = the LDS kernels above
+    AdmmStream *st = nullptr;  // streamed engine (admm_streamed.hip: state in HBM); null = the LDS kernels above
+    ~AdmmDevice() { admm_stream_destroy(st); }
     // parameter grid (acg_ldpc_mc_run_grid)
     double e_min = 1e9;              // min over e (qp_admm.h:108-111)
     std::vector<double> e_of_slot;   // [n_vpass*L] e of the variable in that thread slot (LDS kernels); < 0 = no variable
@@ -994,33 +985,17 @@ static const void *admm_block_ptr(int f32, bool ee, int passes, bool lean) {
     return ee ? admm_block_ptr_t<double, true, false, GRID...>(passes) : admm_block_ptr_t<double, false, false, GRID...>(passes);
 }
 
-template <typename T>
-static void *upload_vec(const std::vector<T> &h, std::vector<void *> &allocs, std::string &err) {
-    void *d = nullptr;
-    size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    if (hipMalloc(&d, bytes) != hipSuccess) {
-        err = "hipMalloc failed";
-        return nullptr;
-    }
-    if (!h.empty() && hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        err = "hipMemcpy failed";
-        return nullptr;
-    }
-    allocs.push_back(d);
-    return d;
-}
-
 static const char *const ADMM_NO_FIT = "QP-ADMM frame state does not fit in LDS (160 KiB per CU)";
 
 static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
     const AdmmLayout &A = c.admm;
-    auto *d = new AdmmDevice();
+    std::unique_ptr<AdmmDevice> own(new AdmmDevice());
+    AdmmDevice *d = own.get();
     d->alpha = p.alpha;
     d->mu = p.mu;
     d->eps = p.eps_stop;
     if (p.precision == ACG_LDPC_PREC_F16) {
         err = "ACG_LDPC_PREC_F16 exists for the fused min-sum decoder only";
-        delete d;
         return nullptr;
     }
     d->f32 = (p.precision == ACG_LDPC_PREC_F32) ? 1 : 0;
@@ -1052,12 +1027,10 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         d->blockmode = true;
     } else if (p.lanes_per_frame == ADMM_BLK) {
         err = "lanes_per_frame = 256 needs at most 1024 constraint groups and variables";
-        delete d;
         return nullptr;
     }
     if (!d->blockmode && L != 16 && L != 32 && L != 64) {
         err = "lanes_per_frame must be 0, 16, 32, 64 (or 256 for QP-ADMM)";
-        delete d;
         return nullptr;
     }
     d->L = L;
@@ -1080,7 +1053,6 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
     t.zero_gslot = A.n_grp;
     if (t.G_pad >= (1 << 20) || A.n_var >= (1 << 24)) {
         err = "code too large for the fused QP-ADMM kernel";
-        delete d;
         return nullptr;
     }
     t.n_vpass = (A.n_var + L - 1) / L;
@@ -1161,7 +1133,6 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         };
         if (u_addr(t.U_slots, 0) + (uint32_t) t.nwords * 4 + 1024u > 0xFFFFu) {  // (+1 KiB: the kernel's static LDS words sit in front and are added to the 16-bit list addresses)
             err = "QP-ADMM frame state exceeds the 64 KiB the workgroup-per-frame kernel addresses";
-            admm_device_destroy(d);
             return nullptr;
         }
         const std::vector<int> &slot_of = P.slot_of_grp, &cell_of = P.cell_of_var;
@@ -1220,15 +1191,14 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         }
         if (!list_ok) {
             err = "a variable in more than 255 checks: use lanes_per_frame 16/32/64 for QP-ADMM";
-            admm_device_destroy(d);
             return nullptr;
         }
-        t.blk_mem = (const uint32_t *) upload_vec(blk_mem, d->allocs, err);
-        t.blk_list = (const uint32_t *) upload_vec(blk_list, d->allocs, err);
-        t.blk_mlw = (const int32_t *) upload_vec(blk_mlw, d->allocs, err);
-        t.grp_type_slot = (const uint8_t *) upload_vec(type_slot, d->allocs, err);
-        t.blk_generic = (const uint8_t *) upload_vec(blk_generic, d->allocs, err);
-        t.blk_cell = (const int32_t *) upload_vec(blk_cell, d->allocs, err);
+        t.blk_mem = upload_keep(blk_mem, d->allocs);
+        t.blk_list = upload_keep(blk_list, d->allocs);
+        t.blk_mlw = upload_keep(blk_mlw, d->allocs);
+        t.grp_type_slot = upload_keep(type_slot, d->allocs);
+        t.blk_generic = upload_keep(blk_generic, d->allocs);
+        t.blk_cell = upload_keep(blk_cell, d->allocs);
         t.cell_is_slot = 1;
         for (int sidx = 0; sidx < t.n_vpass * L; sidx++)
             if (blk_cell[sidx] >= 0 && blk_cell[sidx] != sidx) t.cell_is_slot = 0;
@@ -1239,23 +1209,23 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
             for (int w_ = 0; w_ < 4; w_++) d->blk_lean = d->blk_lean && blk_mlw[(size_t) p_ * 4 + w_] <= admm_vk(p_);
         ok = t.blk_mem && t.blk_list && t.blk_mlw && t.grp_type_slot && t.blk_generic && t.blk_cell;
     }
-    t.grp_mem = (const uint32_t *) upload_vec(grp_mem, d->allocs, err);
-    t.grp_type = (const uint8_t *) upload_vec(grp_type, d->allocs, err);
-    t.var_of_slot = (const int32_t *) upload_vec(var_of_slot, d->allocs, err);
-    t.v_maxlist = (const int32_t *) upload_vec(v_maxlist, d->allocs, err);
-    t.v_list_off = (const int32_t *) upload_vec(v_list_off, d->allocs, err);
-    t.v_list = (const uint32_t *) upload_vec(v_list, d->allocs, err);
+    t.grp_mem = upload_keep(grp_mem, d->allocs);
+    t.grp_type = upload_keep(grp_type, d->allocs);
+    t.var_of_slot = upload_keep(var_of_slot, d->allocs);
+    t.v_maxlist = upload_keep(v_maxlist, d->allocs);
+    t.v_list_off = upload_keep(v_list_off, d->allocs);
+    t.v_list = upload_keep(v_list, d->allocs);
     if (d->f32) {
         std::vector<float> inv32(inv64.begin(), inv64.end());
-        t.inv_coef = upload_vec(inv32, d->allocs, err);
+        t.inv_coef = upload_keep(inv32, d->allocs);
     } else {
-        t.inv_coef = upload_vec(inv64, d->allocs, err);
+        t.inv_coef = upload_keep(inv64, d->allocs);
     }
-    t.row_ptr = (const int32_t *) upload_vec(c.row_ptr, d->allocs, err);
-    t.edge_var = (const int32_t *) upload_vec(c.edge_var, d->allocs, err);
+    t.row_ptr = upload_keep(c.row_ptr, d->allocs);
+    t.edge_var = upload_keep(c.edge_var, d->allocs);
     ok = ok && t.grp_mem && t.grp_type && t.var_of_slot && t.v_maxlist && t.v_list_off && t.v_list && t.inv_coef && t.row_ptr && t.edge_var;
     if (!ok) {
-        admm_device_destroy(d);
+        err = acg_ldpc_last_error();
         return nullptr;
     }
     const size_t ts = d->f32 ? 4 : 8;
@@ -1268,7 +1238,6 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         d->lds_block = per_frame;
         if (per_frame > 160 * 1024) {
             err = ADMM_NO_FIT;
-            admm_device_destroy(d);
             return nullptr;
         }
         int per_cu = 0;
@@ -1292,7 +1261,7 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
             per_cu = (mc == 0) ? occ : std::max(per_cu, occ);  // frames are handed out dynamically: a generous grid is safe
         }
         d->grid_cap = per_cu * cu_count;
-        return d;
+        return own.release();
     }
     const int fpw = 64 / L;
     // wavefronts per workgroup: whatever packs the most frames into the 160 KiB of a CU
@@ -1307,7 +1276,6 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
     }
     if (per_frame * fpw * waves > 160 * 1024) {
         err = ADMM_NO_FIT;
-        admm_device_destroy(d);
         return nullptr;
     }
     d->block = waves * 64;
@@ -1321,7 +1289,6 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         if (d->lds_block > 64 * 1024 &&
             hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block) != hipSuccess) {
             err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
-            admm_device_destroy(d);
             return nullptr;
         }
         int occ = 0;
@@ -1330,13 +1297,14 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         per_cu = (mc == 0) ? occ : std::min(per_cu, occ);
     }
     d->grid_cap = per_cu * cu_count;
-    return d;
+    return own.release();
 }
 
 // streamed engine: the guard, budget-0 and classification paths need only the CSR and the shape; the sweeps are
 // admm_streamed.hip's
 static AdmmDevice *admm_device_create_streamed(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
-    auto *d = new AdmmDevice();
+    std::unique_ptr<AdmmDevice> own(new AdmmDevice());
+    AdmmDevice *d = own.get();
     d->alpha = p.alpha;
     d->mu = p.mu;
     d->eps = p.eps_stop;
@@ -1355,21 +1323,20 @@ static AdmmDevice *admm_device_create_streamed(const Code &c, const acg_ldpc_par
     d->t.n_grp = c.admm.n_grp;
     d->t.nwords = (c.n + 31) / 32;
     d->t.lds_bytes_per_frame = 0;
-    d->t.row_ptr = (const int32_t *) upload_vec(c.row_ptr, d->allocs, err);
-    d->t.edge_var = (const int32_t *) upload_vec(c.edge_var, d->allocs, err);
+    d->t.row_ptr = upload_keep(c.row_ptr, d->allocs);
+    d->t.edge_var = upload_keep(c.edge_var, d->allocs);
     if (!d->t.row_ptr || !d->t.edge_var) {
-        admm_device_destroy(d);
+        err = acg_ldpc_last_error();
         return nullptr;
     }
     d->st = admm_stream_create(c, p, cu_count, err);
     if (!d->st) {
-        admm_device_destroy(d);
         return nullptr;
     }
     int slabs = 0;
     admm_stream_info(d->st, &slabs, nullptr, nullptr);
     d->grid_cap = slabs;
-    return d;
+    return own.release();
 }
 
 // engine selection (acg_ldpc.h): AUTO keeps the LDS kernels wherever they accept the code and takes the streamed engine
@@ -1392,12 +1359,7 @@ AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_c
     return admm_device_create_streamed(c, p, cu_count, err);
 }
 
-void admm_device_destroy(AdmmDevice *d) {
-    if (!d) return;
-    admm_stream_destroy(d->st);
-    for (void *p : d->allocs) (void) hipFree(p);
-    delete d;
-}
+void admm_device_destroy(AdmmDevice *d) { delete d; }
 
 // true when Monte-Carlo runs should go AWGN kernel -> decode -> classify kernel instead of the fused MC kernel
 bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var) {

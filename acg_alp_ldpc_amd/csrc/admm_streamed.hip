@@ -25,11 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 
-#include "../../include/acg_ldpc.h"
-#include "kernels.hpp"
-#include "ldpc_internal.hpp"
+#include "device_mem.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 
@@ -188,30 +188,14 @@ __global__ void __launch_bounds__(ADMM_ST_WAVES * 64) admm_streamed_kernel(const
 
 struct AdmmStream {
     AdmmStreamDev t{};
-    std::vector<void *> allocs;
-    unsigned char *ws = nullptr;
+    std::vector<DeviceBuf> allocs;
+    DeviceBuf ws;
     int slabs = 0, f32 = 0;
     double alpha = 0, mu = 0, eps = 0;
     std::vector<double> e;  // [n_var] (admm_stream_set_point)
 };
 
-void admm_stream_destroy(AdmmStream *s) {
-    if (!s) return;
-    for (void *p : s->allocs) (void) hipFree(p);
-    if (s->ws) (void) hipFree(s->ws);
-    delete s;
-}
-
-template <typename V>
-static bool stream_upload(const V &h, std::vector<void *> &allocs, const void **out) {
-    void *d = nullptr;
-    const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(h[0]);
-    if (hipMalloc(&d, bytes) != hipSuccess) return false;
-    allocs.push_back(d);
-    if (!h.empty() && hipMemcpy(d, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess) return false;
-    *out = d;
-    return true;
-}
+void admm_stream_destroy(AdmmStream *s) { delete s; }
 
 // Workspace: one slab per workgroup, (C + n_var + n) x 64 words, plain hipMalloc when the decoder is created.
 // Slabs = min(2 x CUs, what fits in a quarter of the free device memory), at least one; none fitting is an error.
@@ -221,7 +205,7 @@ AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_c
         err = "code too large for the streamed QP-ADMM engine (2^28 constraint rows, 2^30 variables)";
         return nullptr;
     }
-    auto *s = new AdmmStream();
+    std::unique_ptr<AdmmStream> s(new AdmmStream());
     s->f32 = (p.precision == ACG_LDPC_PREC_F32) ? 1 : 0;
     s->alpha = p.alpha;
     s->mu = p.mu;
@@ -238,26 +222,20 @@ AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_c
         const double Acoef = (p.mu * c.admm.e[i] - p.alpha) / 2;  // qp_admm.h:125
         inv64[i] = -1.0 / (2 * Acoef);                           // qp_admm.h:126
     }
-    const void *vp = nullptr, *ve = nullptr, *gr = nullptr, *ic = nullptr;
-    bool ok = stream_upload(h.var_ptr, s->allocs, &vp) && stream_upload(h.var_ent, s->allocs, &ve) &&
-              stream_upload(h.grp, s->allocs, &gr);
-    if (ok && s->f32) ok = stream_upload(std::vector<float>(inv64.begin(), inv64.end()), s->allocs, &ic);
-    else if (ok) ok = stream_upload(inv64, s->allocs, &ic);
-    if (!ok) {
+    t.var_ptr = upload_keep(h.var_ptr, s->allocs);
+    t.var_ent = upload_keep(h.var_ent, s->allocs);
+    t.grp = upload_keep(h.grp, s->allocs);
+    if (s->f32) t.inv_coef = upload_keep(std::vector<float>(inv64.begin(), inv64.end()), s->allocs);
+    else t.inv_coef = upload_keep(inv64, s->allocs);
+    if (!t.var_ptr || !t.var_ent || !t.grp || !t.inv_coef) {
         err = "hipMalloc / hipMemcpy of the streamed QP-ADMM tables failed";
-        admm_stream_destroy(s);
         return nullptr;
     }
-    t.var_ptr = (const int32_t *) vp;
-    t.var_ent = (const uint32_t *) ve;
-    t.grp = (const uint32_t *) gr;
-    t.inv_coef = ic;
     const size_t ts = s->f32 ? 4 : 8;
     t.slab_bytes = (int64_t) ((((size_t) h.n_con + h.n_var + h.n) * 64 * ts + 255) & ~(size_t) 255);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
         err = "hipMemGetInfo failed";
-        admm_stream_destroy(s);
         return nullptr;
     }
     const size_t budget = free_b / 4;
@@ -265,17 +243,14 @@ AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_c
     if (fit < 1) {
         err = "streamed QP-ADMM engine: one slab of " + std::to_string(t.slab_bytes) + " bytes exceeds a quarter of the free device memory (" +
               std::to_string(free_b) + " bytes)";
-        admm_stream_destroy(s);
         return nullptr;
     }
     s->slabs = (int) std::min<size_t>((size_t) 2 * std::max(cu_count, 1), fit);
-    if (hipMalloc((void **) &s->ws, (size_t) s->slabs * (size_t) t.slab_bytes) != hipSuccess) {
-        s->ws = nullptr;
+    if (s->ws.reserve((size_t) s->slabs * (size_t) t.slab_bytes)) {
         err = "hipMalloc of the streamed QP-ADMM workspace (" + std::to_string((size_t) s->slabs * (size_t) t.slab_bytes) + " bytes) failed";
-        admm_stream_destroy(s);
         return nullptr;
     }
-    return s;
+    return s.release();
 }
 
 // Re-parameterise in place (parameter grids, acg_ldpc_mc_run_grid): alpha, mu and the inv_coef table, built as in
@@ -310,7 +285,7 @@ hipError_t admm_stream_launch(AdmmStream *s, const DecodeArgs &a, hipStream_t st
     if (grid <= 0) return hipSuccess;
     AdmmStreamDev tt = s->t;
     DecodeArgs aa = a;
-    unsigned char *ws = s->ws;
+    unsigned char *ws = s->ws.as<unsigned char>();
     if (s->f32) {
         float alpha = (float) s->alpha, mu = (float) s->mu, eps = (float) s->eps;
         void *args[6] = {&tt, &aa, &alpha, &mu, &eps, &ws};

@@ -18,67 +18,13 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/acg_ldpc.h"
-#include "kernels.hpp"
-#include "ldpc_internal.hpp"
+#include "device_mem.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
-
-hipError_t bp_launch(const void *kernel, const BpTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
-                     hipStream_t s);
-const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat);
-hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s);
-hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s);
-hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,
-                       const uint32_t *cw_packed, int64_t n_cw, float sigma, hipStream_t s);
-
-const void *bp_block_kernel_ptr(int algo, int f64, int L, bool mc, bool idxlds, bool idxreg, bool regular);
-const void *bp_kernel_ptr_dbg(int f64, int L);
-const void *bp_block_kernel_ptr_dbg(int f64);
-const void *bp_pair_kernel_ptr(int L, bool regular);
-const void *bp_layered_kernel_ptr(int G, int waves, bool qc_arith, bool f16, int algo, bool mc);
-hipError_t bp_layered_launch(const void *kernel, const LayerTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s);
-const void *bp_streamed_ptr(int algo, int f64);
-const void *bp_streamed_ring_ptr(int algo, bool nt);
-const void *bp_streamed_ring_ptr_dbg();
-hipError_t bp_streamed_ring_launch(const void *kernel, const StreamTables &t, const DecodeArgs &a, uint32_t *ws, int grid, hipStream_t s);
-hipError_t bp_streamed_launch(const void *kernel, const StreamTables &t, const DecodeArgs &a, uint32_t *ws, int grid,
-                              int block, hipStream_t s);
-hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
-                           int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
-                           unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
-                           hipStream_t s);
-
-struct AdmmDevice;  // admm_kernels.hip
-AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
-void admm_device_destroy(AdmmDevice *d);
-hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::string &err);
-void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int *frames_per_block, int *grid);
-bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var);
-bool admm_device_streamed(const AdmmDevice *d, int *slabs, int64_t *slab_bytes, int *f32);
-// parameter grid (acg_ldpc_mc_run_grid)
-double admm_device_e_min(const AdmmDevice *d);
-bool admm_device_has_grid_kernel(const AdmmDevice *d);
-void admm_grid_tables(const AdmmDevice *d, const double *alpha, const double *mu, int np, std::vector<unsigned char> &pt,
-                      std::vector<unsigned char> &inv);
-void admm_grid_bind(AdmmDevice *d, const void *pt_dev, const void *inv_dev, uint32_t frames_per_point);
-bool admm_device_set_point(AdmmDevice *d, double alpha, double mu, std::string &err);
-hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
-                                int64_t frames, int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
-                                int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
-                                hipStream_t s);
-
-#define HIP_OK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                       \
-            return 10;                                                                          \
-        }                                                                                       \
-    } while (0)
 
 // No C++ exception may cross the extern "C" boundary (std::bad_alloc from a vector, std::system_error from std::thread, ...):
 // every entry point that can throw runs its body through guarded() and reports an error code + message instead.
@@ -96,14 +42,6 @@ static int guarded(F &&body) noexcept {
         set_error("internal exception");
         return 13;
     }
-}
-
-template <typename T>
-static int upload(const std::vector<T> &h, T **d, size_t min_elems = 1) {
-    size_t n = std::max(h.size(), min_elems);
-    HIP_OK(hipMalloc((void **) d, n * sizeof(T)));
-    if (!h.empty()) HIP_OK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
 }
 
 // A few persistent host threads for the byte shuffling of the host-buffer entry points (pageable user memory -> pinned
@@ -181,25 +119,15 @@ struct HostPipe {
     static constexpr int NBUF = 2;
     int64_t chunk = 0;       // frames per chunk the buffers are sized for
     size_t y_bytes = 0;      // bytes per frame of the symbol buffers
-    void *pin_y[NBUF] = {};
-    unsigned char *pin_out[NBUF] = {};  // [frames][nwords] words | [frames] sweep counts | [frames] flags of the chunk in flight:
-    void *dev_y[NBUF] = {};             // one region, so the results come back in ONE device-to-host copy
-    unsigned char *dev_out[NBUF] = {};
+    PinnedBuf pin_y[NBUF], pin_out[NBUF];  // out: [frames][nwords] words | [frames] sweep counts | [frames] flags of the chunk in
+    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight: one region, so the results come back in ONE device-to-host copy
     hipStream_t stream[NBUF] = {};
     hipEvent_t done[NBUF] = {};
     void release() {
-        for (int b = 0; b < NBUF; b++) {
-            if (pin_y[b]) (void) hipHostFree(pin_y[b]);
-            if (pin_out[b]) (void) hipHostFree(pin_out[b]);
-            if (dev_y[b]) (void) hipFree(dev_y[b]);
-            if (dev_out[b]) (void) hipFree(dev_out[b]);
-            pin_y[b] = dev_y[b] = nullptr;
-            pin_out[b] = dev_out[b] = nullptr;
-        }
+        for (int b = 0; b < NBUF; b++) pin_y[b].reset(), pin_out[b].reset(), dev_y[b].reset(), dev_out[b].reset();
         chunk = 0;
     }
     ~HostPipe() {
-        release();
         for (int b = 0; b < NBUF; b++) {
             if (done[b]) (void) hipEventDestroy(done[b]);
             if (stream[b]) (void) hipStreamDestroy(stream[b]);
@@ -215,13 +143,34 @@ using namespace acg;
 // (HIP virtual-memory-management API).  Why: see decoder_setup_streamed — a physically CONTIGUOUS backing of the slabs is the
 // slow mode of bp_streamed_ring_kernel on slabs beyond the Infinity Cache (181 ms against 158 ms per launch on configs[4]),
 // and plain hipMalloc hands out either kind depending on the allocation history of the process.
+// Move-only owner; adopt() makes it the owner of one plain allocation instead (the small-workspace and fallback path).
 struct ScatteredAlloc {
     void *va = nullptr;
     size_t bytes = 0, chunk = 0;
     std::vector<hipMemGenericAllocationHandle_t> handles;
     std::vector<char> mapped;
+    bool plain = false;  // va is ONE allocation (adopt), released by hipFree
+    ScatteredAlloc() = default;
+    ScatteredAlloc(ScatteredAlloc &&o) noexcept { *this = std::move(o); }
+    ScatteredAlloc &operator=(ScatteredAlloc &&o) noexcept {
+        release();
+        va = o.va, bytes = o.bytes, chunk = o.chunk;
+        handles = std::move(o.handles), mapped = std::move(o.mapped), plain = o.plain;
+        o.va = nullptr;
+        return *this;
+    }
+    ~ScatteredAlloc() { release(); }
+    void adopt(void *p, size_t n) {
+        release();
+        va = p, bytes = n, plain = true;
+    }
     void release() {
         if (!va) return;
+        if (plain) {
+            (void) hipFree(va);
+            va = nullptr, plain = false;
+            return;
+        }
         for (size_t i = 0; i < handles.size(); i++) {
             if (mapped[i]) (void) hipMemUnmap((char *) va + i * chunk, chunk);
         }
@@ -329,7 +278,7 @@ struct acg_ldpc_decoder {
     // BP
     BpLayout lay;
     BpTables tab{};
-    std::vector<void *> dev_allocs;
+    std::vector<DeviceBuf> dev_allocs;  // the device copies of the tables below
     int maxd = 0, f64 = 0, L = 64;
     int block = 256, frames_per_block = 0;
     int grid_cap[2] = {0, 0};          // [mc] resident blocks: occupancy x CUs
@@ -350,33 +299,25 @@ struct acg_ldpc_decoder {
     const void *sring = nullptr;  // LDS-DMA ring variant (fp32), null = not available for this code
     int sring_per_cu = 2;
     bool sring_nt = false;  // ring instance with non-temporal slab accesses (slabs beyond the Infinity Cache)
-    uint32_t *sws = nullptr;
-    ScatteredAlloc sws_scattered;  // backing of sws when it was made of shuffled physical chunks (else sws is a hipMalloc)
+    ScatteredAlloc sws;  // the slabs: shuffled physical chunks, or one plain allocation
     std::vector<float> sws_probe_ms;  // probe time of every workspace candidate that was tried (the fastest was kept)
     int sws_spread = 1;               // the kept physical chunks are every sws_spread-th of those created
     int sgrid = 0;
     // ADMM
-    AdmmDevice *admm = nullptr;
-    // staging for the host API
-    void *st_y = nullptr;
-    uint32_t *st_bits = nullptr;
-    uint8_t *st_ok = nullptr;
-    int32_t *st_iters = nullptr;
-    int64_t st_frames = 0;
-    HostPipe *pipe = nullptr;  // pipelined staging of the host-buffer entry points (created on first use)
+    struct AdmmDrop { void operator()(AdmmDevice *a) const { admm_device_destroy(a); } };
+    std::unique_ptr<AdmmDevice, AdmmDrop> admm;
+    // staging for the host API (ensure_staging)
+    DeviceBuf st_y, st_bits, st_ok, st_iters;
+    std::unique_ptr<HostPipe> pipe;  // pipelined staging of the host-buffer entry points (created on first use)
     // MC through engines without an in-kernel generator (streamed): chunk buffers
-    float *mc_y = nullptr;
-    int64_t mc_frames = 0;
+    DeviceBuf mc_y;
     // MC
-    uint32_t *cw_dev = nullptr;
+    DeviceBuf cw_dev;
     int64_t cw_count = 0;
     uint64_t cw_hash = 0;
-    unsigned long long *counters = nullptr;
+    DeviceBuf counters;
     // parameter grid (acg_ldpc_mc_run_grid): counters[point][MC_NCOUNTERS] and the per-point tables of the chunk in flight
-    unsigned long long *grid_counters = nullptr;
-    int64_t grid_counters_rows = 0;
-    unsigned char *grid_tab = nullptr;
-    size_t grid_tab_bytes = 0;
+    DeviceBuf grid_counters, grid_tab;
     // Per-launch work counters: every launch takes the next slot of a small ring of device words (the dynamic frame /
     // tile hand-out of the kernels), so launches of one handle that overlap on different streams never share one.
     // ring_ev[k] is recorded behind the launch that used slot k; the next user of the slot — and, for the streamed
@@ -384,14 +325,39 @@ struct acg_ldpc_decoder {
     // Timing: every launch also owns the (start, stop) event pair of its slot, so two launches of one handle in flight on
     // two streams never pair each other's events; ring_ev[k] IS the stop event of slot k.
     static constexpr int WORK_RING = 32;
-    unsigned long long *work_ring = nullptr;
+    DeviceBuf work_ring;
     hipEvent_t ring_ev0[WORK_RING] = {};
     hipEvent_t ring_ev[WORK_RING] = {};
     bool ring_used[WORK_RING] = {};
     uint64_t launch_seq = 0;
     int last_slot = -1;
     hipStream_t last_stream = nullptr;
+
+    unsigned long long *counters_dev() const { return counters.as<unsigned long long>(); }
+    unsigned long long *work_counter(int slot) const { return work_ring.as<unsigned long long>() + slot; }
 };
+
+// owned until handed out: an exception or an error releases the streams, events and device memory made so far
+struct DecoderDrop { void operator()(acg_ldpc_decoder *x) const { acg_ldpc_decoder_destroy(x); } };
+using DecoderPtr = std::unique_ptr<acg_ldpc_decoder, DecoderDrop>;
+
+// one check degree and one variable degree
+static bool is_regular(const Code &c) {
+    bool regular = c.max_cdeg >= 1 && c.max_vdeg >= 1;
+    for (int i = 0; i < c.m && regular; i++) regular = (c.row_ptr[i + 1] - c.row_ptr[i] == c.max_cdeg);
+    for (int j = 0; j < c.n && regular; j++) regular = (c.col_ptr[j + 1] - c.col_ptr[j] == c.max_vdeg);
+    return regular;
+}
+
+// kernel[mc] = kp: raise its dynamic-LDS limit where the workgroup needs more than 64 KiB, and size the grid by its occupancy
+static int bind_kernel(acg_ldpc_decoder *d, int mc, const void *kp) {
+    if (d->lds_block > 64 * 1024) HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
+    int occ = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
+    d->kernel[mc] = kp;
+    d->grid_cap[mc] = std::max(occ, 1) * d->cu_count;
+    return 0;
+}
 
 extern "C" {
 
@@ -516,11 +482,8 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
     d->f64 = (d->p.precision == ACG_LDPC_PREC_F64) ? 1 : 0;
     d->L = 1;
     StreamTables &t = d->stab;
-    int32_t *p32 = nullptr;
-#define UP32S(vec, field)                                      \
-    if (upload<int32_t>(vec, &p32)) return 10;                 \
-    d->dev_allocs.push_back(p32);                              \
-    t.field = p32;
+#define UP32S(vec, field) \
+    if (!(t.field = upload_keep(vec, d->dev_allocs))) return 10;
     UP32S(c.row_ptr, row_ptr)
     UP32S(c.col_ptr, col_ptr)
     UP32S(c.col_edge, col_edge)
@@ -599,7 +562,8 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
         const char *wa = getenv("ACG_STREAM_WS_ALLOC");
         const int mode = wa ? atoi(wa) : (ws_bytes >= ((size_t) 64 << 20) ? 2 : 0);
         hipError_t e = hipErrorUnknown;
-        if (mode == 1) e = hipExtMallocWithFlags((void **) &d->sws, ws_bytes, hipDeviceMallocContiguous);
+        void *plain = nullptr;
+        if (mode == 1) e = hipExtMallocWithFlags(&plain, ws_bytes, hipDeviceMallocContiguous);
         if (mode >= 2) {
             const char *cm = getenv("ACG_STREAM_WS_CHUNK_MB");
             const size_t chunk = (size_t) (cm ? atol(cm) : 64) << 20;
@@ -636,10 +600,10 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
                     pa.max_iter = 3;
                     pa.early_exit = 0;
                     pa.ms_scale = 0.75f;
-                    pa.work_counter = d->work_ring;
+                    pa.work_counter = d->work_counter(0);
                     bool okp = true;
                     for (int rep = 0; rep < 2 && okp; rep++) {   // the second launch is the one timed
-                        okp = hipMemsetAsync(d->work_ring, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
+                        okp = hipMemsetAsync(pa.work_counter, 0, sizeof(unsigned long long), d->stream) == hipSuccess &&
                               hipEventRecord(d->ring_ev0[0], d->stream) == hipSuccess &&
                               bp_streamed_ring_launch(d->sring, d->stab, pa, (uint32_t *) cand[k].va, d->sgrid, d->stream) == hipSuccess &&
                               hipEventRecord(d->ring_ev[0], d->stream) == hipSuccess && hipStreamSynchronize(d->stream) == hipSuccess;
@@ -653,19 +617,16 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
                 }
             }
             (void) hipGetLastError();
-            for (int k = 0; k < tries; k++)
-                if (k != best) cand[k].release();
             if (best >= 0) {
-                d->sws_scattered = std::move(cand[best]);
-                cand[best].va = nullptr;
-                d->sws = (uint32_t *) d->sws_scattered.va;
+                d->sws = std::move(cand[best]);
                 e = hipSuccess;
             }
-        }
+        }   // (the other candidates are released here)
         if (e != hipSuccess) {
             (void) hipGetLastError();
-            HIP_OK(hipMalloc((void **) &d->sws, ws_bytes));
+            HIP_OK(hipMalloc(&plain, ws_bytes));
         }
+        if (plain) d->sws.adopt(plain, ws_bytes);
     }
     d->grid_cap[0] = d->grid_cap[1] = d->sgrid;
     return 0;
@@ -688,25 +649,15 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
         return 3;
     }
     LayerTables &t = d->ltab;
-    int32_t *p32 = nullptr;
-    uint16_t *p16 = nullptr;
-    if (upload<int32_t>(ll.layer, &p32)) return 10;
-    d->dev_allocs.push_back(p32);
-    t.layer = p32;
+    if (!(t.layer = upload_keep(ll.layer, d->dev_allocs))) return 10;
     if (ll.qc) {
-        if (upload<int32_t>(ll.proto, &p32)) return 10;
-        d->dev_allocs.push_back(p32);
-        t.proto = p32;
+        if (!(t.proto = upload_keep(ll.proto, d->dev_allocs))) return 10;
         t.pos = nullptr;
         std::vector<int32_t> packed(ll.proto.size() / 2 + 8, 0);   // (+8: the kernel's scalar loads may run a few words ahead)
         for (size_t k = 0; k + 1 < ll.proto.size(); k += 2) packed[k / 2] = (int32_t) (((uint32_t) (ll.proto[k] * ll.Z * 4) << 16) | (uint32_t) (ll.proto[k + 1] * 4));
-        if (upload<int32_t>(packed, &p32)) return 10;
-        d->dev_allocs.push_back(p32);
-        t.proto_packed = p32;
+        if (!(t.proto_packed = upload_keep(packed, d->dev_allocs))) return 10;
     } else {
-        if (upload<uint16_t>(ll.pos, &p16)) return 10;
-        d->dev_allocs.push_back(p16);
-        t.pos = p16;
+        if (!(t.pos = upload_keep(ll.pos, d->dev_allocs))) return 10;
         t.proto = nullptr;
     }
     t.n_layers = ll.n_layers;
@@ -756,12 +707,7 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
             set_error("no layered kernel instance for this group width");
             return 3;
         }
-        if (d->lds_block > 64 * 1024) HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
-        int occ = 0;
-        HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
-        if (occ < 1) occ = 1;
-        d->kernel[mc] = kp;
-        d->grid_cap[mc] = occ * d->cu_count;
+        if (int rc = bind_kernel(d, mc, kp)) return rc;
     }
     d->tab.lds_bytes_per_frame = t.lds_bytes_per_frame;
     return 0;
@@ -879,8 +825,6 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     per_frame = (per_frame + 15) & ~(size_t) 15;
 
     BpTables &t = d->tab;
-    int32_t *p32 = nullptr;
-    uint16_t *p16 = nullptr;
     std::vector<int32_t> c_pass(2 * (size_t) lay.n_cpass), v_pass(2 * (size_t) lay.n_vpass);
     for (int p = 0; p < lay.n_cpass; p++) {
         c_pass[2 * p] = lay.c_maxdeg[p];
@@ -893,10 +837,8 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     std::vector<int32_t> c_cnt(34, 0), v_cnt(34, 0);
     for (size_t i = 0; i < lay.c_cnt_ge.size() && i < 34; i++) c_cnt[i] = lay.c_cnt_ge[i];
     for (size_t i = 0; i < lay.v_cnt_ge.size() && i < 34; i++) v_cnt[i] = lay.v_cnt_ge[i];
-#define UP32(vec, field)                                       \
-    if (upload<int32_t>(vec, &p32)) return 10;                 \
-    d->dev_allocs.push_back(p32);                              \
-    t.field = p32;
+#define UP32(vec, field) \
+    if (!(t.field = upload_keep(vec, d->dev_allocs))) return 10;
     UP32(c_pass, c_pass)
     UP32(c_cnt, c_cnt_ge)
     UP32(v_pass, v_pass)
@@ -905,10 +847,8 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     if (lay.n_apass > 0) {
         UP32(lay.a_var, a_var)
     }
+    UP32(lay.v_apos, v_apos)
 #undef UP32
-    if (upload<uint16_t>(lay.v_apos, &p16)) return 10;
-    d->dev_allocs.push_back(p16);
-    t.v_apos = p16;
     t.v_apos_len = lay.v_apos_len;
     // the variable-side index table is read by every wave in every iteration: keep a block-shared
     // copy in LDS unless it is large (then it is read through L1/L2)
@@ -930,7 +870,6 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     if (blockmode) {
         if (per_frame + t.idx_lds_bytes > 160 * 1024) {
             if (d->p.engine == ACG_LDPC_ENGINE_AUTO && d->p.lanes_per_frame == 0) {
-                for (void *q : d->dev_allocs) (void) hipFree(q);
                 d->dev_allocs.clear();
                 return decoder_setup_streamed(d);
             }
@@ -946,21 +885,13 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
             d->lds_block = per_frame;
             t.idx_lds_bytes = 0;
             // regular code (one check degree, one variable degree): the instance with fully unrolled passes
-            bool regular = c.max_cdeg >= 1 && c.max_vdeg >= 1;
-            for (int i = 0; i < c.m && regular; i++) regular = (c.row_ptr[i + 1] - c.row_ptr[i] == c.max_cdeg);
-            for (int j = 0; j < c.n && regular; j++) regular = (c.col_ptr[j + 1] - c.col_ptr[j] == c.max_vdeg);
-            const void *kp = bp_pair_kernel_ptr(L, regular);
+            const void *kp = bp_pair_kernel_ptr(L, is_regular(c));
             if (!kp) {
                 set_error("no paired-frame kernel instance for this configuration");
                 return 3;
             }
-            if (d->lds_block > 64 * 1024)
-                HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
-            int occ = 0;
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
-            d->kernel[0] = kp;
-            d->kernel[1] = nullptr;  // Monte-Carlo runs go AWGN kernel -> decode -> classify kernel
-            d->grid_cap[0] = d->grid_cap[1] = std::max(occ, 1) * d->cu_count;
+            if (int rc = bind_kernel(d, 0, kp)) return rc;
+            d->grid_cap[1] = d->grid_cap[0];  // (kernel[1] stays null: Monte-Carlo runs go AWGN kernel -> decode -> classify kernel)
             return 0;
         }
         const int algo_b = (d->p.algo == ACG_LDPC_BP_MINSUM) ? 1 : 0;
@@ -968,9 +899,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
             // index table too large for LDS and variable degree <= 4: keep it in registers (decode kernel only)
             const bool idxreg = !idxlds && c.max_vdeg <= 4 && lay.n_vpass <= 12 && getenv("ACG_BP_NO_IDXREG") == nullptr;
             // regular code (one check degree <= 8, one variable degree <= 4): the instance without the paths for anything else
-            bool regular_b = idxreg && c.max_cdeg >= 1 && c.max_cdeg <= 8 && c.max_vdeg >= 1 && c.max_vdeg <= 4 && getenv("ACG_BP_NO_REGULAR") == nullptr;
-            for (int i = 0; i < c.m && regular_b; i++) regular_b = (c.row_ptr[i + 1] - c.row_ptr[i] == c.max_cdeg);
-            for (int j = 0; j < c.n && regular_b; j++) regular_b = (c.col_ptr[j + 1] - c.col_ptr[j] == c.max_vdeg);
+            const bool regular_b = idxreg && c.max_cdeg <= 8 && c.max_vdeg <= 4 && getenv("ACG_BP_NO_REGULAR") == nullptr && is_regular(c);
             const void *kp = bp_block_kernel_ptr(algo_b, d->f64, L, mc != 0, idxlds, idxreg, regular_b);
             if (mc == 0) {
                 d->blk_idxlds = idxlds;
@@ -980,13 +909,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
                 set_error("no workgroup-per-frame kernel instance for this configuration");
                 return 3;
             }
-            if (d->lds_block > 64 * 1024)
-                HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
-            int occ = 0;
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
-            if (occ < 1) occ = 1;
-            d->kernel[mc] = kp;
-            d->grid_cap[mc] = occ * d->cu_count;
+            if (int rc = bind_kernel(d, mc, kp)) return rc;
         }
         return 0;
     }
@@ -996,7 +919,6 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     while (waves > 1 && per_frame * fpw * waves + t.idx_lds_bytes > 160 * 1024 / 2) waves >>= 1;
     if (per_frame * fpw * waves + t.idx_lds_bytes > 160 * 1024) {
         if (d->p.engine == ACG_LDPC_ENGINE_AUTO) {
-            for (void *q : d->dev_allocs) (void) hipFree(q);
             d->dev_allocs.clear();
             return decoder_setup_streamed(d);
         }
@@ -1020,13 +942,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
             set_error("no kernel instance for this configuration");
             return 3;
         }
-        if (d->lds_block > 64 * 1024)
-            HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
-        int occ = 0;
-        HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
-        if (occ < 1) occ = 1;
-        d->kernel[mc] = kp;
-        d->grid_cap[mc] = occ * d->cu_count;
+        if (int rc = bind_kernel(d, mc, kp)) return rc;
     }
     return 0;
 }
@@ -1045,9 +961,7 @@ static int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldp
         set_error("no HIP device available: libacg_ldpc_hip has no CPU fallback");
         return 20;
     }
-    // owned until handed out: an exception or an error below releases the streams, events and device memory made so far
-    struct Drop { void operator()(acg_ldpc_decoder *x) const { acg_ldpc_decoder_destroy(x); } };
-    std::unique_ptr<acg_ldpc_decoder, Drop> own(new acg_ldpc_decoder());
+    DecoderPtr own(new acg_ldpc_decoder());
     acg_ldpc_decoder *d = own.get();
     d->c = code->c;
     d->p = *params;
@@ -1067,8 +981,8 @@ static int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldp
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess) { set_error("hipGetDeviceProperties failed"); rc = 10; break; }
         d->cu_count = prop.multiProcessorCount;
         if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); rc = 10; break; }
-        if (hipMalloc((void **) &d->counters, sizeof(unsigned long long) * MC_NCOUNTERS) != hipSuccess) { set_error("hipMalloc failed"); rc = 10; break; }
-        if (hipMalloc((void **) &d->work_ring, sizeof(unsigned long long) * acg_ldpc_decoder::WORK_RING) != hipSuccess) { set_error("hipMalloc failed"); rc = 10; break; }
+        if (d->counters.reserve(sizeof(unsigned long long) * MC_NCOUNTERS) ||
+            d->work_ring.reserve(sizeof(unsigned long long) * acg_ldpc_decoder::WORK_RING)) { set_error("hipMalloc failed"); rc = 10; break; }
         {
             bool evok = true;
             for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++)
@@ -1078,7 +992,7 @@ static int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldp
         if (params->algo == ACG_LDPC_QPADMM) {
             d->name = "QP-ADMM";  // qp_admm.h:189
             std::string err;
-            d->admm = admm_device_create(d->c, d->p, d->cu_count, err);
+            d->admm.reset(admm_device_create(d->c, d->p, d->cu_count, err));
             if (!d->admm) { set_error(err); rc = 3; break; }
         } else if (params->algo == ACG_LDPC_BP_SUMPRODUCT || params->algo == ACG_LDPC_BP_MINSUM) {
             d->name = params->algo == ACG_LDPC_BP_SUMPRODUCT ? "BP" : "MS";  // bp.h:218
@@ -1106,21 +1020,7 @@ void acg_ldpc_decoder_destroy(acg_ldpc_decoder *d) {
     // destroyed by the LRU of a host mirror while the caller's stream is still busy)
     for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++)
         if (d->ring_used[k] && d->ring_ev[k]) (void) hipEventSynchronize(d->ring_ev[k]);
-    for (void *p : d->dev_allocs) (void) hipFree(p);
-    if (d->admm) admm_device_destroy(d->admm);
-    if (d->sws_scattered.va) d->sws_scattered.release();
-    else if (d->sws) (void) hipFree(d->sws);
-    if (d->mc_y) (void) hipFree(d->mc_y);
-    if (d->st_y) (void) hipFree(d->st_y);
-    if (d->st_bits) (void) hipFree(d->st_bits);
-    if (d->st_ok) (void) hipFree(d->st_ok);
-    if (d->st_iters) (void) hipFree(d->st_iters);
-    delete d->pipe;
-    if (d->cw_dev) (void) hipFree(d->cw_dev);
-    if (d->grid_counters) (void) hipFree(d->grid_counters);
-    if (d->grid_tab) (void) hipFree(d->grid_tab);
-    if (d->counters) (void) hipFree(d->counters);
-    if (d->work_ring) (void) hipFree(d->work_ring);
+    // (the device and pinned buffers belong to the members of the handle: `delete d` below releases them)
     for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++) {
         if (d->ring_ev0[k]) (void) hipEventDestroy(d->ring_ev0[k]);
         if (d->ring_ev[k]) (void) hipEventDestroy(d->ring_ev[k]);
@@ -1134,7 +1034,7 @@ const char *acg_ldpc_decoder_name(const acg_ldpc_decoder *d) { return d->name.c_
 void acg_ldpc_decoder_layout(const acg_ldpc_decoder *d, int32_t *lds_bytes_per_frame, int32_t *lanes_per_frame,
                              int32_t *frames_per_block, int32_t *grid_blocks) {
     if (d->admm) {
-        admm_device_layout(d->admm, lds_bytes_per_frame, lanes_per_frame, frames_per_block, grid_blocks);
+        admm_device_layout(d->admm.get(), lds_bytes_per_frame, lanes_per_frame, frames_per_block, grid_blocks);
         return;
     }
     if (lds_bytes_per_frame) *lds_bytes_per_frame = d->streamed ? 0 : d->tab.lds_bytes_per_frame;
@@ -1149,22 +1049,22 @@ static std::string describe(const acg_ldpc_decoder *d) {
     const char *algo = d->p.algo == ACG_LDPC_QPADMM ? "qpadmm" : (d->p.algo == ACG_LDPC_BP_MINSUM ? "minsum" : "sum-product");
     int slabs = 0, f32 = 0;
     int64_t slab = 0;
-    if (d->admm && admm_device_streamed(d->admm, &slabs, &slab, &f32)) {
+    if (d->admm && admm_device_streamed(d->admm.get(), &slabs, &slab, &f32)) {
         snprintf(b, sizeof b, "%s engine=streamed kernel=admm_streamed_kernel<%s> f64=%d slab_bytes=%lld slabs=%d workspace_bytes=%lld "
                                "workspace=hipMalloc mc_grid=per-point",
                  algo, f32 ? "float" : "double", f32 ? 0 : 1, (long long) slab, slabs, (long long) slab * slabs);
     } else if (d->admm) {
         int lds = 0, L = 0, fpb = 0, grid = 0;
-        admm_device_layout(d->admm, &lds, &L, &fpb, &grid);
+        admm_device_layout(d->admm.get(), &lds, &L, &fpb, &grid);
         snprintf(b, sizeof b, "%s engine=lds lanes_per_frame=%d frames_per_block=%d lds_bytes_per_frame=%d grid_cap=%d mc_grid=%s", algo, L, fpb, lds, grid,
-                 admm_device_has_grid_kernel(d->admm) ? "single-launch" : "per-point");
+                 admm_device_has_grid_kernel(d->admm.get()) ? "single-launch" : "per-point");
     } else if (d->streamed) {
         const size_t slab = (size_t) d->stab.ws_words_per_wave * 4;
         snprintf(b, sizeof b, "%s engine=streamed kernel=%s%s f64=%d slab_bytes=%zu slabs=%d workspace_bytes=%zu workspace_base=%p "
                                "workgroups_per_cu=%d schedule=%s",
                  algo, d->sring ? "bp_streamed_ring_kernel" : "bp_streamed_kernel", d->sring ? (d->sring_nt ? "<NT>" : "<default-policy>") : "",
-                 d->f64, slab, d->sgrid, slab * (size_t) d->sgrid, (void *) d->sws, d->sring ? d->sring_per_cu : 2,
-                 d->sws_scattered.va ? "flooding workspace=mapped-chunks" : "flooding workspace=hipMalloc");
+                 d->f64, slab, d->sgrid, slab * (size_t) d->sgrid, d->sws.va, d->sring ? d->sring_per_cu : 2,
+                 !d->sws.plain ? "flooding workspace=mapped-chunks" : "flooding workspace=hipMalloc");
         if (!d->sws_probe_ms.empty()) {
             std::string t = b;
             t += " workspace_spread=" + std::to_string(d->sws_spread) + " workspace_probe_ms=";
@@ -1197,8 +1097,12 @@ int32_t acg_ldpc_decoder_describe(const acg_ldpc_decoder *d, char *buf, int32_t 
     return (int32_t) s.size() + 1;
 }
 
+double acg_ldpc_llr_variance(double snr) { return std::pow(10, -(snr / 10)) / 2; }  // llr_variance, channel.h:12
+
+static double channel_sigma(double snr) { return std::sqrt(acg_ldpc_llr_variance(snr)); }  // channel.h:20
+
 static void fill_channel(DecodeArgs &a, double snr) {
-    const double var = std::pow(10, -(snr / 10)) / 2;  // llr_variance, channel.h:12
+    const double var = acg_ldpc_llr_variance(snr);
     a.var = var;
     a.inv_var2 = 2.0 / var;
     a.sigma = (float) std::sqrt(var);
@@ -1215,9 +1119,9 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
     const int slot = (int) (d->launch_seq++ % acg_ldpc_decoder::WORK_RING);
     if (d->ring_used[slot]) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[slot], 0));
     // engines whose HBM workspace belongs to the handle (streamed BP, streamed QP-ADMM): a launch on another stream waits
-    const bool owns_ws = d->streamed || (d->admm && admm_device_streamed(d->admm, nullptr, nullptr, nullptr));
+    const bool owns_ws = d->streamed || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
     if (owns_ws && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
-    a.work_counter = d->work_ring + slot;
+    a.work_counter = d->work_counter(slot);
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
 #ifdef ACG_BLOCK_STAMPS
     static unsigned long long *stamp_buf = nullptr;  // developer build only (tools/ab_variant.sh ... -DACG_BLOCK_STAMPS)
@@ -1228,7 +1132,7 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
     HIP_OK(hipEventRecord(d->ring_ev0[slot], s));
     if (d->admm) {
         std::string err;
-        hipError_t e = admm_launch(d->admm, a, s, err);
+        hipError_t e = admm_launch(d->admm.get(), a, s, err);
         if (e != hipSuccess) {
             set_error(err.empty() ? std::string("admm launch: ") + hipGetErrorString(e) : err);
             return 10;
@@ -1252,9 +1156,9 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
                 HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS_BYTES));
             }
             grid = (int) std::min<int64_t>(tiles, (int64_t) d->sring_per_cu * d->cu_count);
-            HIP_OK(bp_streamed_ring_launch(kp, d->stab, a, d->sws, grid, s));
+            HIP_OK(bp_streamed_ring_launch(kp, d->stab, a, (uint32_t *) d->sws.va, grid, s));
         } else {
-            HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, d->sws, grid, W * 64, s));
+            HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, (uint32_t *) d->sws.va, grid, W * 64, s));
         }
     } else if (d->layered) {
         const int mc = a.mc ? 1 : 0;
@@ -1316,24 +1220,20 @@ int acg_ldpc_decode_batch_dev(acg_ldpc_decoder *d, const void *y_dev, int32_t y_
     return guarded([&] { return acg_ldpc_decode_batch_dev_impl(d, y_dev, y_is_f64, frames, snr, bits_dev, ok_dev, iters_dev, stream); });
 }
 
+// outputs of `frames` frames, and room for their symbols as doubles
 static int ensure_staging(acg_ldpc_decoder *d, int64_t frames) {
-    if (frames <= d->st_frames) return 0;
-    if (d->st_y) (void) hipFree(d->st_y);
-    if (d->st_bits) (void) hipFree(d->st_bits);
-    if (d->st_ok) (void) hipFree(d->st_ok);
-    if (d->st_iters) (void) hipFree(d->st_iters);
-    d->st_y = nullptr;
-    d->st_bits = nullptr;
-    d->st_ok = nullptr;
-    d->st_iters = nullptr;
-    d->st_frames = 0;
-    const int nwords = (d->c.n + 31) / 32;
-    HIP_OK(hipMalloc(&d->st_y, (size_t) frames * d->c.n * sizeof(double)));
-    HIP_OK(hipMalloc((void **) &d->st_bits, (size_t) frames * nwords * sizeof(uint32_t)));
-    HIP_OK(hipMalloc((void **) &d->st_ok, (size_t) frames));
-    HIP_OK(hipMalloc((void **) &d->st_iters, (size_t) frames * sizeof(int32_t)));
-    d->st_frames = frames;
-    return 0;
+    const size_t f = (size_t) frames, nwords = (size_t) (d->c.n + 31) / 32;
+    if (int rc = d->st_y.reserve(f * d->c.n * sizeof(double))) return rc;
+    if (int rc = d->st_bits.reserve(f * nwords * sizeof(uint32_t))) return rc;
+    if (int rc = d->st_ok.reserve(f)) return rc;
+    return d->st_iters.reserve(f * sizeof(int32_t));
+}
+
+// the decode outputs of a launch into the staging buffers
+static void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a) {
+    a.out_bits = d->st_bits.as<uint32_t>();
+    a.out_ok = d->st_ok.as<uint8_t>();
+    a.out_iters = d->st_iters.as<int32_t>();
 }
 
 static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes) {
@@ -1344,7 +1244,7 @@ static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes) {
             HIP_OK(hipStreamCreateWithFlags(&np->stream[b], hipStreamNonBlocking));
             HIP_OK(hipEventCreateWithFlags(&np->done[b], hipEventDisableTiming));
         }
-        d->pipe = np.release();
+        d->pipe = std::move(np);
     }
     HostPipe &P = *d->pipe;
     // keep the buffers while they fit and are not grossly oversized for what is asked now (a 1M-frame batch followed by
@@ -1354,10 +1254,10 @@ static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes) {
     P.release();
     const int nwords = (d->c.n + 31) / 32;
     for (int b = 0; b < HostPipe::NBUF; b++) {
-        HIP_OK(hipHostMalloc(&P.pin_y[b], (size_t) chunk * y_bytes, hipHostMallocDefault));
-        HIP_OK(hipHostMalloc((void **) &P.pin_out[b], (size_t) chunk * (nwords * 4 + 5), hipHostMallocDefault));
-        HIP_OK(hipMalloc(&P.dev_y[b], (size_t) chunk * y_bytes));
-        HIP_OK(hipMalloc((void **) &P.dev_out[b], (size_t) chunk * (nwords * 4 + 5)));
+        if (int rc = P.pin_y[b].reserve((size_t) chunk * y_bytes)) return rc;
+        if (int rc = P.pin_out[b].reserve((size_t) chunk * (nwords * 4 + 5))) return rc;
+        if (int rc = P.dev_y[b].reserve((size_t) chunk * y_bytes)) return rc;
+        if (int rc = P.dev_out[b].reserve((size_t) chunk * (nwords * 4 + 5))) return rc;
     }
     P.chunk = chunk;
     P.y_bytes = y_bytes;
@@ -1412,7 +1312,7 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         const int b = (int) (c % HostPipe::NBUF);
         const int64_t fc = chunk_frames(c);
         const unsigned char *src = reinterpret_cast<const unsigned char *>(y) + (size_t) c * chunk * y_bytes;
-        unsigned char *dst = reinterpret_cast<unsigned char *>(P.pin_y[b]);
+        unsigned char *dst = P.pin_y[b].as<unsigned char>();
         const size_t total = (size_t) fc * y_bytes;
         if (!threads) {
             std::memcpy(dst, src, total);
@@ -1427,17 +1327,18 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         const int b = (int) (c % HostPipe::NBUF);
         const int64_t fc = chunk_frames(c);
         hipStream_t s = P.stream[b];
-        HIP_OK(hipMemcpyAsync(P.dev_y[b], P.pin_y[b], (size_t) fc * y_bytes, hipMemcpyHostToDevice, s));
+        unsigned char *dev_out = P.dev_out[b].as<unsigned char>();
+        HIP_OK(hipMemcpyAsync(P.dev_y[b].p, P.pin_y[b].p, (size_t) fc * y_bytes, hipMemcpyHostToDevice, s));
         DecodeArgs a{};
-        a.y = P.dev_y[b];
+        a.y = P.dev_y[b].p;
         a.y_is_f64 = (elem == 8) ? 1 : 0;
         a.frames = fc;
         fill_channel(a, snr);
-        a.out_bits = reinterpret_cast<uint32_t *>(P.dev_out[b]);
-        a.out_iters = reinterpret_cast<int32_t *>(P.dev_out[b] + (size_t) fc * nwords * 4);
-        a.out_ok = P.dev_out[b] + (size_t) fc * (nwords * 4 + 4);
+        a.out_bits = reinterpret_cast<uint32_t *>(dev_out);
+        a.out_iters = reinterpret_cast<int32_t *>(dev_out + (size_t) fc * nwords * 4);
+        a.out_ok = dev_out + (size_t) fc * (nwords * 4 + 4);
         if (int rc = launch_decode(d, a, s)) return rc;
-        HIP_OK(hipMemcpyAsync(P.pin_out[b], P.dev_out[b], (size_t) fc * (nwords * 4 + 5), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, (size_t) fc * (nwords * 4 + 5), hipMemcpyDeviceToHost, s));
         HIP_OK(hipEventRecord(P.done[b], s));
         return 0;
     };
@@ -1445,9 +1346,10 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         const int b = (int) (c % HostPipe::NBUF);
         const int64_t fc = chunk_frames(c), f0 = c * chunk;
         HIP_OK(hipEventSynchronize(P.done[b]));
-        const uint32_t *pbits = reinterpret_cast<const uint32_t *>(P.pin_out[b]);
-        std::memcpy(ok + f0, P.pin_out[b] + (size_t) fc * (nwords * 4 + 4), (size_t) fc);
-        if (iters) std::memcpy(iters + f0, P.pin_out[b] + (size_t) fc * nwords * 4, (size_t) fc * 4);
+        const unsigned char *out = P.pin_out[b].as<unsigned char>();
+        const uint32_t *pbits = reinterpret_cast<const uint32_t *>(out);
+        std::memcpy(ok + f0, out + (size_t) fc * (nwords * 4 + 4), (size_t) fc);
+        if (iters) std::memcpy(iters + f0, out + (size_t) fc * nwords * 4, (size_t) fc * 4);
         if (!threads) {
             unpack_bits(pbits, nwords, n, fc, bits + (size_t) f0 * n);
             return 0;
@@ -1473,8 +1375,9 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
     return collect(nchunks - 1);
 }
 
-static int acg_ldpc_decode_batch_impl(acg_ldpc_decoder *d, const double *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
-                          int32_t *iters) {
+// elem = 8: double symbols (acg_ldpc_decode_batch), 4: float symbols (acg_ldpc_decode_batch_f32)
+static int decode_batch_impl(acg_ldpc_decoder *d, const void *y, int elem, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
+                             int32_t *iters) {
     if (!d) {
         set_error("null decoder");
         return 1;
@@ -1486,33 +1389,17 @@ static int acg_ldpc_decode_batch_impl(acg_ldpc_decoder *d, const double *y, int6
     if (frames == 0) return 0;
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
-    return decode_batch_host(d, y, 8, frames, snr, bits, ok, iters);
+    return decode_batch_host(d, y, elem, frames, snr, bits, ok, iters);
 }
 
 int acg_ldpc_decode_batch(acg_ldpc_decoder *d, const double *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
                           int32_t *iters) {
-    return guarded([&] { return acg_ldpc_decode_batch_impl(d, y, frames, snr, bits, ok, iters); });
-}
-
-static int acg_ldpc_decode_batch_f32_impl(acg_ldpc_decoder *d, const float *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
-                              int32_t *iters) {
-    if (!d) {
-        set_error("null decoder");
-        return 1;
-    }
-    if (frames < 0 || (frames > 0 && (!y || !bits || !ok))) {
-        set_error("null buffer");
-        return 1;
-    }
-    if (frames == 0) return 0;
-    std::lock_guard<std::recursive_mutex> lk(d->mu);
-    HIP_OK(hipSetDevice(d->device));
-    return decode_batch_host(d, y, 4, frames, snr, bits, ok, iters);
+    return guarded([&] { return decode_batch_impl(d, y, 8, frames, snr, bits, ok, iters); });
 }
 
 int acg_ldpc_decode_batch_f32(acg_ldpc_decoder *d, const float *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
                               int32_t *iters) {
-    return guarded([&] { return acg_ldpc_decode_batch_f32_impl(d, y, frames, snr, bits, ok, iters); });
+    return guarded([&] { return decode_batch_impl(d, y, 4, frames, snr, bits, ok, iters); });
 }
 
 int acg_ldpc_decoder_sync(acg_ldpc_decoder *d) {
@@ -1564,19 +1451,52 @@ static int ensure_codewords(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg) {
         for (; i < nb; i++) hl[0] = (hl[0] ^ (uint64_t) (pb[i] != 0)) * 1099511628211ull;
         h = ((hl[0] * 31 + hl[1]) * 31 + hl[2]) * 31 + hl[3];
     }
-    if (d->cw_dev && d->cw_hash == h && d->cw_count == cfg->n_codewords) return 0;
-    if (d->cw_dev) (void) hipFree(d->cw_dev);
-    d->cw_dev = nullptr;
+    if (d->cw_dev.p && d->cw_hash == h && d->cw_count == cfg->n_codewords) return 0;
+    d->cw_dev.reset();  // (hipFree waits for the device: no launch still reads the old words when the new ones are copied)
     const int n = d->c.n, nwords = (n + 31) / 32;
     std::vector<uint32_t> packed((size_t) cfg->n_codewords * nwords, 0u);
     for (int64_t f = 0; f < cfg->n_codewords; f++)
         for (int v = 0; v < n; v++)
             if (cfg->codewords[(size_t) f * n + v]) packed[(size_t) f * nwords + (v >> 5)] |= 1u << (v & 31);
-    HIP_OK(hipMalloc((void **) &d->cw_dev, packed.size() * sizeof(uint32_t)));
-    HIP_OK(hipMemcpy(d->cw_dev, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = d->cw_dev.reserve(packed.size() * sizeof(uint32_t))) return rc;
+    HIP_OK(hipMemcpy(d->cw_dev.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     d->cw_hash = h;
     d->cw_count = cfg->n_codewords;
     return 0;
+}
+
+// the sent words as the kernels take them: (packed device copy, count), or (null, 1) for the all-zero word
+struct SentWords {
+    const uint32_t *dev;
+    int64_t n;
+};
+static SentWords sent_words(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg) {
+    if (!cfg->codewords) return {nullptr, 1};
+    return {d->cw_dev.as<uint32_t>(), cfg->n_codewords};
+}
+
+static void counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *r) {
+    r->correct = (int64_t) c[MC_CORRECT];
+    r->pseudo = (int64_t) c[MC_PSEUDO];
+    r->total = (int64_t) c[MC_TOTAL];
+    r->sum_hamming = (int64_t) c[MC_HAM];
+    r->sum_hamming_ok = (int64_t) c[MC_HAM_OK];
+    r->sum_hamming_wrong = (int64_t) c[MC_HAM_WRONG];
+    r->sum_iters = (int64_t) c[MC_ITERS];
+}
+
+// Bit-exact experiment.h:90-99 (single-threaded order): frame g (0-based global index) is seeded mt19937(g+1) and
+// transmitted with libstdc++ normal_distribution (channel.h:18-26); codewords == null sends the all-zero word
+static void transmit_host(const uint8_t *codewords, int64_t n_codewords, int n, int64_t first_frame, int64_t frames, double snr,
+                          double *y) {
+    const double sigma = channel_sigma(snr);
+    for (int64_t f = 0; f < frames; f++) {
+        const int64_t gidx = first_frame + f;
+        const uint8_t *cw = codewords ? codewords + (size_t) (gidx % n_codewords) * n : nullptr;
+        std::mt19937 rnd((uint32_t) (gidx + 1));
+        std::normal_distribution<double> dst(0, sigma);
+        for (int i = 0; i < n; i++) y[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + dst(rnd);
+    }
 }
 
 void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
@@ -1593,28 +1513,19 @@ void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
 }
 
 static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
-    // Bit-exact experiment.h:80-123 (single-threaded order): frame g (0-based global index) is
-    // seeded mt19937(g+1) (:90-97), transmitted with libstdc++ normal_distribution (channel.h:18-26),
-    // decoded on the device, classified on the host.
+    // Bit-exact experiment.h:80-123: transmit_host, decoded on the device, classified on the host.
     const int n = d->c.n;
     const int64_t chunk_max = 1 << 16;
     std::vector<double> y;
     std::vector<uint8_t> bits, ok;
     std::vector<int32_t> iters;
-    const double sigma = std::sqrt(std::pow(10, -(cfg->snr / 10)) / 2);
     for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk_max) {
         const int64_t fc = std::min(chunk_max, cfg->frames - f0);
         y.resize((size_t) fc * n);
         bits.resize((size_t) fc * n);
         ok.resize((size_t) fc);
         iters.resize((size_t) fc);
-        for (int64_t f = 0; f < fc; f++) {
-            const int64_t gidx = cfg->first_frame + f0 + f;
-            const uint8_t *cw = cfg->codewords ? cfg->codewords + (size_t) (gidx % cfg->n_codewords) * n : nullptr;
-            std::mt19937 rnd((uint32_t) (gidx + 1));
-            std::normal_distribution<double> dst(0, sigma);
-            for (int i = 0; i < n; i++) y[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + dst(rnd);
-        }
+        transmit_host(cfg->codewords, cfg->n_codewords, n, cfg->first_frame + f0, fc, cfg->snr, y.data());
         if (int rc = acg_ldpc_decode_batch(d, y.data(), fc, cfg->snr, bits.data(), ok.data(), iters.data())) return rc;
         res->kernel_ms += acg_ldpc_decoder_last_kernel_ms(d);
         for (int64_t f = 0; f < fc; f++) {
@@ -1662,84 +1573,64 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
     int rc = 0;
     if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
         rc = mc_run_host_noise(d, cfg, res);
-    } else if (d->streamed || d->pair || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm, nullptr, nullptr))) {
+    } else if (d->streamed || d->pair || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
         // AWGN kernel -> decode -> classify kernel, in bounded chunks, all on the device.  Used by the streamed BP
         // engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
         // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
-        if (d->admm) (void) admm_device_unfused_mc(d->admm, &csr_row, &csr_col);
+        if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
         std::lock_guard<std::recursive_mutex> lk(d->mu);
         HIP_OK(hipSetDevice(d->device));
         if ((rc = ensure_codewords(d, cfg))) return rc;
         const int n = d->c.n, nwords = (n + 31) / 32;
         int64_t chunk = std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4)));
-        if (chunk > d->mc_frames) {
-            if (d->mc_y) (void) hipFree(d->mc_y);
-            d->mc_y = nullptr;
-            HIP_OK(hipMalloc((void **) &d->mc_y, (size_t) chunk * n * sizeof(float)));
-            d->mc_frames = chunk;
-        }
-        if (int rc2 = ensure_staging(d, std::min<int64_t>(chunk, std::max<int64_t>(cfg->frames, 1)))) return rc2;
-        HIP_OK(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
-        const double var = std::pow(10, -(cfg->snr / 10)) / 2;
+        if ((rc = d->mc_y.reserve((size_t) chunk * n * sizeof(float)))) return rc;
+        if ((rc = ensure_staging(d, std::min<int64_t>(chunk, std::max<int64_t>(cfg->frames, 1))))) return rc;
+        HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+        const SentWords cw = sent_words(d, cfg);
+        float *mc_y = d->mc_y.as<float>();
         float kms = 0;
         for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
             const int64_t fc = std::min(chunk, cfg->frames - f0);
-            HIP_OK(awgn_launch(d->mc_y, fc, n, nwords, cfg->first_frame + f0, cfg->seed, cfg->codewords ? d->cw_dev : nullptr,
-                               cfg->codewords ? cfg->n_codewords : 1, (float) std::sqrt(var), d->stream));
+            HIP_OK(awgn_launch(mc_y, fc, n, nwords, cfg->first_frame + f0, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
             DecodeArgs a{};
-            a.y = d->mc_y;
+            a.y = mc_y;
             a.y_is_f64 = 0;
             a.frames = fc;
             fill_channel(a, cfg->snr);
-            a.out_bits = d->st_bits;
-            a.out_ok = d->st_ok;
-            a.out_iters = d->st_iters;
+            stage_outputs(d, a);
             if ((rc = launch_decode(d, a, d->stream))) return rc;
             const int slot = d->last_slot;   // this launch's own event pair (d->mu is held)
-            HIP_OK(classify_launch(d->mc_y, d->st_bits, d->st_ok, d->st_iters, fc, n, nwords, cfg->first_frame + f0,
-                                   cfg->codewords ? d->cw_dev : nullptr, cfg->codewords ? cfg->n_codewords : 1,
-                                   d->counters, csr_row, csr_col, d->c.m, d->stream));
+            HIP_OK(classify_launch(mc_y, a.out_bits, a.out_ok, a.out_iters, fc, n, nwords, cfg->first_frame + f0, cw.dev, cw.n,
+                                   d->counters_dev(), csr_row, csr_col, d->c.m, d->stream));
             HIP_OK(hipStreamSynchronize(d->stream));
             float ms = 0;
             if (hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess) kms += ms;
         }
         unsigned long long h[MC_NCOUNTERS];
-        HIP_OK(hipMemcpy(h, d->counters, sizeof(h), hipMemcpyDeviceToHost));
-        res->correct = (int64_t) h[MC_CORRECT];
-        res->pseudo = (int64_t) h[MC_PSEUDO];
-        res->total = (int64_t) h[MC_TOTAL];
-        res->sum_hamming = (int64_t) h[MC_HAM];
-        res->sum_hamming_ok = (int64_t) h[MC_HAM_OK];
-        res->sum_hamming_wrong = (int64_t) h[MC_HAM_WRONG];
-        res->sum_iters = (int64_t) h[MC_ITERS];
+        HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
+        counters_to_result(h, res);
         res->kernel_ms = kms;
     } else {
         std::lock_guard<std::recursive_mutex> lk(d->mu);
         HIP_OK(hipSetDevice(d->device));
         if ((rc = ensure_codewords(d, cfg))) return rc;
-        HIP_OK(hipMemsetAsync(d->counters, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+        HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
         DecodeArgs a{};
         a.frames = cfg->frames;
         fill_channel(a, cfg->snr);
         a.mc = 1;
         a.seed = cfg->seed;
         a.first_frame = cfg->first_frame;
-        a.cw_packed = cfg->codewords ? d->cw_dev : nullptr;
-        a.n_cw = cfg->codewords ? cfg->n_codewords : 1;
-        a.counters = d->counters;
+        a.cw_packed = sent_words(d, cfg).dev;
+        a.n_cw = sent_words(d, cfg).n;
+        a.counters = d->counters_dev();
         if ((rc = launch_decode(d, a, d->stream))) return rc;
         const int slot = d->last_slot;   // this launch's own event pair (d->mu is held)
         unsigned long long h[MC_NCOUNTERS];
-        HIP_OK(hipMemcpyAsync(h, d->counters, sizeof(h), hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipMemcpyAsync(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipStreamSynchronize(d->stream));
-        res->correct = (int64_t) h[MC_CORRECT];
-        res->pseudo = (int64_t) h[MC_PSEUDO];
-        res->total = (int64_t) h[MC_TOTAL];
-        res->sum_hamming = (int64_t) h[MC_HAM];
-        res->sum_hamming_ok = (int64_t) h[MC_HAM_OK];
-        res->sum_hamming_wrong = (int64_t) h[MC_HAM_WRONG];
-        res->sum_iters = (int64_t) h[MC_ITERS];
+        counters_to_result(h, res);
         float ms = 0;
         if (cfg->frames > 0 && slot >= 0 && hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess) res->kernel_ms = ms;
     }
@@ -1764,21 +1655,13 @@ static int64_t mc_grid_budget() {
 // mc_run_host_noise) or floats from the device generator (as the unfused path of acg_ldpc_mc_run).  Caller holds d->mu.
 static int mc_grid_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, std::vector<double> &yh) {
     const int n = d->c.n, nwords = (n + 31) / 32;
-    const double var = std::pow(10, -(cfg->snr / 10)) / 2;
     if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
-        const double sigma = std::sqrt(var);
         yh.resize((size_t) fc * n);
-        for (int64_t f = 0; f < fc; f++) {
-            const int64_t gidx = first + f;
-            const uint8_t *cw = cfg->codewords ? cfg->codewords + (size_t) (gidx % cfg->n_codewords) * n : nullptr;
-            std::mt19937 rnd((uint32_t) (gidx + 1));
-            std::normal_distribution<double> dst(0, sigma);
-            for (int i = 0; i < n; i++) yh[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + dst(rnd);
-        }
-        HIP_OK(hipMemcpyAsync(d->st_y, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
+        transmit_host(cfg->codewords, cfg->n_codewords, n, first, fc, cfg->snr, yh.data());
+        HIP_OK(hipMemcpyAsync(d->st_y.p, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
     } else {
-        HIP_OK(awgn_launch((float *) d->st_y, fc, n, nwords, first, cfg->seed, cfg->codewords ? d->cw_dev : nullptr,
-                           cfg->codewords ? cfg->n_codewords : 1, (float) std::sqrt(var), d->stream));
+        const SentWords cw = sent_words(d, cfg);
+        HIP_OK(awgn_launch(d->st_y.as<float>(), fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
     }
     return 0;
 }
@@ -1809,22 +1692,21 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
     std::memset(res, 0, sizeof(*res) * (size_t) n_points);
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
-    const double e_min = admm_device_e_min(d->admm);
+    const double e_min = admm_device_e_min(d->admm.get());
     std::vector<int32_t> run;  // the points that decode; the others are guard points (qp_admm.h:108-114)
     for (int32_t k = 0; k < n_points; k++)
         if (!(e_min * mu[k] <= alpha[k])) run.push_back(k);
     const int64_t n_run = (int64_t) run.size();
     const bool any_guard = n_run < n_points;
-    const bool single_launch = admm_device_has_grid_kernel(d->admm);
+    const bool single_launch = admm_device_has_grid_kernel(d->admm.get());
     int rc = 0;
     if (cfg->frames > 0 && (any_guard || (single_launch && n_run > 0))) {
         if ((rc = ensure_codewords(d, cfg))) return rc;
         const int n = d->c.n, nwords = (n + 31) / 32;
         const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
-        (void) admm_device_unfused_mc(d->admm, &csr_row, &csr_col);
-        const uint32_t *cw_dev = cfg->codewords ? d->cw_dev : nullptr;
-        const int64_t n_cw = cfg->codewords ? cfg->n_codewords : 1;
+        (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
+        const SentWords cw = sent_words(d, cfg);
         // frames in blocks of fb, points in chunks of npc: one launch covers npc * fb <= budget virtual frames (or one
         // point's fb frames); its outputs use the handle's staging buffers
         const int64_t budget = mc_grid_budget();
@@ -1832,22 +1714,18 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
         const int64_t npc = single_launch ? std::max<int64_t>(1, std::min<int64_t>(budget / fb, std::max<int64_t>(n_run, 1))) : 1;
         if ((rc = ensure_staging(d, npc * fb))) return rc;
         // counters: row j < n_run = point run[j], row n_run = every guard point
-        if (n_run + 1 > d->grid_counters_rows) {
-            if (d->grid_counters) (void) hipFree(d->grid_counters);
-            d->grid_counters = nullptr;
-            d->grid_counters_rows = 0;
-            HIP_OK(hipMalloc((void **) &d->grid_counters, (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long)));
-            d->grid_counters_rows = n_run + 1;
-        }
-        HIP_OK(hipMemsetAsync(d->grid_counters, 0, (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long), d->stream));
+        const size_t counter_bytes = (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long);
+        if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
+        unsigned long long *counters = d->grid_counters.as<unsigned long long>();
+        HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
         std::vector<double> yh, ca, cm;
         std::vector<unsigned char> pt, inv;
         for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
             const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
             if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
             if (any_guard)
-                HIP_OK(classify_grid_launch(d->st_y, host, nullptr, nullptr, nullptr, fc, 1, n, nwords, first, cw_dev, n_cw,
-                                            d->grid_counters + (size_t) n_run * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+                HIP_OK(classify_grid_launch(d->st_y.p, host, nullptr, nullptr, nullptr, fc, 1, n, nwords, first, cw.dev, cw.n,
+                                            counters + (size_t) n_run * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
             for (int64_t c0 = 0; single_launch && c0 < n_run; c0 += npc) {
                 const int64_t np = std::min(npc, n_run - c0);
                 ca.resize((size_t) np);
@@ -1856,33 +1734,26 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
                     ca[(size_t) j] = alpha[run[(size_t) (c0 + j)]];
                     cm[(size_t) j] = mu[run[(size_t) (c0 + j)]];
                 }
-                admm_grid_tables(d->admm, ca.data(), cm.data(), (int) np, pt, inv);
+                admm_grid_tables(d->admm.get(), ca.data(), cm.data(), (int) np, pt, inv);
                 const size_t pt_bytes = (pt.size() + 255) & ~(size_t) 255;
-                if (pt_bytes + inv.size() > d->grid_tab_bytes) {
-                    if (d->grid_tab) (void) hipFree(d->grid_tab);
-                    d->grid_tab = nullptr;
-                    d->grid_tab_bytes = 0;
-                    HIP_OK(hipMalloc((void **) &d->grid_tab, pt_bytes + inv.size()));
-                    d->grid_tab_bytes = pt_bytes + inv.size();
-                }
+                if ((rc = d->grid_tab.reserve(pt_bytes + inv.size()))) return rc;
+                unsigned char *tab = d->grid_tab.as<unsigned char>();
                 // (the stream is idle here: the previous chunk ended with a synchronisation, so pt / inv may be rewritten)
-                HIP_OK(hipMemcpyAsync(d->grid_tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
-                HIP_OK(hipMemcpyAsync(d->grid_tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(hipMemcpyAsync(tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(hipMemcpyAsync(tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
                 DecodeArgs a{};
-                a.y = d->st_y;
+                a.y = d->st_y.p;
                 a.y_is_f64 = host;
                 a.frames = np * fc;
                 fill_channel(a, cfg->snr);
-                a.out_bits = d->st_bits;
-                a.out_ok = d->st_ok;
-                a.out_iters = d->st_iters;
-                admm_grid_bind(d->admm, d->grid_tab, d->grid_tab + pt_bytes, (uint32_t) fc);
+                stage_outputs(d, a);
+                admm_grid_bind(d->admm.get(), tab, tab + pt_bytes, (uint32_t) fc);
                 rc = launch_decode(d, a, d->stream);
-                admm_grid_bind(d->admm, nullptr, nullptr, 0);
+                admm_grid_bind(d->admm.get(), nullptr, nullptr, 0);
                 if (rc) return rc;
                 const int slot = d->last_slot;
-                HIP_OK(classify_grid_launch(d->st_y, host, d->st_bits, d->st_ok, d->st_iters, fc, np, n, nwords, first, cw_dev, n_cw,
-                                            d->grid_counters + (size_t) c0 * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+                HIP_OK(classify_grid_launch(d->st_y.p, host, a.out_bits, a.out_ok, a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
+                                            counters + (size_t) c0 * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
                 HIP_OK(hipStreamSynchronize(d->stream));
                 float ms = 0;
                 if (hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess)
@@ -1891,23 +1762,14 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
             HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
         }
         std::vector<unsigned long long> h((size_t) (n_run + 1) * MC_NCOUNTERS);
-        HIP_OK(hipMemcpy(h.data(), d->grid_counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        auto fill = [&](acg_ldpc_mc_result &r, const unsigned long long *c) {
-            r.correct = (int64_t) c[MC_CORRECT];
-            r.pseudo = (int64_t) c[MC_PSEUDO];
-            r.total = (int64_t) c[MC_TOTAL];
-            r.sum_hamming = (int64_t) c[MC_HAM];
-            r.sum_hamming_ok = (int64_t) c[MC_HAM_OK];
-            r.sum_hamming_wrong = (int64_t) c[MC_HAM_WRONG];
-            r.sum_iters = (int64_t) c[MC_ITERS];
-        };
+        HIP_OK(hipMemcpy(h.data(), counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         std::vector<char> is_run((size_t) n_points, 0);
         for (int64_t j = 0; j < n_run; j++) {
             is_run[(size_t) run[(size_t) j]] = 1;
-            if (single_launch) fill(res[run[(size_t) j]], &h[(size_t) j * MC_NCOUNTERS]);
+            if (single_launch) counters_to_result(&h[(size_t) j * MC_NCOUNTERS], &res[run[(size_t) j]]);
         }
         for (int32_t k = 0; k < n_points; k++)
-            if (!is_run[(size_t) k]) fill(res[k], &h[(size_t) n_run * MC_NCOUNTERS]);
+            if (!is_run[(size_t) k]) counters_to_result(&h[(size_t) n_run * MC_NCOUNTERS], &res[k]);
     }
     if (!single_launch && n_run > 0) {
         // one point after another on this handle: acg_ldpc_mc_run with the handle re-parameterised in place
@@ -1916,7 +1778,7 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
         std::string err;
         for (int64_t j = 0; j < n_run && !rc; j++) {
             const int32_t k = run[(size_t) j];
-            if (!admm_device_set_point(d->admm, alpha[k], mu[k], err)) {
+            if (!admm_device_set_point(d->admm.get(), alpha[k], mu[k], err)) {
                 set_error(err);
                 rc = 10;
                 break;
@@ -1924,7 +1786,7 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
             rc = acg_ldpc_mc_run_impl(d, cfg, &res[k]);  // (synchronises the stream before it returns)
         }
         const std::string first_err = rc ? g_err : std::string();
-        if (!admm_device_set_point(d->admm, alpha0, mu0, err) && !rc) {
+        if (!admm_device_set_point(d->admm.get(), alpha0, mu0, err) && !rc) {
             set_error(err);
             rc = 10;
         } else if (rc) {
@@ -1949,10 +1811,9 @@ static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cf
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     if (int rc = ensure_codewords(d, cfg)) return rc;
-    const double var = std::pow(10, -(cfg->snr / 10)) / 2;
-    HIP_OK(awgn_launch(y_dev, cfg->frames, d->c.n, (d->c.n + 31) / 32, cfg->first_frame, cfg->seed,
-                       cfg->codewords ? d->cw_dev : nullptr, cfg->codewords ? cfg->n_codewords : 1,
-                       (float) std::sqrt(var), stream ? (hipStream_t) stream : d->stream));
+    const SentWords cw = sent_words(d, cfg);
+    HIP_OK(awgn_launch(y_dev, cfg->frames, d->c.n, (d->c.n + 31) / 32, cfg->first_frame, cfg->seed, cw.dev, cw.n,
+                       (float) channel_sigma(cfg->snr), stream ? (hipStream_t) stream : d->stream));
     return 0;
 }
 
@@ -1983,22 +1844,13 @@ int acg_ldpc_gen_codewords(const uint8_t *G, int32_t k, int32_t n, uint32_t seed
     return guarded([&] { return acg_ldpc_gen_codewords_impl(G, k, n, seed, count, out); });
 }
 
-double acg_ldpc_llr_variance(double snr) { return std::pow(10, -(snr / 10)) / 2; }
-
 static int acg_ldpc_transmit_host_impl(const uint8_t *codewords, int64_t n_codewords, int32_t n, int64_t first_frame,
                            int64_t frames, double snr, double *y) {
     if (!y || n <= 0 || frames < 0 || (codewords && n_codewords <= 0)) {
         set_error("bad argument");
         return 1;
     }
-    const double sigma = std::sqrt(acg_ldpc_llr_variance(snr));  // channel.h:20
-    for (int64_t f = 0; f < frames; f++) {
-        const int64_t gidx = first_frame + f;
-        const uint8_t *cw = codewords ? codewords + (size_t) (gidx % n_codewords) * n : nullptr;
-        std::mt19937 rnd((uint32_t) (gidx + 1));              // experiment.h:90-97, single-threaded order
-        std::normal_distribution<double> dst(0, sigma);       // channel.h:22
-        for (int i = 0; i < n; i++) y[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + dst(rnd);
-    }
+    transmit_host(codewords, n_codewords, n, first_frame, frames, snr, y);
     return 0;
 }
 
@@ -2024,8 +1876,10 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
     p.engine = fused ? ACG_LDPC_ENGINE_FUSED : ACG_LDPC_ENGINE_STREAMED;
     p.lanes_per_frame = fused ? lanes_per_frame : 0;
     p.precision = f64 ? ACG_LDPC_PREC_F64 : ACG_LDPC_PREC_DEFAULT;
-    acg_ldpc_decoder *d = nullptr;
-    if (int rc = acg_ldpc_decoder_create(code, &p, &d)) return rc;
+    acg_ldpc_decoder *made = nullptr;
+    if (int rc = acg_ldpc_decoder_create(code, &p, &made)) return rc;
+    const DecoderPtr own(made);  // destroyed on every return, after the three dumps below
+    acg_ldpc_decoder *d = made;
     const int n = d->c.n, E = d->c.E;
     const size_t ts = f64 ? 8 : 4;
     // words per frame of the three dumps: streamed [E][64] / [E][64] / [n][64]; fused [frame][a_words] x2 / [frame][n_vpass*L]
@@ -2036,7 +1890,6 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
         else if (d->variant == -1 && d->L == 256 && d->blk_idxlds && !d->blk_idxreg) kp = bp_block_kernel_ptr_dbg(f64);
         if (!kp) {
             set_error("no debug instance of the fused kernel for this code / lanes_per_frame");
-            acg_ldpc_decoder_destroy(d);
             return 3;
         }
         if (d->lds_block > 64 * 1024) (void) hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block);
@@ -2045,97 +1898,93 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
         wc = (size_t) frames * (d->tab.a_words + d->lay.n_apass * d->L);
         wp = (size_t) frames * (d->lay.n_vpass + d->lay.n_apass) * d->L;
     }
-    void *dc = nullptr, *dv = nullptr, *dp = nullptr;
-    int rc = 0;
-    do {
-        if (hipMalloc(&dc, wc * ts) != hipSuccess || hipMalloc(&dv, wc * ts) != hipSuccess ||
-            hipMalloc(&dp, wp * ts) != hipSuccess) { set_error("hipMalloc failed"); rc = 10; break; }
-        if ((rc = ensure_staging(d, frames))) break;
-        if (hipMemcpy(d->st_y, y, (size_t) frames * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { rc = 10; break; }
-        DecodeArgs a{};
-        a.y = d->st_y;
-        a.y_is_f64 = 1;
-        a.frames = frames;
-        fill_channel(a, snr);
-        a.out_bits = d->st_bits;
-        a.out_ok = d->st_ok;
-        a.out_iters = d->st_iters;
-        a.dbg_c2v = dc;
-        a.dbg_v2c = dv;
-        a.dbg_post = dp;
-        if ((rc = launch_decode(d, a, d->stream))) break;
-        if (hipStreamSynchronize(d->stream) != hipSuccess) { set_error("sync failed"); rc = 10; break; }
-        std::vector<unsigned char> hc(wc * ts), hv(wc * ts), hp(wp * ts);
-        (void) hipMemcpy(hc.data(), dc, hc.size(), hipMemcpyDeviceToHost);
-        (void) hipMemcpy(hv.data(), dv, hv.size(), hipMemcpyDeviceToHost);
-        (void) hipMemcpy(hp.data(), dp, hp.size(), hipMemcpyDeviceToHost);
-        // the fp32 kernels work in the log2(e)-scaled message domain (bp_core.inc: Dom<float>): undo it here
-        const double unscale = f64 ? 1.0 : 0.693147180559945309;
-        auto get = [&](const std::vector<unsigned char> &b, size_t idx) -> double {
-            if (f64) return reinterpret_cast<const double *>(b.data())[idx];
-            return unscale * (double) reinterpret_cast<const float *>(b.data())[idx];
-        };
-        // a v->c word = magnitude | hard-decision bit in the LSB | sign: strip the LSB before reading it
-        auto get_v2c = [&](size_t idx) -> double {
-            if (f64) {
-                uint64_t u = reinterpret_cast<const uint64_t *>(hv.data())[idx] & ~1ull;
-                double w;
-                std::memcpy(&w, &u, 8);
-                return w;
-            }
-            uint32_t u = reinterpret_cast<const uint32_t *>(hv.data())[idx] & ~1u;
-            float wf;
-            std::memcpy(&wf, &u, 4);
-            return unscale * (double) wf;
-        };
-        // where edge e (check-major, variables ascending — the oracle's trace order) and variable v live in the dumps
-        std::vector<size_t> epos((size_t) E), vslot((size_t) n, (size_t) -1);
-        if (fused) {
-            const BpLayout &lay = d->lay;
-            for (int sl = 0; sl < lay.n_cpass * lay.L; sl++) {
-                const int chk = lay.c_chk[sl];
-                if (chk < 0) continue;
-                const int pss = sl / lay.L, l = sl % lay.L;
-                const int q = pss - (lay.n_cpass - lay.n_apass);  // >= 0: absorbed pass, its last edge is the register word
-                const int deg = d->c.row_ptr[chk + 1] - d->c.row_ptr[chk];
-                for (int j = 0; j < deg; j++)
-                    epos[(size_t) d->c.row_ptr[chk] + j] = (q >= 0 && j == deg - 1)
-                                                               ? (size_t) d->tab.a_words + (size_t) q * lay.L + l
-                                                               : (size_t) lay.c_off[pss] + (size_t) j * lay.L + l;
-            }
-            for (int sl = 0; sl < lay.n_vpass * lay.L; sl++)
-                if (lay.v_var[sl] >= 0) vslot[lay.v_var[sl]] = (size_t) sl;
-            for (int sl = 0; sl < lay.n_apass * lay.L; sl++)
-                if (lay.a_var[sl] >= 0) vslot[lay.a_var[sl]] = (size_t) lay.n_vpass * lay.L + sl;
+    DeviceBuf dc, dv, dp;
+    if (dc.reserve(wc * ts) || dv.reserve(wc * ts) || dp.reserve(wp * ts)) {
+        set_error("hipMalloc failed");
+        return 10;
+    }
+    if (int rc = ensure_staging(d, frames)) return rc;
+    if (hipMemcpy(d->st_y.p, y, (size_t) frames * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 10;
+    DecodeArgs a{};
+    a.y = d->st_y.p;
+    a.y_is_f64 = 1;
+    a.frames = frames;
+    fill_channel(a, snr);
+    stage_outputs(d, a);
+    a.dbg_c2v = dc.p;
+    a.dbg_v2c = dv.p;
+    a.dbg_post = dp.p;
+    if (int rc = launch_decode(d, a, d->stream)) return rc;
+    if (hipStreamSynchronize(d->stream) != hipSuccess) {
+        set_error("sync failed");
+        return 10;
+    }
+    std::vector<unsigned char> hc(wc * ts), hv(wc * ts), hp(wp * ts);
+    (void) hipMemcpy(hc.data(), dc.p, hc.size(), hipMemcpyDeviceToHost);
+    (void) hipMemcpy(hv.data(), dv.p, hv.size(), hipMemcpyDeviceToHost);
+    (void) hipMemcpy(hp.data(), dp.p, hp.size(), hipMemcpyDeviceToHost);
+    // the fp32 kernels work in the log2(e)-scaled message domain (bp_core.inc: Dom<float>): undo it here
+    const double unscale = f64 ? 1.0 : 0.693147180559945309;
+    auto get = [&](const std::vector<unsigned char> &b, size_t idx) -> double {
+        if (f64) return reinterpret_cast<const double *>(b.data())[idx];
+        return unscale * (double) reinterpret_cast<const float *>(b.data())[idx];
+    };
+    // a v->c word = magnitude | hard-decision bit in the LSB | sign: strip the LSB before reading it
+    auto get_v2c = [&](size_t idx) -> double {
+        if (f64) {
+            uint64_t u = reinterpret_cast<const uint64_t *>(hv.data())[idx] & ~1ull;
+            double w;
+            std::memcpy(&w, &u, 8);
+            return w;
         }
-        const size_t cstride = (size_t) d->tab.a_words + (size_t) d->lay.n_apass * d->L;
-        const size_t pstride = (size_t) (d->lay.n_vpass + d->lay.n_apass) * d->L;
-        for (int f = 0; f < frames; f++) {
-            auto eidx = [&](int e) { return fused ? (size_t) f * cstride + epos[e] : (size_t) e * 64 + f; };
-            for (int e = 0; e < E; e++) {
-                c2v[(size_t) f * E + e] = get(hc, eidx(e));
-                const double w = get_v2c(eidx(e));
-                v2c_mag[(size_t) f * E + e] = std::fabs(w);
-                v2c_sgn[(size_t) f * E + e] = std::signbit(w) ? -1.0 : 1.0;
-            }
-            for (int v = 0; v < n; v++) {
-                if (!fused) {
-                    post[(size_t) f * n + v] = get(hp, (size_t) v * 64 + f);
-                    continue;
-                }
-                // estimate() = llr + sum of the c->v mailbox (bp.h:85-90), summed here from the kernel's own c->v words
-                // and channel LLR (slot order dump), checks ascending
-                double sum = 0;
-                for (int k = d->c.col_ptr[v]; k < d->c.col_ptr[v + 1]; k++) sum += c2v[(size_t) f * E + d->c.col_edge[k]];
-                post[(size_t) f * n + v] = get(hp, (size_t) f * pstride + vslot[v]) + sum;
-            }
+        uint32_t u = reinterpret_cast<const uint32_t *>(hv.data())[idx] & ~1u;
+        float wf;
+        std::memcpy(&wf, &u, 4);
+        return unscale * (double) wf;
+    };
+    // where edge e (check-major, variables ascending — the oracle's trace order) and variable v live in the dumps
+    std::vector<size_t> epos((size_t) E), vslot((size_t) n, (size_t) -1);
+    if (fused) {
+        const BpLayout &lay = d->lay;
+        for (int sl = 0; sl < lay.n_cpass * lay.L; sl++) {
+            const int chk = lay.c_chk[sl];
+            if (chk < 0) continue;
+            const int pss = sl / lay.L, l = sl % lay.L;
+            const int q = pss - (lay.n_cpass - lay.n_apass);  // >= 0: absorbed pass, its last edge is the register word
+            const int deg = d->c.row_ptr[chk + 1] - d->c.row_ptr[chk];
+            for (int j = 0; j < deg; j++)
+                epos[(size_t) d->c.row_ptr[chk] + j] = (q >= 0 && j == deg - 1)
+                                                           ? (size_t) d->tab.a_words + (size_t) q * lay.L + l
+                                                           : (size_t) lay.c_off[pss] + (size_t) j * lay.L + l;
         }
-    } while (0);
-    if (dc) (void) hipFree(dc);
-    if (dv) (void) hipFree(dv);
-    if (dp) (void) hipFree(dp);
-    acg_ldpc_decoder_destroy(d);
-    return rc;
+        for (int sl = 0; sl < lay.n_vpass * lay.L; sl++)
+            if (lay.v_var[sl] >= 0) vslot[lay.v_var[sl]] = (size_t) sl;
+        for (int sl = 0; sl < lay.n_apass * lay.L; sl++)
+            if (lay.a_var[sl] >= 0) vslot[lay.a_var[sl]] = (size_t) lay.n_vpass * lay.L + sl;
+    }
+    const size_t cstride = (size_t) d->tab.a_words + (size_t) d->lay.n_apass * d->L;
+    const size_t pstride = (size_t) (d->lay.n_vpass + d->lay.n_apass) * d->L;
+    for (int f = 0; f < frames; f++) {
+        auto eidx = [&](int e) { return fused ? (size_t) f * cstride + epos[e] : (size_t) e * 64 + f; };
+        for (int e = 0; e < E; e++) {
+            c2v[(size_t) f * E + e] = get(hc, eidx(e));
+            const double w = get_v2c(eidx(e));
+            v2c_mag[(size_t) f * E + e] = std::fabs(w);
+            v2c_sgn[(size_t) f * E + e] = std::signbit(w) ? -1.0 : 1.0;
+        }
+        for (int v = 0; v < n; v++) {
+            if (!fused) {
+                post[(size_t) f * n + v] = get(hp, (size_t) v * 64 + f);
+                continue;
+            }
+            // estimate() = llr + sum of the c->v mailbox (bp.h:85-90), summed here from the kernel's own c->v words
+            // and channel LLR (slot order dump), checks ascending
+            double sum = 0;
+            for (int k = d->c.col_ptr[v]; k < d->c.col_ptr[v + 1]; k++) sum += c2v[(size_t) f * E + d->c.col_edge[k]];
+            post[(size_t) f * n + v] = get(hp, (size_t) f * pstride + vslot[v]) + sum;
+        }
+    }
+    return 0;
 }
 
 int acg_ldpc_debug_bp_trace(const acg_ldpc_code *code, const double *y, int32_t frames, double snr, int32_t iters,
@@ -2188,15 +2037,13 @@ int acg_ldpc_debug_layers(const acg_ldpc_code *code, int32_t *lanes, int32_t *n_
 
 static int acg_ldpc_debug_phi_impl(const void *x_host, void *out_host, int32_t n, int32_t f64) {
     const size_t es = f64 ? 8 : 4;
-    void *dx = nullptr, *dout = nullptr;
-    HIP_OK(hipMalloc(&dx, es * n));
-    HIP_OK(hipMalloc(&dout, es * n));
-    HIP_OK(hipMemcpy(dx, x_host, es * n, hipMemcpyHostToDevice));
-    HIP_OK(phi_debug_launch(dx, dout, n, f64, nullptr));
+    DeviceBuf dx, dout;
+    if (int rc = dx.reserve(es * n)) return rc;
+    if (int rc = dout.reserve(es * n)) return rc;
+    HIP_OK(hipMemcpy(dx.p, x_host, es * n, hipMemcpyHostToDevice));
+    HIP_OK(phi_debug_launch(dx.p, dout.p, n, f64, nullptr));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out_host, dout, es * n, hipMemcpyDeviceToHost));
-    (void) hipFree(dx);
-    (void) hipFree(dout);
+    HIP_OK(hipMemcpy(out_host, dout.p, es * n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2205,16 +2052,13 @@ int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f6
 }
 
 static int acg_ldpc_debug_phi_sat_impl(const void *x_host, void *out_host, int32_t n) {
-    float *dx = nullptr;
-    uint32_t *dout = nullptr;
-    HIP_OK(hipMalloc(&dx, 4 * (size_t) n));
-    HIP_OK(hipMalloc(&dout, 12 * (size_t) n));
-    HIP_OK(hipMemcpy(dx, x_host, 4 * (size_t) n, hipMemcpyHostToDevice));
-    HIP_OK(phi_sat_debug_launch(dx, dout, n, nullptr));
+    DeviceBuf dx, dout;
+    if (int rc = dx.reserve(4 * (size_t) n)) return rc;
+    if (int rc = dout.reserve(12 * (size_t) n)) return rc;
+    HIP_OK(hipMemcpy(dx.p, x_host, 4 * (size_t) n, hipMemcpyHostToDevice));
+    HIP_OK(phi_sat_debug_launch(dx.as<float>(), dout.as<uint32_t>(), n, nullptr));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(out_host, dout, 12 * (size_t) n, hipMemcpyDeviceToHost));
-    (void) hipFree(dx);
-    (void) hipFree(dout);
+    HIP_OK(hipMemcpy(out_host, dout.p, 12 * (size_t) n, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -4,7 +4,7 @@
 // workgroup, all state in LDS for the whole decode, sweeps separated by __syncthreads(), frames handed out dynamically.
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"

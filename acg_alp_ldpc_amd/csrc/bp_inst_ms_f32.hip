@@ -1,7 +1,7 @@
 // Instantiations of the fused BP kernel for T = float, ALGO = 1 (min-sum, fp32).
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"

@@ -28,18 +28,11 @@
 
 #include <algorithm>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"
 
-const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat);
-const void *bp_kernel_ptr_spa_f64(int maxd, int L, bool mc, int variant);
-const void *bp_kernel_ptr_ms_f32(int maxd, int L, bool mc, int variant);
-const void *bp_kernel_ptr_ms_f64(int maxd, int L, bool mc, int variant);
-
-const void *bp_kernel_ptr_spa_f32_dbg(int L);
-const void *bp_kernel_ptr_spa_f64_dbg(int L);
 const void *bp_kernel_ptr_dbg(int f64, int L) {
 #ifdef ACG_FAST_BUILD
     return f64 ? nullptr : bp_kernel_ptr_spa_f32_dbg(L);

@@ -29,7 +29,7 @@
 
 #include <algorithm>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"   // Dom<float>::phi (the fp32 phi of the flooding kernels, log2(e)-scaled domain) for the sum-product variant

@@ -14,7 +14,7 @@
 // hard decision = (posterior <= 0), output latched at the first zero syndrome, bp.h:183-199.
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"

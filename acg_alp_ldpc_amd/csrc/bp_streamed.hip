@@ -13,7 +13,7 @@
 // is the real bound, and rocprofv3's FETCH_SIZE/WRITE_SIZE can be read against it.
 #include <hip/hip_runtime.h>
 
-#include "kernels.hpp"
+#include "launchers.hpp"
 
 namespace acg {
 #include "bp_core.inc"

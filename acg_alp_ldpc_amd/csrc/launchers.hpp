@@ -1,0 +1,83 @@
+// Every function that one .hip file defines and another calls, declared once.  Both the caller and the defining file
+// include this header, so a definition that drifts from its declaration does not compile.  Not part of the ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/acg_ldpc.h"
+#include "kernels.hpp"
+
+namespace acg {
+
+struct Code;  // ldpc_internal.hpp
+
+// ---- bp_inst_{spa,ms}_{f32,f64}.hip: the instances of bp_fused_kernel (bp_core.inc) ----
+const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat);
+const void *bp_kernel_ptr_spa_f64(int maxd, int L, bool mc, int variant);
+const void *bp_kernel_ptr_ms_f32(int maxd, int L, bool mc, int variant);
+const void *bp_kernel_ptr_ms_f64(int maxd, int L, bool mc, int variant);
+const void *bp_kernel_ptr_spa_f32_dbg(int L);
+const void *bp_kernel_ptr_spa_f64_dbg(int L);
+
+// ---- bp_kernels.hip ----
+const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat);
+const void *bp_kernel_ptr_dbg(int f64, int L);
+hipError_t bp_launch(const void *kernel, const BpTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
+                     hipStream_t s);
+hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s);
+hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s);
+hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,
+                       const uint32_t *cw_packed, int64_t n_cw, float sigma, hipStream_t s);
+hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
+                           int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
+                           unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                           hipStream_t s);
+hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                int64_t frames, int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
+                                int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                hipStream_t s);
+
+// ---- bp_block.hip, bp_pair.hip, bp_layered.hip ----
+const void *bp_block_kernel_ptr(int algo, int f64, int L, bool mc, bool idxlds, bool idxreg, bool regular);
+const void *bp_block_kernel_ptr_dbg(int f64);
+const void *bp_pair_kernel_ptr(int L, bool regular);
+const void *bp_layered_kernel_ptr(int G, int waves, bool qc_arith, bool f16, int algo, bool mc);
+hipError_t bp_layered_launch(const void *kernel, const LayerTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s);
+
+// ---- bp_streamed.hip ----
+const void *bp_streamed_ptr(int algo, int f64);
+const void *bp_streamed_ring_ptr(int algo, bool nt);
+const void *bp_streamed_ring_ptr_dbg();
+hipError_t bp_streamed_ring_launch(const void *kernel, const StreamTables &t, const DecodeArgs &a, uint32_t *ws, int grid, hipStream_t s);
+hipError_t bp_streamed_launch(const void *kernel, const StreamTables &t, const DecodeArgs &a, uint32_t *ws, int grid,
+                              int block, hipStream_t s);
+
+// ---- admm_kernels.hip (AdmmDevice stays opaque to its callers) ----
+struct AdmmDevice;
+AdmmDevice *admm_device_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
+void admm_device_destroy(AdmmDevice *d);
+hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::string &err);
+void admm_device_layout(const AdmmDevice *d, int *lds_per_frame, int *lanes, int *frames_per_block, int *grid);
+bool admm_device_unfused_mc(const AdmmDevice *d, const int32_t **row_ptr, const int32_t **edge_var);
+bool admm_device_streamed(const AdmmDevice *d, int *slabs, int64_t *slab_bytes, int *f32);
+// parameter grid (acg_ldpc_mc_run_grid)
+double admm_device_e_min(const AdmmDevice *d);
+bool admm_device_has_grid_kernel(const AdmmDevice *d);
+void admm_grid_tables(const AdmmDevice *d, const double *alpha, const double *mu, int np, std::vector<unsigned char> &pt,
+                      std::vector<unsigned char> &inv);
+void admm_grid_bind(AdmmDevice *d, const void *pt_dev, const void *inv_dev, uint32_t frames_per_point);
+bool admm_device_set_point(AdmmDevice *d, double alpha, double mu, std::string &err);
+
+// ---- admm_streamed.hip (called by admm_kernels.hip) ----
+struct AdmmStream;
+AdmmStream *admm_stream_create(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err);
+void admm_stream_destroy(AdmmStream *s);
+void admm_stream_info(const AdmmStream *s, int *slabs, int64_t *slab_bytes, int *f32);
+bool admm_stream_set_point(AdmmStream *s, double alpha, double mu);
+hipError_t admm_stream_launch(AdmmStream *s, const DecodeArgs &a, hipStream_t st);
+
+}  // namespace acg
