@@ -10,8 +10,8 @@ from .channel import gen_random_codewords, llr, llr_variance, transmit_frames  #
 from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
 from .decoder import BeliefPropagationDecoder, Decoder, MinSumDecoder, QPADMMDecoder  # noqa: F401
-from .experiment import (ExperimentResult, merge_exp_results, run_experiment, run_experiment_grid,  # noqa: F401
-                         run_experiment_inproc, run_experiment_sharded, shard_range)
+from .experiment import (CodesEvaluator, ExperimentResult, merge_exp_results, run_experiment, run_experiment_codes,  # noqa: F401
+                         run_experiment_grid, run_experiment_inproc, run_experiment_sharded, shard_range)
 
 
 def read_pcm(path):

@@ -71,6 +71,10 @@ SYMBOLS = {
     "acg_ldpc_mc_run": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McResult)]),
     "acg_ldpc_mc_merge": (None, [C.POINTER(McResult), C.POINTER(McResult)]),
     "acg_ldpc_mc_run_grid": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _vp, _i32, _vp]),
+    "acg_ldpc_evaluator_create": (C.c_int, [C.POINTER(Params), C.POINTER(_vp)]),
+    "acg_ldpc_evaluator_destroy": (None, [_vp]),
+    "acg_ldpc_mc_run_codes": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "acg_ldpc_evaluator_describe": (_i32, [_vp, C.c_char_p, _i32]),
     "acg_ldpc_gen_codewords": (C.c_int, [_vp, _i32, _i32, C.c_uint32, _i64, _vp]),
     "acg_ldpc_transmit_host": (C.c_int, [_vp, _i64, _i32, _i64, _i64, _f64, _vp]),
     "acg_ldpc_llr_variance": (_f64, [_f64]),

@@ -25,8 +25,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device_mem.hpp"
@@ -127,6 +129,9 @@ struct AdmmDevice {
     const void *kernel_grid[2] = {nullptr, nullptr};  // grid instances of admm_block_kernel; null = points run one after another
     const void *grid_pt = nullptr, *grid_inv = nullptr;  // bound tables: the next admm_launch is a grid launch
     uint32_t grid_fpp = 0;
+    // batch of codes (acg_ldpc_mc_run_codes): a plan made by admm_codes_plan — t holds blob offsets, nothing is on the device
+    int passes = 0;  // workgroup-per-frame kernel: the BP instance
+    const void *kernel_codes[2] = {nullptr, nullptr};  // codes instances of admm_block_kernel
 };
 
 // NGP = 0: row state w in LDS (any code size).  NGP > 0 (requires n_gpass <= NGP): every lane keeps the w of its own
@@ -690,22 +695,47 @@ struct AdmmGridArgs {
 };
 __device__ __forceinline__ const AdmmGridArgs &admm_grid_args(const AdmmGridArgs &g) { return g; }
 
+// Batch of parity-check matrices (acg_ldpc_mc_run_codes): one launch decodes `frames_per_code` frames for each of several
+// codes of one n.  Virtual frame g of the launch belongs to code g / frames_per_code; the channel symbols are laid out
+// [code][frame][n], so it reads its symbols and writes its outputs at index g.  alpha, mu and eps are the launch's; what
+// differs per code is the whole structure: tabs[code] is the AdmmDevTables admm_device_create_lds builds for that code.
+struct AdmmCodesArgs {
+    const AdmmDevTables *tabs;  // device array, one per code of the launch
+    uint32_t frames_per_code;
+};
+__device__ __forceinline__ const AdmmCodesArgs &admm_codes_args(const AdmmCodesArgs &c) { return c; }
+
+// tabs[code] -> t through uniform loads: every word goes through readfirstlane, so the tables stay scalar values
+__device__ __forceinline__ void admm_load_tables(AdmmDevTables &t, const AdmmDevTables *src) {
+    static_assert(sizeof(AdmmDevTables) % 4 == 0, "copied word by word");
+    constexpr int W = (int) (sizeof(AdmmDevTables) / 4);
+    const uint32_t *s = reinterpret_cast<const uint32_t *>(src);
+    uint32_t w[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) w[i] = (uint32_t) __builtin_amdgcn_readfirstlane((int) s[i]);
+    __builtin_memcpy(&t, w, sizeof(AdmmDevTables));
+}
+
 // BP = passes (of blockDim.x constraint groups / variables) the register-resident structure is sized for; fewer passes
 // = fewer registers = more wavefronts per SIMD (launch bound: 4, 5, 6 workgroups of 4 wavefronts per CU for BP = 4, 3, 2).
 // LEAN: the instance for problems that need none of the general paths inside the sweep — no one-/two-variable checks, every
 // list within the register-resident entries of its pass, V cell = thread slot (all true for the quasi-cyclic tuple placement
 // of H05 / optimalH).  The wavefronts of this kernel are bound by how many instructions they have to get through per sweep,
 // scalar tests and branches included, so the paths are compiled out, not branched around.
-// GRID: empty (the decode kernel: its parameter list and code are exactly those of the kernel without this pack) or one
-// AdmmGridArgs (the parameter-grid instance: alpha_in / mu_in are ignored, every point brings its own).
+// GRID: empty (the decode kernel: its parameter list and code are exactly those of the kernel without this pack), one
+// AdmmGridArgs (the parameter-grid instance: alpha_in / mu_in are ignored, every point brings its own) or one AdmmCodesArgs
+// (the batch-of-codes instance: t_in is ignored, every code brings its own tables).
 template <typename T, bool EE, int BP, bool LEAN, typename... GRID>
-__global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? ADMM_OCC_F32 : 0)) admm_block_kernel(const AdmmDevTables t, const DecodeArgs a, const T alpha_in,
+__global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? ADMM_OCC_F32 : 0)) admm_block_kernel(const AdmmDevTables t_in, const DecodeArgs a, const T alpha_in,
                                                               const T mu_in, const T eps_stop, const GRID... grid) {
     using X = AdmmVec<T>;
-    constexpr bool IS_GRID = sizeof...(GRID) != 0;
-    static_assert(sizeof...(GRID) <= 1, "GRID is empty or one AdmmGridArgs");
+    static_assert(sizeof...(GRID) <= 1, "GRID is empty, one AdmmGridArgs or one AdmmCodesArgs");
+    constexpr bool IS_CODES = (std::is_same<GRID, AdmmCodesArgs>::value || ...);
+    constexpr bool IS_GRID = sizeof...(GRID) != 0 && !IS_CODES;
+    // the tables: the kernel argument itself, or (codes) a copy that is reloaded whenever the workgroup changes code
+    typename std::conditional<IS_CODES, AdmmDevTables, const AdmmDevTables &>::type t = t_in;
     T alpha = alpha_in, mu = mu_in;
-    uint32_t cur_point = 0xFFFFFFFFu;  // (grid) point whose alpha, mu, inv[] are loaded
+    uint32_t cur_point = 0xFFFFFFFFu;  // (grid) point whose alpha, mu, inv[] are loaded; (codes) code whose structure is loaded
     extern __shared__ __attribute__((aligned(32))) unsigned char smem[];
     const int L = blockDim.x;  // 128, 192 or 256 threads = one frame
     __builtin_amdgcn_s_setreg((0 << 11) | (8 << 6) | 1, 0);  // hwreg(HW_REG_MODE, offset 8, width 1) = DX10_CLAMP := 0: the clamp modifier passes NaN (see the v-update)
@@ -715,62 +745,95 @@ __global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? AD
     const int wave = __builtin_amdgcn_readfirstlane(l >> 6);
     // LDS: V[V_pad] by variable id (+ zero cell at n_var) | U[G_pad][4] | packed hard decisions
     T *V = reinterpret_cast<T *>(smem);
-    const uint32_t u_base = (uint32_t) t.V_pad * (uint32_t) sizeof(T);
-    uint32_t *OB = reinterpret_cast<uint32_t *>(smem + u_base + (size_t) 4 * t.U_slots * sizeof(T));
+    uint32_t u_base;
+    uint32_t *OB;
     // ---- loop-invariant per-thread structure -> registers ------------------------------------------------------------
     uint32_t mem[BP][3];  // member k of my group in pass p: LDS byte address of V[member] | address of U[group][wpos k] << 16
-    uint32_t tys = 0;          // group type of pass p at bits 2p..2p+1 (0 = padding slot)
-#pragma unroll
-    for (int p = 0; p < BP; ++p) {
-        mem[p][0] = mem[p][1] = mem[p][2] = 0;
-        if (p < t.n_gpass) {
-            const int gs = p * L + l;
-            tys |= (uint32_t) t.grp_type_slot[gs] << (2 * p);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) mem[p][k] = t.blk_mem[(size_t) k * t.G_pad + gs];
-        }
-    }
+    uint32_t tys;              // group type of pass p at bits 2p..2p+1 (0 = padding slot)
     uint32_t ent[BP][ADMM_VK];  // list entries: ABSOLUTE LDS byte address of U[group][0] | "coefficient is -1" flags, row r at bit 31-r
     const uint32_t smem_abs = (uint32_t) (uintptr_t) smem;  // start of the dynamic LDS (behind the static words)
-    uint32_t mlw_pk = 0;             // list length of (pass p, my wavefront) at bits 8p..8p+7
-    uint32_t gen_pk = 0;             // bit p: (pass p, my wavefront) holds one- or two-variable checks
+    uint32_t mlw_pk;                 // list length of (pass p, my wavefront) at bits 8p..8p+7
+    uint32_t gen_pk;                 // bit p: (pass p, my wavefront) holds one- or two-variable checks
     // LDS byte address of my variable in pass p: its thread slot when the placement says so (cell_is_slot), otherwise read
     // from the table once per sweep (ahead of the list, so the list hides the load); bit 8+p of tys = "I own a variable"
-    const bool cell_slot = LEAN || t.cell_is_slot != 0;
+    bool cell_slot;
     T inv[BP];
-    const T *inv_coef = reinterpret_cast<const T *>(t.inv_coef);
-#pragma unroll
-    for (int p = 0; p < BP; ++p) {
-        inv[p] = (T) 0;
-#pragma unroll
-        for (int k = 0; k < ADMM_VK; ++k)
-            if (k < admm_vk(p)) ent[p][k] = 0;
-        if (p < t.n_gpass) gen_pk |= (uint32_t) (t.blk_generic[p * 4 + wave] != 0) << p;
-        if (p < t.n_vpass) {
-            const int ml = t.blk_mlw[p * 4 + wave];
-            mlw_pk |= (uint32_t) ml << (8 * p);
-            const int cell = t.blk_cell[p * L + l];
-            tys |= (cell >= 0 ? 1u : 0u) << (8 + p);
-            inv[p] = inv_coef[p * L + l];
-#pragma unroll
-            for (int k = 0; k < ADMM_VK; ++k)
-                if (k < admm_vk(p) && k < ml) ent[p][k] = t.blk_list[(size_t) t.v_list_off[p] + (size_t) k * L + l] + smem_abs;  // (no carry into the flags: host check)
-        }
-    }
-    mlw_pk = (uint32_t) __builtin_amdgcn_readfirstlane((int) mlw_pk);
-    gen_pk = (uint32_t) __builtin_amdgcn_readfirstlane((int) gen_pk);
-    T ylreg[BP][4], qreg[BP];
     // U is tiled 32 slots x 4 rows: my slot in pass p has row 3 at u3_0 + p * u3_step, row r 32 words before per row
-    const uint32_t u3_0 = u_base + (uint32_t) ((l >> 5) * 128 + 96 + (l & 31)) * (uint32_t) sizeof(T);
-    const uint32_t u3_step = (uint32_t) L * 4u * (uint32_t) sizeof(T);
+    uint32_t u3_0, u3_step;
+    // everything above from the tables in t: once per kernel, or (codes) once per change of code.  One text for both, and a
+    // macro rather than a function or a lambda: the decode and grid instances must compile to the code they had before the
+    // codes instance existed, and a closure over these registers changes their allocation
+#define ADMM_LOAD_STRUCTURE()                                                                                                       \
+    do {                                                                                                                           \
+        u_base = (uint32_t) t.V_pad * (uint32_t) sizeof(T); \
+        OB = reinterpret_cast<uint32_t *>(smem + u_base + (size_t) 4 * t.U_slots * sizeof(T)); \
+        tys = 0; \
+        _Pragma("unroll")          \
+        for (int p = 0; p < BP; ++p) { \
+            mem[p][0] = mem[p][1] = mem[p][2] = 0; \
+            if (p < t.n_gpass) { \
+                const int gs = p * L + l; \
+                tys |= (uint32_t) t.grp_type_slot[gs] << (2 * p); \
+        _Pragma("unroll")          \
+                for (int k = 0; k < 3; ++k) mem[p][k] = t.blk_mem[(size_t) k * t.G_pad + gs]; \
+            } \
+        } \
+        mlw_pk = 0; \
+        gen_pk = 0; \
+        cell_slot = LEAN || t.cell_is_slot != 0; \
+        const T *inv_coef = reinterpret_cast<const T *>(t.inv_coef); \
+        _Pragma("unroll")          \
+        for (int p = 0; p < BP; ++p) { \
+            inv[p] = (T) 0; \
+        _Pragma("unroll")          \
+            for (int k = 0; k < ADMM_VK; ++k) \
+                if (k < admm_vk(p)) ent[p][k] = 0; \
+            if (p < t.n_gpass) gen_pk |= (uint32_t) (t.blk_generic[p * 4 + wave] != 0) << p; \
+            if (p < t.n_vpass) { \
+                const int ml = t.blk_mlw[p * 4 + wave]; \
+                mlw_pk |= (uint32_t) ml << (8 * p); \
+                const int cell = t.blk_cell[p * L + l]; \
+                tys |= (cell >= 0 ? 1u : 0u) << (8 + p); \
+                inv[p] = inv_coef[p * L + l]; \
+        _Pragma("unroll")          \
+                for (int k = 0; k < ADMM_VK; ++k) \
+                    if (k < admm_vk(p) && k < ml) ent[p][k] = t.blk_list[(size_t) t.v_list_off[p] + (size_t) k * L + l] + smem_abs; \
+            } \
+        } \
+        mlw_pk = (uint32_t) __builtin_amdgcn_readfirstlane((int) mlw_pk); \
+        gen_pk = (uint32_t) __builtin_amdgcn_readfirstlane((int) gen_pk); \
+        u3_0 = u_base + (uint32_t) ((l >> 5) * 128 + 96 + (l & 31)) * (uint32_t) sizeof(T); \
+        u3_step = (uint32_t) L * 4u * (uint32_t) sizeof(T); \
+    } while (0)
+    if constexpr (!IS_CODES) ADMM_LOAD_STRUCTURE();
+    T ylreg[BP][4], qreg[BP];
 
     for (;;) {
         __syncthreads();
         if (l == 0) fr_lds = atomicAdd(a.work_counter, 1ull);  // dynamic frame hand-out
         __syncthreads();
-        const int64_t frame = (int64_t) fr_lds;  // index of the outputs
+        int64_t frame = (int64_t) fr_lds;  // index of the outputs
+        if constexpr (IS_CODES) {
+            // one value for the whole workgroup, told to the compiler: with a uniform loop exit the reloaded tables and the
+            // packed list lengths stay scalar values across the frame loop
+            const uint32_t flo = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) frame);
+            const uint32_t fhi = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) ((unsigned long long) frame >> 32));
+            frame = (int64_t) (((unsigned long long) fhi << 32) | flo);
+        }
         if (frame >= a.frames) break;
         int64_t yframe = frame;                   // index of the channel symbols
+        if constexpr (IS_CODES) {
+            // (below 2^31 virtual frames, consecutive hand-outs and a rare change, as for the grid below.  The two barriers of
+            // the hand-out stand between the last LDS access of the previous frame and this reload, which moves the LDS
+            // offsets derived from V_pad / U_slots; the new code is the same in every thread of the workgroup)
+            const AdmmCodesArgs &cd = admm_codes_args(grid...);
+            const uint32_t code = (uint32_t) __builtin_amdgcn_readfirstlane((int) ((uint32_t) frame / cd.frames_per_code));
+            if (code != cur_point) {
+                cur_point = code;
+                admm_load_tables(t, cd.tabs + code);
+                ADMM_LOAD_STRUCTURE();
+            }
+        }
         if constexpr (IS_GRID) {
             // (the host keeps a grid launch below 2^31 virtual frames; hand-outs are consecutive, so a workgroup changes
             // point about once per frames_per_point / workgroups frames and the reload below is rare)
@@ -818,6 +881,10 @@ __global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? AD
             // Constants the compiler must not see through: everything derived from the register-resident tables
             // (addresses, +-1 patterns) would otherwise be hoisted out of the sweep loop into ~5 registers per entry.
             uint32_t k80, k1 = 1, k2 = 2, lds0, one_hi, mlw_o = mlw_pk, gen_o = gen_pk;
+            if constexpr (IS_CODES) {  // (values carried around the frame loop: scalar again for the "s" operands below)
+                mlw_o = (uint32_t) __builtin_amdgcn_readfirstlane((int) mlw_o);
+                gen_o = (uint32_t) __builtin_amdgcn_readfirstlane((int) gen_o);
+            }
             asm volatile("s_mov_b32 %0, 0x80000000\n\ts_mov_b32 %1, 0" : "=s"(k80), "=s"(lds0));
             if (!LEAN) asm volatile("s_mov_b32 %0, 1\n\ts_mov_b32 %1, 2" : "=s"(k1), "=s"(k2));  // (only the long-list path shifts by them)
             if (sizeof(T) == 8) asm volatile("v_mov_b32 %0, 0x3ff00000" : "=v"(one_hi));  // in a VGPR: (x & k80) | one_hi is one v_and_or_b32
@@ -916,6 +983,8 @@ __global__ void __launch_bounds__(ADMM_BLK, ADMM_OCC - BP + (sizeof(T) == 4 ? AD
     }
 }
 
+#undef ADMM_LOAD_STRUCTURE
+
 // guard path (qp_admm.h:112-114): all-zero word, ok = false, no sweeps
 __global__ void admm_guard_kernel(DecodeArgs a, int nwords) {
     for (int64_t f = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; f < a.frames; f += (int64_t) gridDim.x * blockDim.x) {
@@ -987,7 +1056,22 @@ static const void *admm_block_ptr(int f32, bool ee, int passes, bool lean) {
 
 static const char *const ADMM_NO_FIT = "QP-ADMM frame state does not fit in LDS (160 KiB per CU)";
 
-static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err) {
+// Where admm_device_create_lds puts a table.  blob == null: a device allocation of its own, kept in `keep` (a decoder handle).
+// Otherwise the table is appended to the host blob, 256-byte aligned, and the value returned is its OFFSET in the blob (never 0)
+// in place of an address: admm_codes_tables turns the offsets into device addresses once the blob has its place on the device.
+template <typename T>
+static const T *admm_put(const std::vector<T> &h, std::vector<DeviceBuf> &keep, std::vector<unsigned char> *blob) {
+    if (!blob) return upload_keep(h, keep);
+    const size_t off = std::max<size_t>((blob->size() + 255) & ~(size_t) 255, 256);
+    blob->resize(off + std::max<size_t>(h.size(), 1) * sizeof(T), 0);
+    if (!h.empty()) memcpy(blob->data() + off, h.data(), h.size() * sizeof(T));
+    return reinterpret_cast<const T *>((uintptr_t) off);
+}
+
+// blob != null (acg_ldpc_mc_run_codes): the same tables into a host blob instead of device memory, the workgroup-per-frame
+// kernel or nothing, and no HIP call at all — the caller uploads the blob and sizes the launch
+static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &p, int cu_count, std::string &err,
+                                          std::vector<unsigned char> *blob = nullptr) {
     const AdmmLayout &A = c.admm;
     std::unique_ptr<AdmmDevice> own(new AdmmDevice());
     AdmmDevice *d = own.get();
@@ -1027,6 +1111,10 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         d->blockmode = true;
     } else if (p.lanes_per_frame == ADMM_BLK) {
         err = "lanes_per_frame = 256 needs at most 1024 constraint groups and variables";
+        return nullptr;
+    }
+    if (blob && !d->blockmode) {
+        err = "not a code of the workgroup-per-frame kernel";
         return nullptr;
     }
     if (!d->blockmode && L != 16 && L != 32 && L != 64) {
@@ -1193,12 +1281,12 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
             err = "a variable in more than 255 checks: use lanes_per_frame 16/32/64 for QP-ADMM";
             return nullptr;
         }
-        t.blk_mem = upload_keep(blk_mem, d->allocs);
-        t.blk_list = upload_keep(blk_list, d->allocs);
-        t.blk_mlw = upload_keep(blk_mlw, d->allocs);
-        t.grp_type_slot = upload_keep(type_slot, d->allocs);
-        t.blk_generic = upload_keep(blk_generic, d->allocs);
-        t.blk_cell = upload_keep(blk_cell, d->allocs);
+        t.blk_mem = admm_put(blk_mem, d->allocs, blob);
+        t.blk_list = admm_put(blk_list, d->allocs, blob);
+        t.blk_mlw = admm_put(blk_mlw, d->allocs, blob);
+        t.grp_type_slot = admm_put(type_slot, d->allocs, blob);
+        t.blk_generic = admm_put(blk_generic, d->allocs, blob);
+        t.blk_cell = admm_put(blk_cell, d->allocs, blob);
         t.cell_is_slot = 1;
         for (int sidx = 0; sidx < t.n_vpass * L; sidx++)
             if (blk_cell[sidx] >= 0 && blk_cell[sidx] != sidx) t.cell_is_slot = 0;
@@ -1209,20 +1297,20 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
             for (int w_ = 0; w_ < 4; w_++) d->blk_lean = d->blk_lean && blk_mlw[(size_t) p_ * 4 + w_] <= admm_vk(p_);
         ok = t.blk_mem && t.blk_list && t.blk_mlw && t.grp_type_slot && t.blk_generic && t.blk_cell;
     }
-    t.grp_mem = upload_keep(grp_mem, d->allocs);
-    t.grp_type = upload_keep(grp_type, d->allocs);
-    t.var_of_slot = upload_keep(var_of_slot, d->allocs);
-    t.v_maxlist = upload_keep(v_maxlist, d->allocs);
-    t.v_list_off = upload_keep(v_list_off, d->allocs);
-    t.v_list = upload_keep(v_list, d->allocs);
+    t.grp_mem = admm_put(grp_mem, d->allocs, blob);
+    t.grp_type = admm_put(grp_type, d->allocs, blob);
+    t.var_of_slot = admm_put(var_of_slot, d->allocs, blob);
+    t.v_maxlist = admm_put(v_maxlist, d->allocs, blob);
+    t.v_list_off = admm_put(v_list_off, d->allocs, blob);
+    t.v_list = admm_put(v_list, d->allocs, blob);
     if (d->f32) {
         std::vector<float> inv32(inv64.begin(), inv64.end());
-        t.inv_coef = upload_keep(inv32, d->allocs);
+        t.inv_coef = admm_put(inv32, d->allocs, blob);
     } else {
-        t.inv_coef = upload_keep(inv64, d->allocs);
+        t.inv_coef = admm_put(inv64, d->allocs, blob);
     }
-    t.row_ptr = upload_keep(c.row_ptr, d->allocs);
-    t.edge_var = upload_keep(c.edge_var, d->allocs);
+    t.row_ptr = admm_put(c.row_ptr, d->allocs, blob);
+    t.edge_var = admm_put(c.edge_var, d->allocs, blob);
     ok = ok && t.grp_mem && t.grp_type && t.var_of_slot && t.v_maxlist && t.v_list_off && t.v_list && t.inv_coef && t.row_ptr && t.edge_var;
     if (!ok) {
         err = acg_ldpc_last_error();
@@ -1239,6 +1327,11 @@ static AdmmDevice *admm_device_create_lds(const Code &c, const acg_ldpc_params &
         if (per_frame > 160 * 1024) {
             err = ADMM_NO_FIT;
             return nullptr;
+        }
+        d->passes = std::max(std::max(t.n_gpass, t.n_vpass), 2);
+        if (blob) {
+            for (int ee = 0; ee < 2; ee++) d->kernel_codes[ee] = admm_block_ptr<AdmmCodesArgs>(d->f32, ee != 0, d->passes, d->blk_lean);
+            return own.release();
         }
         int per_cu = 0;
         for (int ee = 0; ee < 2; ee++) {  // kernel[0]: fixed sweep count, kernel[1]: with the residual stopping rule
@@ -1518,6 +1611,75 @@ hipError_t admm_launch(AdmmDevice *d, const DecodeArgs &a, hipStream_t s, std::s
     int64_t blocks = (a.frames + d->frames_per_block - 1) / d->frames_per_block;
     int grid = (int) std::min<int64_t>(blocks, d->grid_cap);
     const hipError_t e = d->f32 ? admm_launch_t<float>(d, a, grid, s) : admm_launch_t<double>(d, a, grid, s);
+    if (e != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+// ---- batch of codes (acg_ldpc_mc_run_codes) ----------------------------------------------------------------------------
+// The tables of `c` exactly as a decoder handle with these parameters would have them, appended to the host blob; null
+// (err says why) when the handle would not run the workgroup-per-frame kernel on this code.  Makes no HIP call.
+AdmmDevice *admm_codes_plan(const Code &c, const acg_ldpc_params &p, std::vector<unsigned char> &blob, std::string &err) {
+    return admm_device_create_lds(c, p, 1, err, &blob);
+}
+
+// launch shape: codes with equal shapes share a launch (threads per workgroup, BP instance, LEAN or general; the precision is
+// the parameters' and so the same for every code of a call)
+int admm_codes_shape(const AdmmDevice *d) { return d->block | (d->passes << 12) | ((d->blk_lean ? 1 : 0) << 16); }
+size_t admm_codes_lds(const AdmmDevice *d) { return d->lds_block; }
+size_t admm_codes_tables_bytes() { return sizeof(AdmmDevTables); }
+void admm_codes_csr(const AdmmDevice *d, size_t *row_ptr_off, size_t *edge_var_off) {
+    *row_ptr_off = (size_t) (uintptr_t) d->t.row_ptr;
+    *edge_var_off = (size_t) (uintptr_t) d->t.edge_var;
+}
+
+// the plan's AdmmDevTables for a blob that lies at device address `base`, written to out (admm_codes_tables_bytes() bytes)
+void admm_codes_tables(const AdmmDevice *d, uintptr_t base, void *out) {
+    AdmmDevTables t = d->t;
+    auto at = [base](auto *&ptr) {
+        if (ptr) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + (uintptr_t) ptr);
+    };
+    at(t.grp_mem), at(t.grp_type), at(t.var_of_slot), at(t.v_maxlist), at(t.v_list_off), at(t.v_list), at(t.inv_coef);
+    at(t.blk_mem), at(t.blk_list), at(t.blk_mlw), at(t.grp_type_slot), at(t.blk_generic), at(t.blk_cell), at(t.row_ptr), at(t.edge_var);
+    memcpy(out, &t, sizeof t);
+}
+
+// workgroups one launch of this shape with `lds` bytes of dynamic LDS can keep resident (0: err is set)
+int admm_codes_grid_cap(const AdmmDevice *d, size_t lds, int cu_count, std::string &err) {
+    int per_cu = 0;
+    for (int ee = 0; ee < 2; ee++) {
+        const void *kp = d->kernel_codes[ee];
+        if (lds > 64 * 1024 && hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds) != hipSuccess) {
+            err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
+            return 0;
+        }
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, lds) != hipSuccess) occ = 1;
+        per_cu = std::max(per_cu, std::max(occ, 1));  // frames are handed out dynamically: a generous grid is safe
+    }
+    return per_cu * cu_count;
+}
+
+template <typename T>
+static hipError_t admm_launch_codes_t(const AdmmDevice *d, const void *tabs_dev, uint32_t frames_per_code, size_t lds, int grid,
+                                      const DecodeArgs &a, hipStream_t s) {
+    AdmmDevTables tt{};  // (every code brings its own)
+    DecodeArgs aa = a;
+    T alpha = (T) d->alpha, mu = (T) d->mu, eps = (T) d->eps;
+    AdmmCodesArgs c{reinterpret_cast<const AdmmDevTables *>(tabs_dev), frames_per_code};
+    void *args[6] = {&tt, &aa, &alpha, &mu, &eps, &c};
+    const int which = (a.early_exit && d->eps > 0) ? 1 : 0;  // as admm_launch_t
+    return hipLaunchKernel(d->kernel_codes[which], dim3(grid), dim3(d->block), args, lds, s);
+}
+
+// a.frames = codes * frames_per_code virtual frames of the codes whose tables are tabs_dev[0 .. codes), all of d's shape
+hipError_t admm_codes_launch(const AdmmDevice *d, const void *tabs_dev, uint32_t frames_per_code, size_t lds, int grid_cap,
+                             const DecodeArgs &a, hipStream_t s) {
+    if (!d->kernel_codes[0] || a.mc || a.max_iter == 0 || frames_per_code == 0 || a.frames <= 0 || a.frames >= ((int64_t) 1 << 31) ||
+        a.frames % frames_per_code != 0 || lds < d->lds_block)
+        return hipErrorInvalidValue;
+    const int grid = (int) std::min<int64_t>(a.frames, std::max(grid_cap, 1));
+    const hipError_t e = d->f32 ? admm_launch_codes_t<float>(d, tabs_dev, frames_per_code, lds, grid, a, s)
+                                : admm_launch_codes_t<double>(d, tabs_dev, frames_per_code, lds, grid, a, s);
     if (e != hipSuccess) return e;
     return hipGetLastError();
 }

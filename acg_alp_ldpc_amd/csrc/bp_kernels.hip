@@ -256,6 +256,93 @@ hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bit
     return hipGetLastError();
 }
 
+// The same for a batch of codes (acg_ldpc_mc_run_codes): virtual frame g = code * frames + f carries the outputs of frame f
+// decoded with code `code`; its symbols are y[g] (every code transmits its own words), its sent word, CSR and counters row are
+// refs[code]'s.  bits == null (then ok and iters are null too): guard codes — all-zero words, ok = false, no sweeps.
+template <typename Y>
+__global__ void classify_codes_kernel(const Y *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
+                                      int64_t codes, int n, int nwords, int64_t first_frame, const CodeRef *refs, int m) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t) gridDim.x * (blockDim.x >> 6);
+    const int64_t total = frames * codes, per = (total + nw - 1) / nw;
+    const int64_t g0 = wid * per, g1 = g0 + per < total ? g0 + per : total;
+    unsigned long long c_ok = 0, c_ps = 0, c_tot = 0, c_h = 0, c_hok = 0, c_hw = 0, c_it = 0;
+    auto flush = [&](int64_t code) {
+        if (lane == 0 && c_tot) {
+            unsigned long long *row = refs[code].counters;
+            atomicAdd(&row[MC_CORRECT], c_ok);
+            atomicAdd(&row[MC_PSEUDO], c_ps);
+            atomicAdd(&row[MC_TOTAL], c_tot);
+            atomicAdd(&row[MC_HAM], c_h);
+            atomicAdd(&row[MC_HAM_OK], c_hok);
+            atomicAdd(&row[MC_HAM_WRONG], c_hw);
+            atomicAdd(&row[MC_ITERS], c_it);
+        }
+        c_ok = c_ps = c_tot = c_h = c_hok = c_hw = c_it = 0;
+    };
+    int64_t code = g0 < g1 ? g0 / frames : 0;
+    for (int64_t g = g0; g < g1; ++g) {
+        if (g >= (code + 1) * frames) {
+            flush(code);
+            code = g / frames;
+        }
+        const int64_t f = g - code * frames;
+        const CodeRef r = refs[code];
+        const uint32_t *cw = r.cw_packed ? r.cw_packed + (size_t) ((first_frame + f) % r.n_cw) * nwords : nullptr;
+        int ham;
+        bool correct, pseudo;
+        classify_frame(y + (size_t) g * n, bits ? bits + (size_t) g * nwords : nullptr, bits ? ok[g] != 0 : false, cw, n, nwords,
+                       bits ? r.row_ptr : nullptr, r.edge_var, m, lane, ham, correct, pseudo);
+        c_ok += correct;
+        c_ps += pseudo;
+        c_tot += 1;
+        c_h += ham;
+        c_hok += correct ? ham : 0;
+        c_hw += correct ? 0 : ham;
+        c_it += (bits && iters) ? iters[g] : 0;
+    }
+    flush(code);
+}
+
+hipError_t classify_codes_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                 int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame, const CodeRef *refs, int m,
+                                 hipStream_t s) {
+    int grid = (int) std::min<int64_t>((frames * codes + 3) / 4, 256 * 8);
+    if (grid < 1) grid = 1;
+    if (y_is_f64)
+        hipLaunchKernelGGL(classify_codes_kernel<double>, dim3(grid), dim3(256), 0, s, (const double *) y, bits, ok, iters, frames, codes,
+                           n, nwords, first_frame, refs, m);
+    else
+        hipLaunchKernelGGL(classify_codes_kernel<float>, dim3(grid), dim3(256), 0, s, (const float *) y, bits, ok, iters, frames, codes, n,
+                           nwords, first_frame, refs, m);
+    return hipGetLastError();
+}
+
+// Host-noise symbols of a batch of codes: y[code][f][v] = (+-1 of the code's sent word) + noise[f][v], in double — the one
+// IEEE addition of utils/channel.h:24 with the normal deviate the host drew for global frame first_frame + f, which is the
+// same for every code (the generator is seeded by the frame alone, experiment.h:90-99).
+__global__ void codes_symbols_kernel(const double *noise, double *y, int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame,
+                                     const CodeRef *refs) {
+    const int64_t per = frames * n, total = per * codes;
+    for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t) gridDim.x * blockDim.x) {
+        const int64_t code = i / per, r = i - code * per, f = r / n;
+        const int v = (int) (r - f * n);
+        const CodeRef c = refs[code];
+        const uint32_t bit = c.cw_packed ? (c.cw_packed[(size_t) ((first_frame + f) % c.n_cw) * nwords + (v >> 5)] >> (v & 31)) & 1u : 0u;
+        y[i] = (bit ? -1.0 : 1.0) + noise[r];
+    }
+}
+
+hipError_t codes_symbols_launch(const double *noise, double *y, int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame,
+                                const CodeRef *refs, hipStream_t s) {
+    const int64_t total = frames * codes * n;
+    int grid = (int) std::min<int64_t>((total + 255) / 256, 256 * 16);
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(codes_symbols_kernel, dim3(grid), dim3(256), 0, s, noise, y, frames, codes, n, nwords, first_frame, refs);
+    return hipGetLastError();
+}
+
 hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
                            int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
                            unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,

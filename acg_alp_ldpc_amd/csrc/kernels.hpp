@@ -63,6 +63,15 @@ struct DecodeArgs {
     void *dbg_post;
 };
 
+// One code of a batch (acg_ldpc_mc_run_codes) as the classification and symbol kernels of bp_kernels.hip see it
+struct CodeRef {
+    const uint32_t *cw_packed;     // n_cw * nwords sent words of THIS code, null = the all-zero word
+    int64_t n_cw;
+    const int32_t *row_ptr;        // its CSR (IsCodeword, experiment.h:111); unused by guard codes
+    const int32_t *edge_var;
+    unsigned long long *counters;  // its row of MC_NCOUNTERS
+};
+
 // ---- QP-ADMM constraint rows (qp_admm.h:34-83), shared by the streamed engine (admm_streamed.hip) and host checks ----
 // A constraint group of type 3 (three variables, qp_admm.h:34-57) owns 4 consecutive rows, type 2 (:75-83) 2 rows, type 1
 // (:70-74) 1 row.  Member `wpos` (its position in the group's construction, 0..2) has coefficient +1 in row `wpos` and in

@@ -36,6 +36,11 @@ hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *
                            int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
                            unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
                            hipStream_t s);
+hipError_t classify_codes_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                 int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame, const CodeRef *refs, int m,
+                                 hipStream_t s);
+hipError_t codes_symbols_launch(const double *noise, double *y, int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame,
+                                const CodeRef *refs, hipStream_t s);
 hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
                                 int64_t frames, int64_t points, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
                                 int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
@@ -71,6 +76,16 @@ void admm_grid_tables(const AdmmDevice *d, const double *alpha, const double *mu
                       std::vector<unsigned char> &inv);
 void admm_grid_bind(AdmmDevice *d, const void *pt_dev, const void *inv_dev, uint32_t frames_per_point);
 bool admm_device_set_point(AdmmDevice *d, double alpha, double mu, std::string &err);
+// batch of codes (acg_ldpc_mc_run_codes): a plan is an AdmmDevice whose tables lie in a host blob (see admm_kernels.hip)
+AdmmDevice *admm_codes_plan(const Code &c, const acg_ldpc_params &p, std::vector<unsigned char> &blob, std::string &err);
+int admm_codes_shape(const AdmmDevice *d);
+size_t admm_codes_lds(const AdmmDevice *d);
+size_t admm_codes_tables_bytes();
+void admm_codes_csr(const AdmmDevice *d, size_t *row_ptr_off, size_t *edge_var_off);
+void admm_codes_tables(const AdmmDevice *d, uintptr_t base, void *out);
+int admm_codes_grid_cap(const AdmmDevice *d, size_t lds, int cu_count, std::string &err);
+hipError_t admm_codes_launch(const AdmmDevice *d, const void *tabs_dev, uint32_t frames_per_code, size_t lds, int grid_cap,
+                             const DecodeArgs &a, hipStream_t s);
 
 // ---- admm_streamed.hip (called by admm_kernels.hip) ----
 struct AdmmStream;

@@ -137,6 +137,81 @@ def run_experiment_grid(decoder, codewords, H, snr, alphas, mus, frames=None, fi
                              kernel_ms=r.kernel_ms) for r in res[:a.size]]
 
 
+class CodesEvaluator:
+    """acg_ldpc_evaluator: scores batches of parity-check matrices of one m x n under one set of QP-ADMM parameters
+    (the scoring of optimize_H.cpp:16-25 for many proposals at once).  params_or_decoder: a QPADMMDecoder (its alpha, mu,
+    max_iter, eps_stop, early_exit, precision, lanes_per_frame and engine apply) or a _lib.Params."""
+
+    def __init__(self, params_or_decoder):
+        p = params_or_decoder if isinstance(params_or_decoder, _lib.Params) else params_or_decoder._params()
+        self._h = C.c_void_p()
+        check(lib().acg_ldpc_evaluator_create(C.byref(p), C.byref(self._h)))
+
+    def run(self, codes, snr, frames=None, first_frame=0, noise="host", seed=1):
+        """codes: a list of (H, codewords); H a ParityCheckMatrix or a dense 0/1 matrix, codewords an array of that code's own
+        words (None: the all-zero word).  Returns one ExperimentResult per code, equal in the seven counters to run_experiment
+        on that code's own QPADMMDecoder(..., fast_setup=True); guard codes (e_min*mu <= alpha) are counted as failures."""
+        from .code import ParityCheckMatrix
+        pcms, cws = [], []
+        cfgs = (McCfg * max(1, len(codes)))()
+        for k, (H, cw) in enumerate(codes):
+            code = H if isinstance(H, ParityCheckMatrix) else ParityCheckMatrix(H)
+            pcms.append(code)
+            cfg = cfgs[k]
+            if cw is not None:
+                cw = np.ascontiguousarray(cw, dtype=np.uint8)
+                if cw.ndim != 2 or cw.shape[1] != code.n:
+                    raise ValueError("codewords must be count x n")
+                cfg.codewords = cw.ctypes.data
+                cfg.n_codewords = cw.shape[0]
+            cws.append(cw)  # (keeps the array alive for the call)
+            f = frames
+            if f is None:
+                if cw is None:
+                    raise ValueError("frames required without codewords")
+                f = cw.shape[0]
+            cfg.frames = int(f)
+            cfg.first_frame = int(first_frame)
+            cfg.snr = float(snr)
+            cfg.seed = int(seed)
+            cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
+        handles = (C.c_void_p * max(1, len(pcms)))(*[c._h.value for c in pcms])
+        res = (McResult * max(1, len(pcms)))()
+        check(lib().acg_ldpc_mc_run_codes(self._h, handles, len(pcms), cfgs, res))
+        return [ExperimentResult(**{f: getattr(r, f) for f in ExperimentResult.FIELDS}, time_sec=r.time_sec,
+                                 kernel_ms=r.kernel_ms) for r in res[:len(pcms)]]
+
+    def describe(self):
+        """one line on what the last run did: mc_codes=single-launch groups=<g> chunks=<c> ... or mc_codes=per-code ..."""
+        buf = C.create_string_buffer(512)
+        lib().acg_ldpc_evaluator_describe(self._h, buf, 512)
+        return buf.value.decode()
+
+    def close(self):
+        if self._h:
+            lib().acg_ldpc_evaluator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def run_experiment_codes(params_or_decoder, codes, snr, frames=None, first_frame=0, noise="host", seed=1):
+    """acg_ldpc_mc_run_codes: run_experiment for every (H, codewords) of `codes` in one call — the codes the
+    workgroup-per-frame QP-ADMM kernel accepts share one launch per launch shape.  params_or_decoder: a QPADMMDecoder, a
+    _lib.Params, or a CodesEvaluator to reuse (its buffers stay).  See CodesEvaluator.run."""
+    if isinstance(params_or_decoder, CodesEvaluator):
+        return params_or_decoder.run(codes, snr, frames, first_frame, noise, seed)
+    ev = CodesEvaluator(params_or_decoder)
+    try:
+        return ev.run(codes, snr, frames, first_frame, noise, seed)
+    finally:
+        ev.close()
+
+
 def run_experiment_sharded(decoder, codewords, H, snr, frames, rank=0, world=1, noise="device", seed=1, group=None):
     """One rank's shard + host-side sum of the counters across ranks.
 

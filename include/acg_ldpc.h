@@ -244,6 +244,30 @@ void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b);
 int acg_ldpc_mc_run_grid(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
                          int32_t n_points, acg_ldpc_mc_result *res);
 
+/* replaces the scoring of optimize_H.cpp:16-25 for a BATCH of parity-check matrices: acg_ldpc_mc_run for n_codes codes of one
+ * m x n under one set of QP-ADMM parameters.  An evaluator owns one stream, one work-counter ring, one set of staging and
+ * output buffers, one table buffer and one counter buffer; it creates no decoder handle and allocates nothing per code.
+ * res[k] equals, in its seven integer counters, what acg_ldpc_mc_run returns on a decoder created from codes[k] with *params
+ * and fast_setup = 1, given cfgs[k]; time_sec of every entry is the wall time of the call, kernel_ms the device time of the
+ * code's launch divided by the codes in that launch.  cfgs[k].codewords / n_codewords are per code; frames, first_frame, snr,
+ * seed and noise must be equal in every cfgs[k].  A guard code (e_min*mu <= alpha for that code's e_min) is not an error: it
+ * gets what the reference's loop computes from DecodeQPADMM's (zeros, false) (qp_admm.h:112-114), as a guard point of
+ * acg_ldpc_mc_run_grid does.  Sharding by first_frame / frames and acg_ldpc_mc_merge per code work as for acg_ldpc_mc_run.
+ * Single launch: with parameters that select the workgroup-per-frame kernel (lanes_per_frame 0 or 256, not the streamed
+ * engine, max_iter > 0) the codes that kernel accepts are grouped by launch shape (threads per workgroup, passes, lean or
+ * general instance) and every group decodes in one launch per chunk of codes x frames (chunked like the parameter grid);
+ * acg_ldpc_evaluator_describe then says mc_codes=single-launch groups=<g> chunks=<c>.  Every other code runs through a decoder
+ * handle of its own on the evaluator's stream, with the same results (mc_codes=per-code when no code took a shared launch).
+ * Errors (non-zero, message in acg_ldpc_last_error, nothing launched): parameters that are not QP-ADMM, n_codes < 1, null
+ * pointers, codes of different m or n, cfgs that disagree, no device. */
+typedef struct acg_ldpc_evaluator acg_ldpc_evaluator;
+int acg_ldpc_evaluator_create(const acg_ldpc_params *params, acg_ldpc_evaluator **out);
+void acg_ldpc_evaluator_destroy(acg_ldpc_evaluator *ev);
+int acg_ldpc_mc_run_codes(acg_ldpc_evaluator *ev, const acg_ldpc_code *const *codes, int32_t n_codes,
+                          const acg_ldpc_mc_cfg *cfgs, acg_ldpc_mc_result *res);
+/* one line on what the last acg_ldpc_mc_run_codes of this evaluator did; buf / cap / return value as acg_ldpc_decoder_describe */
+int32_t acg_ldpc_evaluator_describe(const acg_ldpc_evaluator *ev, char *buf, int32_t cap);
+
 /* ---- host-side generators used by the reference's drivers (bit-exact, libstdc++) ----------- */
 
 /* replaces gen_random_codewords (utils/channel.h:28-44) with std::mt19937(seed): row i of G (k x n bytes)

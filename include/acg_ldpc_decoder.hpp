@@ -268,4 +268,46 @@ private:
     bool _layered;
 };
 
+// Scores a batch of parity-check matrices of one m x n under one set of QP-ADMM parameters (acg_ldpc_mc_run_codes): the
+// scoring step of optimize_H.cpp:16-25 for many proposals at once.  Thin: one evaluator handle, results as the C ABI's.
+class QPADMMEvaluator {
+public:
+    explicit QPADMMEvaluator(double alpha, double mu, int max_iter = 2000, double eps_stop = 1e-5) {
+        acg_ldpc_params p;
+        acg_ldpc_params_default(&p);
+        p.algo = ACG_LDPC_QPADMM;
+        p.alpha = alpha;
+        p.mu = mu;
+        p.max_iter = max_iter;
+        p.eps_stop = eps_stop;
+        check(acg_ldpc_evaluator_create(&p, &ev_));
+    }
+    ~QPADMMEvaluator() { acg_ldpc_evaluator_destroy(ev_); }
+    QPADMMEvaluator(const QPADMMEvaluator &) = delete;
+    QPADMMEvaluator &operator=(const QPADMMEvaluator &) = delete;
+
+    // res[k] for codes[k] / cfgs[k]; frames, first_frame, snr, seed and noise must be equal in every cfg
+    std::vector<acg_ldpc_mc_result> run(const std::vector<const acg_ldpc_code *> &codes, const std::vector<acg_ldpc_mc_cfg> &cfgs) {
+        assert(codes.size() == cfgs.size());
+        std::vector<acg_ldpc_mc_result> res(codes.size());
+        check(acg_ldpc_mc_run_codes(ev_, codes.data(), (int32_t) codes.size(), cfgs.data(), res.data()));
+        return res;
+    }
+
+    std::string describe() const {
+        char b[512];
+        acg_ldpc_evaluator_describe(ev_, b, (int32_t) sizeof b);
+        return b;
+    }
+
+private:
+    static void check(int rc) {
+        if (rc != 0) {
+            std::fprintf(stderr, "acg_ldpc: error %d: %s\n", rc, acg_ldpc_last_error());
+            std::abort();
+        }
+    }
+    acg_ldpc_evaluator *ev_ = nullptr;
+};
+
 }  // namespace acg_ldpc
