@@ -62,6 +62,16 @@ class ParityCheckMatrix:
         check(lib().acg_ldpc_debug_layers(self._h, C.byref(G), C.byref(nl), C.byref(Z), chk.ctypes.data, chk.size))
         return G.value, Z.value, chk
 
+    def layers_block(self):
+        """sets of the layered schedule with one workgroup per frame (SCHEDULE_LAYERED, lanes_per_frame 256 / 512 / 1024):
+        (circulant size Z or 0, [n_layers, width] check ids in processing order, occupied slots first, -1 = empty slot);
+        width is the largest set, which may exceed the workgroup"""
+        nl, w, Z = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().acg_ldpc_debug_layers_block(self._h, C.byref(nl), C.byref(w), C.byref(Z), None, 0))
+        chk = np.full((nl.value, w.value), -1, dtype=np.int32)
+        check(lib().acg_ldpc_debug_layers_block(self._h, C.byref(nl), C.byref(w), C.byref(Z), chk.ctypes.data, chk.size))
+        return Z.value, chk
+
     def is_codeword(self, bits):
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         assert b.shape[-1] == self.n

@@ -293,6 +293,11 @@ struct acg_ldpc_decoder {
     bool layered = false;
     LayeredLayout llay;
     LayerTables ltab{};
+    // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory
+    bool layered_block = false;
+    LayeredBlockLayout lblay;
+    LayerBlockTables lbtab{};
+    DeviceBuf lb_step, lb_pos;
     // streamed BP engine
     bool streamed = false;
     StreamTables stab{};
@@ -633,6 +638,57 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
     return 0;
 }
 
+// schedule = LAYERED with one workgroup of L = 256, 512 or 1024 threads per frame (bp_layered_block.hip): the layered engine for
+// codes whose frame is too large for a wavefront group.  Its only size limit is the LDS of a CU: posteriors + messages +
+// output word of ONE frame.
+static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L) {
+    const Code &c = d->c;
+    const bool f16 = d->p.precision == ACG_LDPC_PREC_F16;
+    if (!bp_layered_block_build(c, d->lblay)) return 3;
+    const LayeredBlockLayout &ll = d->lblay;
+    LayerBlockTables &t = d->lbtab;
+    t.n = c.n;
+    t.nwords = (c.n + 31) / 32;
+    t.e = ll.e;
+    t.n_sets = ll.n_sets;
+    t.p_words = (c.n + 1 + 3) & ~3;
+    t.r_words = f16 ? (ll.e + 1) / 2 : ll.e;
+    const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
+    const int algo = d->p.algo == ACG_LDPC_BP_MINSUM ? 1 : 0;
+    const void *kp = bp_layered_block_kernel_ptr(L, f16, algo);
+    if (!kp) {
+        set_error("no layered workgroup-per-frame kernel instance for this lanes_per_frame");
+        return 3;
+    }
+    hipFuncAttributes fa{};
+    HIP_OK(hipFuncGetAttributes(&fa, kp));
+    if (lds + fa.sharedSizeBytes > 160 * 1024) {   // (sharedSizeBytes: the kernel's few control words)
+        set_error("layered schedule: a frame (posteriors + messages) does not fit in LDS");
+        return 3;
+    }
+    std::vector<int32_t> step, pos4(ll.pos.size());
+    bp_layered_block_steps(ll, L, step);
+    for (size_t i = 0; i < ll.pos.size(); i++) pos4[i] = 4 * ll.pos[i];
+    d->lb_step = upload(step, 8);
+    d->lb_pos = upload(pos4);
+    if (!d->lb_step.p || !d->lb_pos.p) return 10;
+    t.step = d->lb_step.as<const int32_t>();
+    t.pos = d->lb_pos.as<const int32_t>();
+    t.n_steps = (int) (step.size() / 8);
+    d->layered_block = true;
+    d->L = L;
+    d->f64 = 0;
+    d->block = L;
+    d->frames_per_block = 1;
+    d->lds_block = lds;
+    // decode only: a Monte-Carlo run goes AWGN kernel -> decode -> classification kernel (acg_ldpc_mc_run)
+    if (int rc = bind_kernel(d, 0, kp)) return rc;
+    d->kernel[1] = nullptr;
+    d->grid_cap[1] = d->grid_cap[0];
+    d->tab.lds_bytes_per_frame = (int32_t) lds;
+    return 0;
+}
+
 // schedule = LAYERED: min-sum over conflict-free layers of checks with in-place posteriors (bp_layered.hip)
 static int decoder_setup_layered(acg_ldpc_decoder *d) {
     const Code &c = d->c;
@@ -643,10 +699,15 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
         return 3;
     }
     const bool lay_f16 = d->p.precision == ACG_LDPC_PREC_F16;
+    // 256, 512, 1024: one workgroup per frame.  0 keeps the wavefront-group kernel for every code it accepts and falls
+    // through to a workgroup of 1024 only where that kernel refuses for size (n >= 16000 here, a frame beyond LDS below)
+    const int want_L = d->p.lanes_per_frame;
+    if (want_L == 256 || want_L == 512 || want_L == 1024) return decoder_setup_layered_block(d, want_L);
+    if (want_L == 0 && c.n >= 16000) return decoder_setup_layered_block(d, 1024);
     if (!bp_layered_build(c, d->llay)) return 3;
     const LayeredLayout &ll = d->llay;
     if (d->p.lanes_per_frame != 0 && d->p.lanes_per_frame != ll.G) {
-        set_error("layered schedule: lanes_per_frame is chosen by the layering (pass 0)");
+        set_error("layered schedule: lanes_per_frame is chosen by the layering (pass 0), or 256, 512, 1024 for one workgroup per frame");
         return 3;
     }
     LayerTables &t = d->ltab;
@@ -689,6 +750,10 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
         waves = best_w;
     }
     if (per_wave * waves + t.tab_lds_bytes > 160 * 1024) {
+        if (want_L == 0) {   // the workgroup-per-frame engine keeps no table in LDS and splits a frame over 16 wavefronts
+            d->ltab = LayerTables{};
+            return decoder_setup_layered_block(d, 1024);
+        }
         set_error("layered schedule: a frame (posteriors + messages) does not fit in LDS");
         return 3;
     }
@@ -1081,6 +1146,11 @@ static std::string describe(const acg_ldpc_decoder *d) {
             }
             return t;
         }
+    } else if (d->layered_block) {
+        snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_block_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
+                               "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=%s",
+                 algo, d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width,
+                 d->p.precision == ACG_LDPC_PREC_F16 ? "fp16" : "fp32");
     } else {
         snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=%d block=%d frames_per_block=%d lds_block=%zu grid_cap=%d "
                                "idx_lds=%d idx_reg=%d schedule=%s",
@@ -1166,6 +1236,13 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
         } else {
             HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, (uint32_t *) d->sws.va, grid, W * 64, s));
         }
+    } else if (d->layered_block) {
+        if (a.mc) {
+            set_error("internal: the workgroup-per-frame layered engine has no in-kernel generator");
+            return 11;
+        }
+        const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
+        HIP_OK(bp_layered_block_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
     } else if (d->layered) {
         const int mc = a.mc ? 1 : 0;
         const int64_t blocks = (a.frames + d->frames_per_block - 1) / d->frames_per_block;
@@ -1579,9 +1656,9 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
     int rc = 0;
     if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
         rc = mc_run_host_noise(d, cfg, res);
-    } else if (d->streamed || d->pair || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
+    } else if (d->streamed || d->pair || d->layered_block || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
         // AWGN kernel -> decode -> classify kernel, in bounded chunks, all on the device.  Used by the streamed BP
-        // engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
+        // engine and the workgroup-per-frame layered engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
         // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
         if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
@@ -2381,6 +2458,23 @@ int acg_ldpc_debug_ring_tasks(const acg_ldpc_code *code, int32_t *n_ctask, int32
             consts[2] = RING_SLOT_LINES;
             consts[3] = RING_VAR_EDGE_LINES;
         }
+        return 0;
+    });
+}
+
+int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
+    return guarded([&]() -> int {
+        if (!code) {
+            set_error("null argument");
+            return 1;
+        }
+        LayeredBlockLayout ll;
+        if (!bp_layered_block_build(code->c, ll)) return 3;
+        if (n_layers) *n_layers = ll.n_sets;
+        if (width) *width = ll.width;
+        if (qc_Z) *qc_Z = ll.qc ? ll.Z : 0;
+        if (chk)
+            for (int64_t i = 0; i < std::min<int64_t>(cap, (int64_t) ll.chk.size()); i++) chk[i] = ll.chk[(size_t) i];
         return 0;
     });
 }

@@ -803,6 +803,87 @@ bool bp_layered_build(const Code &c, LayeredLayout &o) {
     return true;
 }
 
+// Sets of the workgroup-per-frame layered schedule (see LayeredBlockLayout).
+bool bp_layered_block_build(const Code &c, LayeredBlockLayout &o) {
+    o = LayeredBlockLayout();
+    if (c.m <= 0 || c.n <= 0) {
+        set_error("layered schedule: the matrix has no checks");
+        return false;
+    }
+    if (c.max_cdeg > 8) {
+        set_error("layered schedule: check degree above 8 is not supported");
+        return false;
+    }
+    struct Set { int deg; std::vector<int> chk; };
+    std::vector<Set> sets;
+    QcInfo q;
+    const bool qc = code_detect_qc(c, q) && q.Z >= 2;
+    if (qc) {
+        for (int R = 0; R < q.mb; R++) {
+            Set s{c.row_ptr[R * q.Z + 1] - c.row_ptr[R * q.Z], {}};
+            for (int k = 0; k < q.Z; k++) s.chk.push_back(R * q.Z + k);
+            if (s.deg > 0) sets.push_back(s);
+        }
+    } else {
+        std::vector<std::vector<uint8_t>> used;  // per set: variable occupied
+        for (int r = 0; r < c.m; r++) {
+            const int deg = c.row_ptr[r + 1] - c.row_ptr[r];
+            if (deg == 0) continue;
+            size_t k = 0;
+            for (; k < sets.size(); k++) {
+                if (sets[k].deg != deg) continue;
+                bool free_ = true;
+                for (int e = c.row_ptr[r]; e < c.row_ptr[r + 1] && free_; e++) free_ = !used[k][c.edge_var[e]];
+                if (free_) break;
+            }
+            if (k == sets.size()) {
+                sets.push_back(Set{deg, {}});
+                used.emplace_back((size_t) c.n, 0);
+            }
+            sets[k].chk.push_back(r);
+            for (int e = c.row_ptr[r]; e < c.row_ptr[r + 1]; e++) used[k][c.edge_var[e]] = 1;
+        }
+    }
+    if (sets.empty()) {
+        set_error("layered schedule: the matrix has no checks");
+        return false;
+    }
+    o.qc = qc;
+    o.Z = qc ? q.Z : 0;
+    o.n_sets = (int) sets.size();
+    for (auto &s : sets) o.width = std::max(o.width, (int) s.chk.size());
+    o.chk.assign((size_t) o.n_sets * o.width, -1);
+    int off = 0;
+    for (size_t k = 0; k < sets.size(); k++) {
+        const Set &s = sets[k];
+        const int cnt = (int) s.chk.size();
+        o.set.push_back(s.deg);
+        o.set.push_back(off);
+        o.set.push_back(cnt);
+        o.pos.resize((size_t) off + (size_t) s.deg * cnt);
+        for (int i = 0; i < cnt; i++) {
+            const int r = s.chk[i];
+            o.chk[k * o.width + i] = r;
+            for (int j = 0; j < s.deg; j++) o.pos[(size_t) off + (size_t) j * cnt + i] = c.edge_var[c.row_ptr[r] + j];
+        }
+        off += s.deg * cnt;
+    }
+    o.e = off;
+    return true;
+}
+
+void bp_layered_block_steps(const LayeredBlockLayout &lay, int L, std::vector<int32_t> &step) {
+    step.clear();
+    for (int k = 0; k < lay.n_sets; k++) {
+        const int deg = lay.set[3 * k], off = lay.set[3 * k + 1], cnt = lay.set[3 * k + 2];
+        for (int s0 = 0; s0 < cnt; s0 += L) {
+            const bool last_pass = s0 + L >= cnt;
+            const int32_t w[8] = {deg, (last_pass && k + 1 < lay.n_sets) ? 1 : 0, off + s0 * deg, off + s0, std::min(L, cnt - s0), cnt, 0, 0};
+            step.insert(step.end(), w, w + 8);
+        }
+    }
+}
+
 namespace {
 
 int admm_llen(const AdmmLayout &A, int i) { return A.var_ptr[i + 1] - A.var_ptr[i]; }

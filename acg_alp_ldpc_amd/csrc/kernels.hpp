@@ -99,6 +99,22 @@ struct LayerTables {
     int32_t lds_bytes_per_frame;
 };
 
+// Workgroup-per-frame layered BP (bp_layered_block.hip; LayeredBlockLayout in ldpc_internal.hpp).  Both tables live in device
+// memory; a workgroup's LDS holds the state of its frame and nothing else.
+struct LayerBlockTables {
+    // [n_steps][8]: the (set, pass) pairs of one iteration in processing order =
+    //   {degree, 1 = barrier behind the step (the last pass of a set; 0 behind the last set: the round's OR is its barrier),
+    //    message cell of (edge 0, thread 0), position entry of (edge 0, thread 0), checks in the pass (<= L),
+    //    checks in the whole set (the distance between the position entries of consecutive edges), 0, 0}
+    const int32_t *step;
+    const int32_t *pos;      // [e] byte offset of the posterior cell of (set, edge j, slot) at set offset + j * cnt + slot
+    int32_t n_steps, n_sets;
+    int32_t n, nwords;
+    int32_t e;               // message cells per frame = edges of the graph
+    int32_t p_words;         // posterior words per frame (n + the neutral cell, rounded up to a multiple of 4)
+    int32_t r_words;         // 32-bit words the e message cells occupy (e, or half of it rounded up for fp16 storage)
+};
+
 // Streamed ("HBM") BP engine: plain CSR of the Tanner graph, read through scalar loads.
 struct StreamTables {
     const int32_t *row_ptr;   // [m+1] edges in check-major order (variables ascending)

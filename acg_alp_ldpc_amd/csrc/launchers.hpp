@@ -53,6 +53,11 @@ const void *bp_pair_kernel_ptr(int L, bool regular);
 const void *bp_layered_kernel_ptr(int G, int waves, bool qc_arith, bool f16, int algo, bool mc);
 hipError_t bp_layered_launch(const void *kernel, const LayerTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s);
 
+// ---- bp_layered_block.hip ----
+const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo);
+hipError_t bp_layered_block_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
+                                   hipStream_t s);
+
 // ---- bp_streamed.hip ----
 const void *bp_streamed_ptr(int algo, int f64);
 const void *bp_streamed_ring_ptr(int algo, bool nt);

@@ -154,6 +154,25 @@ struct LayeredLayout {
 };
 bool bp_layered_build(const Code &c, LayeredLayout &out);
 
+// ---- layered schedule for one workgroup per frame (bp_layered_block.hip) ----------------------------------------------
+// The same kind of layering — sets of checks of ONE degree that share no variable, in a fixed processing order, empty checks
+// left out — without a bound on the size of a set: a workgroup of L threads works a set off in ceil(cnt / L) passes.
+// Quasi-cyclic H: the block rows.  Any other H: first-fit colouring in row order (a check joins the first set of its degree in
+// which none of its variables occurs yet).  Slot s of a set is its s-th check in that order.
+struct LayeredBlockLayout {
+    int n_sets = 0;
+    int width = 0;             // checks in the largest set
+    bool qc = false;
+    int Z = 0;
+    int e = 0;                 // entries of pos = edges of the graph
+    std::vector<int32_t> set;        // [n_sets][3] = {degree, offset (entries of pos = message cells), checks}
+    std::vector<int32_t> chk;        // [n_sets*width] check id of (set, slot), -1 = none; occupied slots first
+    std::vector<int32_t> pos;        // [e] variable of edge j (ascending variable order) of (set, slot) at offset + j * cnt + slot
+};
+bool bp_layered_block_build(const Code &c, LayeredBlockLayout &out);
+// the (set, pass) steps of LayerBlockTables for a workgroup of L threads
+void bp_layered_block_steps(const LayeredBlockLayout &lay, int L, std::vector<int32_t> &step);
+
 // ---- placement of the QP-ADMM problem on the threads / LDS of admm_block_kernel ------------------------------------
 // One workgroup of L threads owns a frame: thread l handles, in pass p, the variable var_of_slot[p*L + l] (v-update) and
 // the constraint group living in U slot p*L + l (row phase).  LDS: V[cell] (fp64/fp32 words) and U[slot][4 rows], tiled so
