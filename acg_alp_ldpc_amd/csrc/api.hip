@@ -287,6 +287,13 @@ struct acg_ldpc_decoder {
     size_t lds_block = 0;
     int variant = -1;       // wave-group kernels: 0 / 1 / 2 (see bp_inst_*.hip); -1 = workgroup-per-frame
     bool phi_memo = false;  // DecodeArgs::phi_memo (the SAT instances read it)
+    // the SAT instances' freeze of latched frames whose state recurs (bp_fused_body): one snapshot slot per resident frame
+    // group behind a small head with the debug counter (DecodeArgs::freeze_ws), allocated at the first launch
+    bool freeze = false;
+    bool freeze_count = false;  // acg_ldpc_debug_freeze_stats asked for the counter
+    int freeze_first = 0, freeze_period = 0;
+    size_t freeze_slot_words = 0;
+    DeviceBuf freeze_ws;
     bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
     bool blk_idxlds = false, blk_idxreg = false;
     // layered min-sum (bp_layered.hip)
@@ -1000,6 +1007,17 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     const bool sat = !d->p.early_exit && getenv("ACG_BP_NO_SATSKIP") == nullptr;
     // the phi memo of the absorbed check passes in those instances (BpPass::phi_c); ACG_BP_NO_PHIMEMO=1 turns it off (A/B runs)
     d->phi_memo = sat && getenv("ACG_BP_NO_PHIMEMO") == nullptr;
+    // a latched frame of those instances stops sweeping once its state recurs (bp_fused_body, FREEZE): same outputs, fewer
+    // sweeps executed; ACG_BP_NO_FREEZE=1 runs them all (A/B runs).  The cadence is in sweeps behind the latch: the first
+    // snapshot, then a compare (and a new snapshot) every `period` (tools/freeze_census.cpp, profiles/r09_freeze_summary.md).
+    d->freeze = sat && algo == 0 && !d->f64 && d->maxd <= 8 && idxlds && llr_regs && getenv("ACG_BP_NO_FREEZE") == nullptr;
+    d->freeze_first = 10;  // measured best on the headline among 3 ... 12 / 1 ... 4 (profiles/r09_freeze_summary.md)
+    d->freeze_period = 1;
+    if (const char *e = getenv("ACG_BP_FREEZE_CADENCE")) {  // "first,period" (tuning runs)
+        int f = 0, q = 0;
+        if (sscanf(e, "%d,%d", &f, &q) == 2 && f >= 1 && q >= 1 && f < (1 << 12) && q < (1 << 12)) d->freeze_first = f, d->freeze_period = q;
+    }
+    d->freeze_slot_words = (size_t) lay.a_words + (size_t) BP_MAX_APASS * L;
     for (int mc = 0; mc < 2; mc++) {
         const int variant = idxlds ? ((llr_regs) ? 2 : 1) : 0;
         d->variant = variant;
@@ -1158,6 +1176,13 @@ static std::string describe(const acg_ldpc_decoder *d) {
                  d->frames_per_block, d->lds_block, d->grid_cap[0], d->variant < 0 ? (int) d->blk_idxlds : (d->variant > 0), (int) d->blk_idxreg,
                  d->p.schedule == ACG_LDPC_SCHEDULE_LAYERED ? (d->p.precision == ACG_LDPC_PREC_F16 ? "layered messages=fp16" : "layered messages=fp32")
                                                             : "flooding");
+        if (d->variant >= 0 && !d->layered && !d->pair && !d->p.early_exit) {
+            // fixed-work decoders: whether latched frames whose state recurs stop sweeping, and on which cadence
+            std::string t = b;
+            if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period);
+            else t += " freeze=0";
+            return t;
+        }
     }
     return b;
 }
@@ -1195,7 +1220,8 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
     const int slot = (int) (d->launch_seq++ % acg_ldpc_decoder::WORK_RING);
     if (d->ring_used[slot]) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[slot], 0));
     // engines whose HBM workspace belongs to the handle (streamed BP, streamed QP-ADMM): a launch on another stream waits
-    const bool owns_ws = d->streamed || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
+    // (and the snapshot slots of the fused kernels' freeze path)
+    const bool owns_ws = d->streamed || d->freeze || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
     if (owns_ws && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
     a.work_counter = d->work_counter(slot);
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
@@ -1252,6 +1278,19 @@ static int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
         int64_t blocks = (a.frames + d->frames_per_block - 1) / d->frames_per_block;
         const int mc = a.mc ? 1 : 0;
         int grid = (int) std::min<int64_t>(blocks, d->grid_cap[mc]);
+        if (d->freeze && !a.dbg_c2v && !a.dbg_v2c) {
+            // one slot per frame group of the largest grid this handle launches: sized once, so no launch in flight loses it
+            // (the kernel forms 32-bit word offsets: a workspace beyond 2^31 words, far from any code these kernels take, goes without)
+            const size_t words = FREEZE_WS_HEAD + (size_t) std::max(d->grid_cap[0], d->grid_cap[1]) * d->frames_per_block * d->freeze_slot_words;
+            if (words < ((size_t) 1 << 31)) {
+                if (!d->freeze_ws.p) {
+                    if (d->freeze_ws.reserve(words * sizeof(uint32_t))) return 10;
+                    HIP_OK(hipMemsetAsync(d->freeze_ws.p, 0, FREEZE_WS_HEAD * sizeof(uint32_t), s));
+                }
+                a.freeze_ws = d->freeze_ws.as<uint32_t>();
+                a.freeze_cfg = (uint32_t) d->freeze_first | ((uint32_t) d->freeze_period << 12) | (d->freeze_count ? 0x80000000u : 0u);
+            }
+        }
         HIP_OK(bp_launch(d->kernel[mc], d->tab, a, grid, d->block, d->lds_block, s));
     }
     HIP_OK(hipEventRecord(d->ring_ev[slot], s));   // stop event of this launch = the event later users of the slot wait on
@@ -2521,6 +2560,32 @@ static int acg_ldpc_debug_phi_sat_impl(const void *x_host, void *out_host, int32
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out_host, dout.p, 12 * (size_t) n, hipMemcpyDeviceToHost));
     return 0;
+}
+
+static int acg_ldpc_debug_freeze_stats_impl(acg_ldpc_decoder *d, int32_t enable, int64_t *frames_frozen, int64_t *sweeps_not_run) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    // every launch of the handle so far, on its own stream or a caller's
+    HIP_OK(hipStreamSynchronize(d->stream));
+    for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++)
+        if (d->ring_used[k]) HIP_OK(hipEventSynchronize(d->ring_ev[k]));
+    unsigned long long h = 0;
+    if (d->freeze_ws.p) {  // the counter is the head of the workspace
+        HIP_OK(hipMemcpy(&h, d->freeze_ws.p, sizeof(h), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemset(d->freeze_ws.p, 0, sizeof(h)));
+    }
+    if (frames_frozen) *frames_frozen = (int64_t) (h >> FREEZE_STATS_SHIFT);
+    if (sweeps_not_run) *sweeps_not_run = (int64_t) (h & ((1ull << FREEZE_STATS_SHIFT) - 1));
+    d->freeze_count = enable != 0 && d->freeze;
+    return 0;
+}
+
+int acg_ldpc_debug_freeze_stats(acg_ldpc_decoder *d, int32_t enable, int64_t *frames_frozen, int64_t *sweeps_not_run) {
+    return guarded([&] { return acg_ldpc_debug_freeze_stats_impl(d, enable, frames_frozen, sweeps_not_run); });
 }
 
 int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n) {

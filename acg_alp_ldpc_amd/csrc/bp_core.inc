@@ -519,7 +519,9 @@ struct BpCore {
     // takes for fixed-work decoders only: with early exit few frames stay long enough to saturate, and the test and its
     // EXEC-mask branch per edge (2 vector + 3 scalar instructions) would cost more than the skipped phi evaluations save
     static constexpr bool SATSKIP = SAT && ALGO == 0 && sizeof(T) == 4 && L <= 64;
-    __device__ __forceinline__ int var_id(const VarIds &vi, int p) const { return NVP > 0 ? vi[p] : t.v_var[p * L + l]; }
+    // REGS = false: read from the table every time (an instance that needs the registers more than the load, see bp_fused_body)
+    template <bool REGS = true>
+    __device__ __forceinline__ int var_id(const VarIds &vi, int p) const { return (NVP > 0 && REGS) ? vi[p] : t.v_var[p * L + l]; }
     __device__ __forceinline__ T get_llr(const LlrRegs &lr, int p, int slot) const { return NVP > 0 ? lr[p] : LLR[slot]; }
     __device__ __forceinline__ void set_llr(LlrRegs &lr, int p, int slot, T v) {
         if (NVP > 0) lr[p] = v;
@@ -887,11 +889,12 @@ struct BpCore {
     }
 
     // pack the frame's hard decisions into OB[0..nwords)
+    template <bool REGS = true>
     __device__ __forceinline__ void pack_bits(const LlrRegs &lr, const VarIds &vi, const AbsWord &aw) {
         for (int w = l; w < t.nwords; w += L) OB[w] = 0u;
         group_sync<L>();
         for (int p = 0; p < t.n_vpass; ++p) {
-            const int v = var_id(vi, p);
+            const int v = var_id<REGS>(vi, p);
             if (v >= 0 && hard_bit(lr, p)) atomicOr(&OB[v >> 5], 1u << (v & 31));
         }
 #pragma unroll
@@ -961,12 +964,16 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     T *LLR = A + t.a_words;
     uint32_t *OB = reinterpret_cast<uint32_t *>(LLR + t.llr_words);
     Core core(t, A, LLR, OB, IDX, l, a.ms_scale);
+    // the instances with the freeze path (see `fz` below) and what they pay for its registers: the variable ids are read from the
+    // table when a frame starts and when it is written out, not held for the whole kernel
+    constexpr bool FREEZE = Core::SATSKIP && NVP > 0 && !DBG;  // (NVP > 0: the instances the host takes for fixed-work decoders)
+    constexpr bool VIREG = !FREEZE;
     typename Core::LlrRegs lr;
     typename Core::VarIds vi;
 #pragma unroll
     for (int p = 0; p < (NVP > 0 ? NVP : 1); ++p) {
         lr[p] = (T) 0;
-        vi[p] = (NVP > 0 && p < t.n_vpass) ? t.v_var[p * L + l] : -1;
+        vi[p] = (VIREG && NVP > 0 && p < t.n_vpass) ? t.v_var[p * L + l] : -1;
     }
     // absorbed degree-1 variables (BpPass::check_abs): LLR, v->c word, c->v word (debug trace only) per absorbed pass
     // and, in the SATSKIP instances, the phi memo of its check's other edges (Core::abs_phi; memo off: am = 0, ag = +inf)
@@ -993,6 +1000,14 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     bool need_init = false;
     bool latched = false;
     int it = 0;
+    // FREEZE (fixed-work SAT instances, a.freeze_ws set): a latched frame stops sweeping once its state recurs.  A flooding sweep
+    // is a function of (A, aw) and of per-frame constants (LLRs, ag); a latched frame writes no output any more.  So when the
+    // words after sweep k equal, bit for bit, those after sweep k - p, every later state is one already seen and the remaining
+    // sweeps can change nothing the caller gets: the frame retires as if it had run them (it = max_iter).  The words of p
+    // sweeps ago are kept in the group's slot of a.freeze_ws; a lane reads back only the words it wrote itself.
+    // fz = 0 until the frame latches (it takes the place of `latched` in these instances), then
+    //      sweeps until the next detection << 2 | the slot holds a snapshot taken since the latch << 1 | 1.
+    int fz = 0;
     int ham = 0;  // raw-channel errors of the current frame (MC)
     // per-group MC accumulators (flushed once at the end)
     unsigned int acc_correct = 0, acc_pseudo = 0, acc_total = 0;
@@ -1014,11 +1029,15 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     // by than the syndrome passes cost (measured: +1.1 % fixed-50, -3.4 % with early exit).
     constexpr bool MERGED = ACG_FUSED_MERGED && ALGO == 1 && MAXD <= 8 && NVP > 0;  // (NVP > 0: at most 12 variable passes, the bit mask holds them)
     uint32_t hard = 0;  // MERGED: posterior hard decisions of my variables, bit p = pass p
+    auto is_latched = [&]() -> bool {
+        if constexpr (FREEZE) return fz != 0;
+        else return latched;
+    };
     auto emit = [&](const bool out_now, const bool fail_now) {
         if (__ballot(out_now || fail_now) != 0ull) {
             if (out_now) {
                 if (MERGED) core.pack_bits_mask(hard, vi);
-                else core.pack_bits(lr, vi, aw);
+                else core.template pack_bits<VIREG>(lr, vi, aw);
             }
             else if (fail_now) {
                 for (int w = l; w < t.nwords; w += L) OB[w] = 0u;  // reference returns an empty vector, bp.h:198
@@ -1049,7 +1068,8 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                     acc_ham_wrong += correct ? 0 : ham;
                     acc_iters += it < a.max_iter ? it : a.max_iter;
                 }
-                latched = true;
+                if constexpr (FREEZE) fz = (int) ((a.freeze_cfg & 0xFFFu) << 2) | 1;
+                else latched = true;
             }
         }
     };
@@ -1131,7 +1151,7 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                     }
                     return llr;
                 };
-                for (int p = 0; p < t.n_vpass; ++p) core.set_llr(lr, p, p * L + l, chan_llr(core.var_id(vi, p)));
+                for (int p = 0; p < t.n_vpass; ++p) core.set_llr(lr, p, p * L + l, chan_llr(core.template var_id<VIREG>(vi, p)));
                 // absorbed variables: LLR and the constant v->c word (+0 for a lane without one)
 #pragma unroll
                 for (int q = 0; q < Core::NAP; ++q) {
@@ -1157,6 +1177,7 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
             if (need_init) {
                 it = 0;
                 latched = false;
+                if constexpr (FREEZE) fz = 0;
                 need_init = false;
             }
             // a fresh frame with max_iter == 0 must fail without iterating; handled by the next round's test
@@ -1202,12 +1223,12 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
         // ---- syndrome of the estimate produced by the previous variable phase -----------------
         // (a group that has not been initialised yet has it == 0 and ignores the result)
         // fixed work: once every group of the wave has latched its output (or is idle) the syndrome feeds nothing
-        const bool pend = active && !latched && it > 0;
+        const bool pend = active && !is_latched() && it > 0;
         const bool bad = __ballot(pend) != 0ull ? group_any<L>(core.syndrome_bad(aw), g) : true;
         const bool conv = active && it > 0 && it <= a.max_iter && !bad;     // bp.h:195 (max_iter = 0: never)
-        const bool out_now = conv && !latched;
+        const bool out_now = conv && !is_latched();
         const bool finish = active && ((a.early_exit && conv) || it >= a.max_iter);
-        const bool fail_now = finish && !conv && !latched;
+        const bool fail_now = finish && !conv && !is_latched();
         emit(out_now, fail_now);
         if (finish) {
             active = false;
@@ -1238,6 +1259,52 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                     reinterpret_cast<T *>(a.dbg_v2c)[(size_t) frame * dbg_cw + t.a_words + q * L + l] = FpBits<T>::from(aw[q]);
                     reinterpret_cast<T *>(a.dbg_post)[(size_t) frame * dbg_pw + (t.n_vpass + q) * L + l] = al[q];
                 }
+        }
+        if constexpr (FREEZE) {
+            if (a.freeze_ws) {
+                const bool cand = active && fz != 0;
+                fz -= cand ? 4 : 0;
+                const bool due = cand && fz < 4 && it + 1 < a.max_iter;  // (nothing left to save behind the last sweep)
+                if (__ballot(due) != 0ull) {
+                    // moved: a word differs from the snapshot, or there is none to compare with (or the group is not due)
+                    typename Core::U moved = (due && (fz & 2)) ? 0 : 1;
+                    if (due) {
+                        // the slot's address is formed here, from values the compiler cannot trace back to the loop-invariant
+                        // thread and block ids: hoisted out of the sweep loop it would hold registers the sweeps need
+                        uint32_t tid = threadIdx.x, bid = blockIdx.x;
+                        asm volatile("" : "+v"(tid), "+s"(bid));
+                        const uint32_t slot = bid * (blockDim.x / L) + tid / L;  // (the host keeps the workspace below 2^31 words)
+                        uint32_t *snap = a.freeze_ws + FREEZE_WS_HEAD + (size_t) (slot * (uint32_t) (t.a_words + Core::NAP * L));
+#pragma unroll 1
+                        for (int w = (int) (tid % L); w < t.a_words; w += 4 * L) {  // (tid % L = l, as opaque as the address; no trip-count set-up to hoist)
+                            typename Core::U cur[4], old[4];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) old[k] = w + k * L < t.a_words ? snap[w + k * L] : 0;  // four loads in flight
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) cur[k] = w + k * L < t.a_words ? FpBits<T>::to(A[w + k * L]) : 0;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                moved |= cur[k] ^ old[k];
+                                if (w + k * L < t.a_words) snap[w + k * L] = cur[k];
+                            }
+                        }
+#pragma unroll
+                        for (int q = 0; q < Core::NAP; ++q) {
+                            if (q < core.n_apass()) {
+                                moved |= aw[q] ^ snap[t.a_words + q * L + (int) (tid % L)];
+                                snap[t.a_words + q * L + (int) (tid % L)] = aw[q];
+                            }
+                        }
+                        fz = (int) (((a.freeze_cfg >> 12) & 0xFFFu) << 2) | 3;
+                    }
+                    if (!group_any<L>(moved != 0, g)) {
+                        if ((int32_t) a.freeze_cfg < 0 && l == 0)
+                            atomicAdd(reinterpret_cast<unsigned long long *>(a.freeze_ws),
+                                      (1ull << FREEZE_STATS_SHIFT) + (unsigned long long) (a.max_iter - (it + 1)));
+                        it = a.max_iter - 1;  // retires at the head of the loop: finish, already latched
+                    }
+                }
+            }
         }
         it += 1;
     }

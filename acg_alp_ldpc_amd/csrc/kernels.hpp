@@ -61,7 +61,17 @@ struct DecodeArgs {
     void *dbg_c2v;
     void *dbg_v2c;
     void *dbg_post;
+    // fused fixed-work sum-product (the SAT instances of bp_fused_body): a latched frame whose state recurs stops sweeping.
+    // (Last in the block: the kernels that do not read them keep every argument offset.)
+    // freeze_ws: FREEZE_WS_HEAD words (the first two: a debug counter, += frames frozen << FREEZE_STATS_SHIFT | sweeps not run),
+    // then one snapshot slot of a_words + BP_MAX_APASS * L words per resident frame group [grid * groups per block]; null = off.
+    // freeze_cfg: bits 0-11 sweeps between the latch and the first snapshot (>= 1), bits 12-23 sweeps between a snapshot and
+    // the compare against it (>= 1), bit 31 count.  (Three scalar registers in all: the kernel has none to spare.)
+    uint32_t *freeze_ws;
+    uint32_t freeze_cfg;
 };
+constexpr int FREEZE_WS_HEAD = 4;
+constexpr int FREEZE_STATS_SHIFT = 40;
 
 // One code of a batch (acg_ldpc_mc_run_codes) as the classification and symbol kernels of bp_kernels.hip see it
 struct CodeRef {

@@ -189,6 +189,14 @@ class Decoder:
         lib().acg_ldpc_decoder_describe(h, buf, 1024)
         return buf.value.decode()
 
+    def freeze_stats(self, H, enable=True):
+        """(frames frozen, sweeps not run) by the handle's launches since the previous call (acg_ldpc_debug_freeze_stats);
+        enable: whether later launches keep counting.  Zeros for a handle without the freeze path."""
+        h, _ = self.handle(H)
+        a, b = C.c_int64(), C.c_int64()
+        check(lib().acg_ldpc_debug_freeze_stats(h, 1 if enable else 0, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def layout(self, H):
         h, _ = self.handle(H)
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()

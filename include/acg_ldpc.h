@@ -301,6 +301,12 @@ int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f6
 /* diagnostics: the phi fast path of the fp32 sum-product sweeps on n float inputs in the kernels' log2(e)-scaled domain;
  * out: 3n uint32 = per input the bits of the full phi, of the check-side path and of the variable-side path (on |x|). */
 int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n);
+/* diagnostics: counters of the fixed-work fused sum-product kernels' freeze path (a latched frame whose message state recurs
+ * bit for bit stops sweeping; outputs are those of max_iter sweeps; ACG_BP_NO_FREEZE=1 at handle creation runs every sweep).
+ * Waits for the handle's launches, returns what they counted since the previous call (frames frozen; sweeps those frames did
+ * not execute), then clears the counters.  enable != 0: later launches count (no effect on a handle without the path: both
+ * figures stay 0); enable == 0: counting stops.  A launch counts at most 2^24 - 1 frozen frames. */
+int acg_ldpc_debug_freeze_stats(acg_ldpc_decoder *d, int32_t enable, int64_t *frames_frozen, int64_t *sweeps_not_run);
 /* diagnostics: soft state of the device sum-product decoder after `iters` full iterations of bp.h:183-199 without
  * the exit test, for 1..64 frames (y: frames*n doubles).  Outputs are frames*E (edge order: check-major, variables
  * ascending) / frames*n doubles: c2v = messages check->variable, (v2c_mag, v2c_sgn) = the (phi(|x|), sign) pairs
