@@ -4,14 +4,15 @@ Only the hot path of GreatDrake/acg-alp-ldpc is here: BP (algo/bp.h
 (algo/qp_admm.h), the AWGN channel (utils/channel.h) and the Monte-Carlo loop (experiment.h),
 implemented as hand-written HIP kernels for gfx950 in csrc/ behind the C ABI of include/acg_ldpc.h.
 """
-from ._lib import (ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED, PREC_DEFAULT, PREC_F16, PREC_F32, PREC_F64,  # noqa: F401
+from ._lib import (ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED, EVENT_NO_WORD, EVENT_NONCODEWORD, EVENT_PSEUDO, PREC_DEFAULT, PREC_F16, PREC_F32, PREC_F64,  # noqa: F401
                    SCHEDULE_FLOODING, SCHEDULE_LAYERED, LdpcError, build, lib)
 from .channel import gen_random_codewords, llr, llr_variance, transmit_frames  # noqa: F401
 from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
 from .decoder import BeliefPropagationDecoder, Decoder, MinSumDecoder, QPADMMDecoder  # noqa: F401
-from .experiment import (CodesEvaluator, ExperimentResult, merge_exp_results, run_experiment, run_experiment_codes,  # noqa: F401
-                         run_experiment_grid, run_experiment_inproc, run_experiment_sharded, shard_range)
+from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_exp_details, merge_exp_results,  # noqa: F401
+                         run_experiment, run_experiment_codes, run_experiment_detail, run_experiment_grid,
+                         run_experiment_inproc, run_experiment_sharded, shard_range)
 
 
 def read_pcm(path):

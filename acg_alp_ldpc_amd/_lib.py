@@ -36,7 +36,20 @@ class McResult(C.Structure):
                 ("time_sec", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class McDetail(C.Structure):
+    _fields_ = [("base", McResult), ("word_frames", C.c_int64), ("bit_errors", C.c_int64),
+                ("noncodeword_frames", C.c_int64), ("sum_syndrome_weight", C.c_int64), ("n_events", C.c_int64),
+                ("n_stored", C.c_int64), ("min_pseudo_frame", C.c_int64), ("min_pseudo_weight", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class McEvent(C.Structure):
+    _fields_ = [("frame", C.c_int64), ("kind", C.c_int32), ("iters", C.c_int32), ("raw_errors", C.c_int32),
+                ("bit_errors", C.c_int32), ("syndrome_weight", C.c_int32), ("reserved", C.c_int32)]
+
+
 ALGO_BP, ALGO_MINSUM, ALGO_QPADMM = 0, 1, 2
+EVENT_PSEUDO, EVENT_NO_WORD, EVENT_NONCODEWORD = 1, 2, 3
 PREC_DEFAULT, PREC_F64, PREC_F32, PREC_F16 = 0, 1, 2, 3
 NOISE_DEVICE_PHILOX, NOISE_HOST_MT19937 = 0, 1
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED = 0, 1, 2
@@ -70,6 +83,8 @@ SYMBOLS = {
     "acg_ldpc_decoder_describe": (_i32, [_vp, C.c_char_p, _i32]),
     "acg_ldpc_mc_run": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McResult)]),
     "acg_ldpc_mc_merge": (None, [C.POINTER(McResult), C.POINTER(McResult)]),
+    "acg_ldpc_mc_run_detail": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McDetail), _vp, _vp, _i64]),
+    "acg_ldpc_mc_detail_merge": (None, [C.POINTER(McDetail), C.POINTER(McDetail)]),
     "acg_ldpc_mc_run_grid": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _vp, _i32, _vp]),
     "acg_ldpc_evaluator_create": (C.c_int, [C.POINTER(Params), C.POINTER(_vp)]),
     "acg_ldpc_evaluator_destroy": (None, [_vp]),

@@ -329,6 +329,10 @@ struct acg_ldpc_decoder {
     int64_t cw_count = 0;
     uint64_t cw_hash = 0;
     DeviceBuf counters;
+    // detail run (acg_ldpc_mc_run_detail), allocated by its first call: DET_NCOUNTERS counters, one kind byte per frame of a
+    // chunk with its pinned copy, the chunk-relative frames selected as events, their records and XOR rows
+    DeviceBuf det_counters, det_kind, det_sel, det_events, det_words;
+    PinnedBuf det_kind_h, det_sel_h, det_counters_h;
     // parameter grid (acg_ldpc_mc_run_grid): counters[point][MC_NCOUNTERS] and the per-point tables of the chunk in flight
     DeviceBuf grid_counters, grid_tab;
     // Per-launch work counters: every launch takes the next slot of a small ring of device words (the dynamic frame /
@@ -1634,10 +1638,34 @@ void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
     a->kernel_ms += b->kernel_ms;
 }
 
-static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
+// ACG_MC_DETAIL_CHUNK=<frames>: developer / test switch that lowers the chunk of a detail run (README, developer variables)
+static int64_t mc_detail_chunk(int64_t chunk) {
+    const char *e = getenv("ACG_MC_DETAIL_CHUNK");
+    const int64_t v = e ? atoll(e) : 0;
+    return v > 0 ? std::min(chunk, v) : chunk;
+}
+
+// where a detail run (acg_ldpc_mc_run_detail) collects what goes beyond the seven counters
+struct DetailSink {
+    acg_ldpc_mc_detail *out;
+    acg_ldpc_mc_event *events;
+    uint32_t *words;
+    int64_t cap;
+};
+
+// a pseudo frame of weight w >= 1: the running minimum keeps the lowest frame among equal weights (a weight <= 0 in *o means
+// "none yet": -1 as the API reports it, or 0 in an accumulator the caller zeroed)
+static void detail_min_pseudo(acg_ldpc_mc_detail *o, int32_t w, int64_t frame) {
+    if (o->min_pseudo_weight <= 0 || w < o->min_pseudo_weight || (w == o->min_pseudo_weight && frame < o->min_pseudo_frame)) {
+        o->min_pseudo_weight = w;
+        o->min_pseudo_frame = frame;
+    }
+}
+
+static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res, DetailSink *ds = nullptr) {
     // Bit-exact experiment.h:80-123: transmit_host, decoded on the device, classified on the host.
     const int n = d->c.n;
-    const int64_t chunk_max = 1 << 16;
+    const int64_t chunk_max = ds ? mc_detail_chunk(1 << 16) : 1 << 16;
     std::vector<double> y;
     std::vector<uint8_t> bits, ok;
     std::vector<int32_t> iters;
@@ -1654,15 +1682,17 @@ static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, ac
             const int64_t gidx = cfg->first_frame + f0 + f;
             const uint8_t *cw = cfg->codewords ? cfg->codewords + (size_t) (gidx % cfg->n_codewords) * n : nullptr;
             const uint8_t *b = &bits[(size_t) f * n];
-            bool is_correct = false;
+            bool is_correct = false, is_pseudo = false;
             if (ok[f] && code_is_codeword(d->c, b)) {  // experiment.h:110-111
                 bool eq = true;
                 for (int i = 0; i < n; i++) eq &= (b[i] == (cw ? cw[i] : 0));
                 if (eq) {
                     res->correct++;
                     is_correct = true;
-                } else
+                } else {
                     res->pseudo++;
+                    is_pseudo = true;
+                }
             }
             res->total++;
             int h = 0;
@@ -1676,6 +1706,44 @@ static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, ac
             if (is_correct) res->sum_hamming_ok += h;
             else res->sum_hamming_wrong += h;
             res->sum_iters += iters[f];
+            if (ds) {   // the detail run's extension of experiment.h:109-120
+                acg_ldpc_mc_detail *o = ds->out;
+                int dist = 0, synw = 0;
+                if (ok[f]) {
+                    o->word_frames++;
+                    for (int i = 0; i < n; i++) dist += (b[i] != 0) != (cw && cw[i]);
+                    o->bit_errors += dist;
+                    if (!is_correct && !is_pseudo) {
+                        for (int c = 0; c < d->c.m; c++) {
+                            int sy = 0;
+                            for (int e = d->c.row_ptr[c]; e < d->c.row_ptr[c + 1]; e++) sy ^= b[d->c.edge_var[e]] != 0;
+                            synw += sy;
+                        }
+                        o->noncodeword_frames++;
+                        o->sum_syndrome_weight += synw;
+                    }
+                }
+                if (is_pseudo) detail_min_pseudo(o, dist, gidx);
+                if (!is_correct && o->n_stored < ds->cap) {
+                    const int64_t k = o->n_stored++;
+                    acg_ldpc_mc_event &ev = ds->events[k];
+                    ev.frame = gidx;
+                    ev.kind = is_pseudo ? ACG_LDPC_EVENT_PSEUDO : ok[f] ? ACG_LDPC_EVENT_NONCODEWORD : ACG_LDPC_EVENT_NO_WORD;
+                    ev.iters = iters[f];
+                    ev.raw_errors = h;
+                    ev.bit_errors = dist;
+                    ev.syndrome_weight = synw;
+                    ev.reserved = 0;
+                    if (ds->words) {
+                        const int nwords = (n + 31) / 32;
+                        uint32_t *row = ds->words + (size_t) k * nwords;
+                        std::fill(row, row + nwords, 0u);
+                        if (ok[f])
+                            for (int i = 0; i < n; i++)
+                                if ((b[i] != 0) != (cw && cw[i])) row[i >> 5] |= 1u << (i & 31);
+                    }
+                }
+            }
         }
     }
     return 0;
@@ -1762,6 +1830,142 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
 
 int acg_ldpc_mc_run(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_impl(d, cfg, res); });
+}
+
+// ---------------------------------------------------------------- Monte-Carlo detail run
+// Device noise: per chunk AWGN kernel -> plain decode (launch_decode with a.y set: every engine has it) -> classify_detail_kernel,
+// the chunks of the unfused branch of acg_ldpc_mc_run.  Events: the kernel leaves one kind byte per frame; while fewer than
+// cap events are stored the host reads those bytes, takes the lowest non-correct frames of the chunk, and gather_events_kernel
+// writes their records and XOR rows from the chunk's still-resident symbols and outputs.  Chunks run in ascending frame
+// order, so the stored events are the cap lowest frames whatever the chunk size.  Caller holds nothing; d->mu is taken here.
+static int mc_run_detail_device(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, DetailSink &ds) {
+    acg_ldpc_mc_detail *o = ds.out;
+    const int32_t *csr_row = nullptr, *csr_col = nullptr;
+    if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    int rc = 0;
+    if ((rc = ensure_codewords(d, cfg))) return rc;
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    const int64_t chunk = mc_detail_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4))));
+    const size_t fcap = (size_t) chunk;
+    if ((rc = d->mc_y.reserve(fcap * n * sizeof(float)))) return rc;
+    if ((rc = d->st_bits.reserve(fcap * nwords * sizeof(uint32_t)))) return rc;
+    if ((rc = d->st_ok.reserve(fcap))) return rc;
+    if ((rc = d->st_iters.reserve(fcap * sizeof(int32_t)))) return rc;
+    if ((rc = d->det_counters.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
+    if ((rc = d->det_counters_h.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
+    if ((rc = d->det_kind.reserve(fcap))) return rc;
+    if (ds.cap > 0) {
+        const size_t ecap = (size_t) std::min<int64_t>(ds.cap, chunk);   // events one chunk can add
+        if ((rc = d->det_kind_h.reserve(fcap))) return rc;
+        if ((rc = d->det_sel.reserve(ecap * sizeof(int32_t)))) return rc;
+        if ((rc = d->det_sel_h.reserve(ecap * sizeof(int32_t)))) return rc;
+        if ((rc = d->det_events.reserve(ecap * sizeof(acg_ldpc_mc_event)))) return rc;
+        if (ds.words && (rc = d->det_words.reserve(ecap * nwords * sizeof(uint32_t)))) return rc;
+    }
+    unsigned long long *cnt = d->det_counters.as<unsigned long long>(), *cnt_h = d->det_counters_h.as<unsigned long long>();
+    HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DET_NCOUNTERS, d->stream));
+    const SentWords cw = sent_words(d, cfg);
+    float *mc_y = d->mc_y.as<float>();
+    uint8_t *kind = d->det_kind.as<uint8_t>();
+    float kms = 0;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+        HIP_OK(hipMemsetAsync(cnt + DET_MIN_PSEUDO, 0xFF, sizeof(unsigned long long), d->stream));
+        HIP_OK(awgn_launch(mc_y, fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
+        DecodeArgs a{};
+        a.y = mc_y;
+        a.y_is_f64 = 0;
+        a.frames = fc;
+        fill_channel(a, cfg->snr);
+        stage_outputs(d, a);
+        if ((rc = launch_decode(d, a, d->stream))) return rc;
+        const int slot = d->last_slot;   // this launch's own event pair (d->mu is held)
+        HIP_OK(classify_detail_launch(mc_y, a.out_bits, a.out_ok, a.out_iters, fc, n, nwords, first, cw.dev, cw.n, cnt, kind, csr_row,
+                                      csr_col, d->c.m, d->stream));
+        const bool want_events = o->n_stored < ds.cap;
+        if (want_events) HIP_OK(hipMemcpyAsync(d->det_kind_h.p, kind, (size_t) fc, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipMemcpyAsync(cnt_h, cnt, sizeof(unsigned long long) * DET_NCOUNTERS, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess) kms += ms;
+        if (cnt_h[DET_MIN_PSEUDO] != ~0ull)
+            detail_min_pseudo(o, (int32_t) (cnt_h[DET_MIN_PSEUDO] >> 32), first + (int64_t) (cnt_h[DET_MIN_PSEUDO] & 0xFFFFFFFFull));
+        if (want_events) {
+            const uint8_t *kh = d->det_kind_h.as<uint8_t>();
+            int32_t *sel = d->det_sel_h.as<int32_t>();
+            const int64_t room = ds.cap - o->n_stored;
+            int n_sel = 0;
+            for (int64_t f = 0; f < fc && n_sel < room; f++)
+                if (kh[f]) sel[n_sel++] = (int32_t) f;
+            if (n_sel > 0) {
+                HIP_OK(hipMemcpyAsync(d->det_sel.p, sel, (size_t) n_sel * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(gather_events_launch(d->det_sel.as<int32_t>(), n_sel, mc_y, a.out_bits, a.out_ok, a.out_iters, kind, n, nwords, first,
+                                            cw.dev, cw.n, csr_row, csr_col, d->c.m, d->det_events.as<acg_ldpc_mc_event>(),
+                                            ds.words ? d->det_words.as<uint32_t>() : nullptr, d->stream));
+                HIP_OK(hipMemcpyAsync(ds.events + o->n_stored, d->det_events.p, (size_t) n_sel * sizeof(acg_ldpc_mc_event),
+                                      hipMemcpyDeviceToHost, d->stream));
+                if (ds.words)
+                    HIP_OK(hipMemcpyAsync(ds.words + (size_t) o->n_stored * nwords, d->det_words.p, (size_t) n_sel * nwords * sizeof(uint32_t),
+                                          hipMemcpyDeviceToHost, d->stream));
+                HIP_OK(hipStreamSynchronize(d->stream));
+                o->n_stored += n_sel;
+            }
+        }
+    }
+    if (cfg->frames > 0) {
+        counters_to_result(cnt_h, &o->base);
+        o->word_frames = (int64_t) cnt_h[DET_WORD_FRAMES];
+        o->bit_errors = (int64_t) cnt_h[DET_BIT_ERRORS];
+        o->noncodeword_frames = (int64_t) cnt_h[DET_NONCODEWORD];
+        o->sum_syndrome_weight = (int64_t) cnt_h[DET_SYNDROME];
+    }
+    o->base.kernel_ms = kms;
+    return 0;
+}
+
+static int acg_ldpc_mc_run_detail_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out,
+                                       acg_ldpc_mc_event *events, uint32_t *words, int64_t cap) {
+    if (!d || !cfg || !out) {
+        set_error("null argument");
+        return 1;
+    }
+    if (cap < 0 || (cap > 0 && !events)) {
+        set_error("acg_ldpc_mc_run_detail: cap must be >= 0, and events non-null when cap > 0");
+        return 1;
+    }
+    if (cfg->frames < 0 || (cfg->codewords && cfg->n_codewords <= 0)) {
+        set_error("bad mc cfg");
+        return 1;
+    }
+    std::memset(out, 0, sizeof(*out));
+    out->min_pseudo_weight = -1;
+    out->min_pseudo_frame = -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    DetailSink ds{out, events, words, cap};
+    int rc = 0;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) rc = mc_run_host_noise(d, cfg, &out->base, &ds);
+    else rc = mc_run_detail_device(d, cfg, ds);
+    out->n_events = out->base.total - out->base.correct;
+    out->base.time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int acg_ldpc_mc_run_detail(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out, acg_ldpc_mc_event *events,
+                           uint32_t *words, int64_t cap) {
+    return guarded([&] { return acg_ldpc_mc_run_detail_impl(d, cfg, out, events, words, cap); });
+}
+
+void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b) {
+    acg_ldpc_mc_merge(&a->base, &b->base);
+    a->word_frames += b->word_frames;
+    a->bit_errors += b->bit_errors;
+    a->noncodeword_frames += b->noncodeword_frames;
+    a->sum_syndrome_weight += b->sum_syndrome_weight;
+    a->n_events += b->n_events;
+    if (b->min_pseudo_weight > 0) detail_min_pseudo(a, b->min_pseudo_weight, b->min_pseudo_frame);
+    if (a->min_pseudo_weight <= 0) a->min_pseudo_weight = -1, a->min_pseudo_frame = -1;
 }
 
 // ---------------------------------------------------------------- Monte-Carlo over a QP-ADMM parameter grid

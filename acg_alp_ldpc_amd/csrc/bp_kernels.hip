@@ -354,6 +354,162 @@ hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *
     return hipGetLastError();
 }
 
+// ---- detail run (acg_ldpc_mc_run_detail) --------------------------------------------------------------------------------
+// What one wavefront adds to classify_frame for the detail run: d_H(word, sent) with the bits >= n of the last word masked
+// off, and, for decoders that pass a CSR (QP-ADMM), the number of unsatisfied checks.  Both are wave-uniform on return.
+__device__ __forceinline__ void frame_detail(const uint32_t *bits, const uint32_t *cw, int n, int nwords, const int32_t *row_ptr,
+                                             const int32_t *edge_var, int m, int lane, int &dist, int &synw) {
+    const uint32_t last_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
+    dist = 0;
+    for (int w = lane; w < nwords; w += 64) {
+        const uint32_t x = (bits[w] ^ (cw ? cw[w] : 0u)) & (w == nwords - 1 ? last_mask : 0xFFFFFFFFu);
+        dist += __popc(x);
+    }
+    synw = 0;
+    if (row_ptr) {
+        for (int c = lane; c < m; c += 64) {
+            uint32_t sy = 0;
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
+                const int v = edge_var[e];
+                sy ^= (bits[v >> 5] >> (v & 31)) & 1u;
+            }
+            synw += (int) sy;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        dist += __shfl_xor(dist, o, 64);
+        synw += __shfl_xor(synw, o, 64);
+    }
+}
+
+// ACG_LDPC_EVENT_* of a frame, 0 for a correct one (experiment.h:109-120 extended: the frames that are not correct, split by
+// what the decoder returned)
+__device__ __forceinline__ int frame_kind(bool flag, bool correct, bool pseudo) {
+    if (correct) return 0;
+    if (pseudo) return ACG_LDPC_EVENT_PSEUDO;
+    return flag ? ACG_LDPC_EVENT_NONCODEWORD : ACG_LDPC_EVENT_NO_WORD;
+}
+
+// classify_kernel plus the detail counters: one wavefront per frame, sums kept per wavefront, one set of atomics at the end.
+// counters: DET_NCOUNTERS words; [0, MC_NCOUNTERS) are classify_kernel's.  kind[f] = the frame's ACG_LDPC_EVENT_* or 0.
+// counters[DET_MIN_PSEUDO] = min over the pseudo frames of (weight << 32 | chunk-relative frame): the lowest frame wins ties.
+__global__ void classify_detail_kernel(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
+                                       int64_t frames, int n, int nwords, int64_t first_frame, const uint32_t *cw_packed,
+                                       int64_t n_cw, unsigned long long *counters, uint8_t *kind, const int32_t *row_ptr,
+                                       const int32_t *edge_var, int m) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t) gridDim.x * (blockDim.x >> 6);
+    unsigned long long c_ok = 0, c_ps = 0, c_tot = 0, c_h = 0, c_hok = 0, c_hw = 0, c_it = 0;
+    unsigned long long c_word = 0, c_be = 0, c_ncw = 0, c_syn = 0, c_minp = ~0ull;
+    for (int64_t f = wid; f < frames; f += nw) {
+        const uint32_t *cw = cw_packed ? cw_packed + (size_t) ((first_frame + f) % n_cw) * nwords : nullptr;
+        const uint32_t *b = bits + (size_t) f * nwords;
+        const bool flag = ok[f] != 0;
+        int ham;
+        bool correct, pseudo;
+        classify_frame(y + (size_t) f * n, b, flag, cw, n, nwords, row_ptr, edge_var, m, lane, ham, correct, pseudo);
+        c_ok += correct;
+        c_ps += pseudo;
+        c_tot += 1;
+        c_h += ham;
+        c_hok += correct ? ham : 0;
+        c_hw += correct ? 0 : ham;
+        c_it += iters ? iters[f] : 0;
+        const int k = frame_kind(flag, correct, pseudo);
+        if (lane == 0) kind[f] = (uint8_t) k;
+        if (flag && !correct) {   // (a correct frame has distance 0 and no unsatisfied check)
+            int dist, synw;
+            frame_detail(b, cw, n, nwords, row_ptr, edge_var, m, lane, dist, synw);
+            c_be += (unsigned long long) dist;
+            if (k == ACG_LDPC_EVENT_NONCODEWORD) {
+                c_ncw += 1;
+                c_syn += (unsigned long long) synw;
+            } else {
+                const unsigned long long key = ((unsigned long long) (uint32_t) dist << 32) | (unsigned long long) (uint32_t) f;
+                c_minp = key < c_minp ? key : c_minp;
+            }
+        }
+        c_word += flag;
+    }
+    if (lane == 0 && c_tot) {
+        atomicAdd(&counters[MC_CORRECT], c_ok);
+        atomicAdd(&counters[MC_PSEUDO], c_ps);
+        atomicAdd(&counters[MC_TOTAL], c_tot);
+        atomicAdd(&counters[MC_HAM], c_h);
+        atomicAdd(&counters[MC_HAM_OK], c_hok);
+        atomicAdd(&counters[MC_HAM_WRONG], c_hw);
+        atomicAdd(&counters[MC_ITERS], c_it);
+        atomicAdd(&counters[DET_WORD_FRAMES], c_word);
+        if (c_be) atomicAdd(&counters[DET_BIT_ERRORS], c_be);
+        if (c_ncw) {
+            atomicAdd(&counters[DET_NONCODEWORD], c_ncw);
+            atomicAdd(&counters[DET_SYNDROME], c_syn);
+        }
+        if (c_minp != ~0ull) atomicMin(&counters[DET_MIN_PSEUDO], c_minp);
+    }
+}
+
+// The records and XOR rows of the selected frames of a chunk (sel[k] = chunk-relative frame, ascending), from the chunk's
+// still-resident symbols and decode outputs: one wavefront per event.  words == null: records only.
+__global__ void gather_events_kernel(const int32_t *sel, int n_sel, const float *y, const uint32_t *bits, const uint8_t *ok,
+                                     const int32_t *iters, const uint8_t *kind, int n, int nwords, int64_t first_frame,
+                                     const uint32_t *cw_packed, int64_t n_cw, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                     acg_ldpc_mc_event *events, uint32_t *words) {
+    const int lane = threadIdx.x & 63;
+    const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int nw = gridDim.x * (blockDim.x >> 6);
+    const uint32_t last_mask = (n & 31) ? ((1u << (n & 31)) - 1u) : 0xFFFFFFFFu;
+    for (int k = wid; k < n_sel; k += nw) {
+        const int64_t f = sel[k];
+        const uint32_t *cw = cw_packed ? cw_packed + (size_t) ((first_frame + f) % n_cw) * nwords : nullptr;
+        const uint32_t *b = bits + (size_t) f * nwords;
+        const bool flag = ok[f] != 0;
+        int ham;
+        bool correct, pseudo;
+        classify_frame(y + (size_t) f * n, b, flag, cw, n, nwords, nullptr, nullptr, 0, lane, ham, correct, pseudo);  // (for ham)
+        int dist = 0, synw = 0;
+        if (flag) frame_detail(b, cw, n, nwords, row_ptr, edge_var, m, lane, dist, synw);
+        if (lane == 0) {
+            acg_ldpc_mc_event ev;
+            ev.frame = first_frame + f;
+            ev.kind = kind[f];
+            ev.iters = iters ? iters[f] : 0;
+            ev.raw_errors = ham;
+            ev.bit_errors = dist;
+            ev.syndrome_weight = ev.kind == ACG_LDPC_EVENT_NONCODEWORD ? synw : 0;
+            ev.reserved = 0;
+            events[k] = ev;
+        }
+        if (words)
+            for (int w = lane; w < nwords; w += 64)
+                words[(size_t) k * nwords + w] = flag ? (b[w] ^ (cw ? cw[w] : 0u)) & (w == nwords - 1 ? last_mask : 0xFFFFFFFFu) : 0u;
+    }
+}
+
+hipError_t classify_detail_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
+                                  int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
+                                  unsigned long long *counters, uint8_t *kind, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                  hipStream_t s) {
+    int grid = (int) std::min<int64_t>((frames + 3) / 4, 256 * 8);
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(classify_detail_kernel, dim3(grid), dim3(256), 0, s, y, bits, ok, iters, frames, n, nwords, first_frame,
+                       cw_packed, n_cw, counters, kind, row_ptr, edge_var, m);
+    return hipGetLastError();
+}
+
+hipError_t gather_events_launch(const int32_t *sel, int n_sel, const float *y, const uint32_t *bits, const uint8_t *ok,
+                                const int32_t *iters, const uint8_t *kind, int n, int nwords, int64_t first_frame,
+                                const uint32_t *cw_packed, int64_t n_cw, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                acg_ldpc_mc_event *events, uint32_t *words, hipStream_t s) {
+    int grid = std::min((n_sel + 3) / 4, 256 * 8);
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(gather_events_kernel, dim3(grid), dim3(256), 0, s, sel, n_sel, y, bits, ok, iters, kind, n, nwords,
+                       first_frame, cw_packed, n_cw, row_ptr, edge_var, m, events, words);
+    return hipGetLastError();
+}
+
 hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,
                        const uint32_t *cw_packed, int64_t n_cw, float sigma, hipStream_t s) {
     const int64_t total = frames * ((n + 3) >> 2);

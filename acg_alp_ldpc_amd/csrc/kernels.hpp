@@ -30,6 +30,9 @@ constexpr int BP_MAX_APASS = 2;
 
 // per-launch MC statistics (one row per launch; experiment.h:25-68)
 enum { MC_CORRECT = 0, MC_PSEUDO, MC_TOTAL, MC_HAM, MC_HAM_OK, MC_HAM_WRONG, MC_ITERS, MC_NCOUNTERS };
+// the counters of a detail run (acg_ldpc_mc_run_detail): the row above, then acg_ldpc_mc_detail's own sums and, per chunk,
+// the packed (weight << 32 | chunk-relative frame) minimum over the pseudo frames (all ones: none)
+enum { DET_WORD_FRAMES = MC_NCOUNTERS, DET_BIT_ERRORS, DET_NONCODEWORD, DET_SYNDROME, DET_MIN_PSEUDO, DET_NCOUNTERS };
 
 struct DecodeArgs {
     // input

@@ -36,6 +36,15 @@ hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *
                            int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
                            unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
                            hipStream_t s);
+// detail run (acg_ldpc_mc_run_detail): counters = DET_NCOUNTERS words, kind = one byte per frame of the chunk
+hipError_t classify_detail_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
+                                  int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
+                                  unsigned long long *counters, uint8_t *kind, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                  hipStream_t s);
+hipError_t gather_events_launch(const int32_t *sel, int n_sel, const float *y, const uint32_t *bits, const uint8_t *ok,
+                                const int32_t *iters, const uint8_t *kind, int n, int nwords, int64_t first_frame,
+                                const uint32_t *cw_packed, int64_t n_cw, const int32_t *row_ptr, const int32_t *edge_var, int m,
+                                acg_ldpc_mc_event *events, uint32_t *words, hipStream_t s);
 hipError_t classify_codes_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
                                  int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame, const CodeRef *refs, int m,
                                  hipStream_t s);

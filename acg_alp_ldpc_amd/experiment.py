@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import McCfg, McResult, check, lib
+from ._lib import McCfg, McDetail, McResult, check, lib
 
 
 class ExperimentResult:
@@ -100,6 +100,114 @@ def run_experiment(decoder, codewords, H, snr, frames=None, first_frame=0, noise
     check(lib().acg_ldpc_mc_run(h, C.byref(cfg), C.byref(res)))
     return ExperimentResult(**{f: getattr(res, f) for f in ExperimentResult.FIELDS}, time_sec=res.time_sec,
                             kernel_ms=res.kernel_ms)
+
+
+# acg_ldpc_mc_event as a numpy record (32 bytes)
+EVENT_DTYPE = np.dtype([("frame", "<i8"), ("kind", "<i4"), ("iters", "<i4"), ("raw_errors", "<i4"), ("bit_errors", "<i4"),
+                        ("syndrome_weight", "<i4"), ("reserved", "<i4")])
+
+
+class ExperimentDetail(ExperimentResult):
+    """acg_ldpc_mc_detail: ExperimentResult plus the bit errors of the returned words, the frames that are not correct split
+    by kind (_lib.EVENT_*), and the first `cap` of them in ascending global frame order.
+
+    events: numpy structured array (EVENT_DTYPE), n_stored entries.  words: uint32[n_stored, (n+31)//32], row k = returned
+    word XOR sent word of event k (all-zero for an EVENT_NO_WORD), or None when the run did not ask for them.
+    A frame without a returned word (BP out of iterations, QP-ADMM guard) adds nothing to bit_errors: BER() is the bit
+    error rate over returned words — undetected errors for BP, all bit errors for QP-ADMM."""
+    DETAIL_FIELDS = ("word_frames", "bit_errors", "noncodeword_frames", "sum_syndrome_weight", "n_events", "n_stored")
+
+    def __init__(self, n=0, cap=0, events=None, words=None, **kw):
+        super().__init__(**kw)
+        for f in self.DETAIL_FIELDS:
+            setattr(self, f, int(kw.get(f, 0)))
+        self.min_pseudo_weight = int(kw.get("min_pseudo_weight", -1))
+        self.min_pseudo_frame = int(kw.get("min_pseudo_frame", -1))
+        self.n = int(n)
+        self.cap = int(cap)
+        self.events = np.zeros(0, dtype=EVENT_DTYPE) if events is None else events
+        self.words = words
+
+    def BER(self):
+        """bit errors of the returned words over ALL transmitted bits (total * n)"""
+        return self.bit_errors / (self.total * self.n)
+
+    def BER_returned(self):
+        """the same per returned word: bit_errors / (word_frames * n)"""
+        return self.bit_errors / max(1, self.word_frames * self.n)
+
+    def mean_syndrome_weight(self):
+        return self.sum_syndrome_weight / max(1, self.noncodeword_frames)
+
+    def __repr__(self):
+        return "ExperimentDetail(" + ", ".join("%s=%d" % (f, getattr(self, f)) for f in self.FIELDS + self.DETAIL_FIELDS +
+                                               ("min_pseudo_weight", "min_pseudo_frame")) + ")"
+
+
+def merge_exp_details(a, b):
+    """acg_ldpc_mc_detail_merge for shards: counters add, the smaller min_pseudo_weight wins (-1 = none; tie: the lower
+    frame), the event lists are concatenated, sorted by frame and cut to a.cap."""
+    merge_exp_results(a, b)
+    for f in ("word_frames", "bit_errors", "noncodeword_frames", "sum_syndrome_weight", "n_events"):
+        setattr(a, f, getattr(a, f) + getattr(b, f))
+    if b.min_pseudo_weight > 0 and (a.min_pseudo_weight <= 0 or (b.min_pseudo_weight, b.min_pseudo_frame) <
+                                    (a.min_pseudo_weight, a.min_pseudo_frame)):
+        a.min_pseudo_weight, a.min_pseudo_frame = b.min_pseudo_weight, b.min_pseudo_frame
+    if a.min_pseudo_weight <= 0:
+        a.min_pseudo_weight, a.min_pseudo_frame = -1, -1
+    a.n = a.n or b.n
+    ev = np.concatenate([a.events, b.events])
+    order = np.argsort(ev["frame"], kind="stable")[:a.cap]
+    if a.words is not None and b.words is not None:
+        a.words = np.concatenate([a.words, b.words])[order]
+    else:
+        a.words = None
+    a.events = ev[order]
+    a.n_stored = len(a.events)
+    return a
+
+
+def run_experiment_detail(decoder, codewords, H, snr, frames=None, first_frame=0, noise="host", seed=1, cap=0, words=False):
+    """acg_ldpc_mc_run_detail: run_experiment plus post-decoding bit errors and a log of the frames that are not correct.
+
+    cap: how many events to store — those of the cap lowest global frame indices, whatever the launch shape.
+    words=True: also return word XOR sent for every stored event.  Other arguments as run_experiment.
+    Returns an ExperimentDetail."""
+    h, code = decoder.handle(H)
+    cfg = McCfg()
+    cw = None
+    if codewords is not None:
+        cw = np.ascontiguousarray(codewords, dtype=np.uint8)
+        assert cw.ndim == 2 and cw.shape[1] == code.n
+        cfg.codewords = cw.ctypes.data
+        cfg.n_codewords = cw.shape[0]
+    if frames is None:
+        if cw is None:
+            raise ValueError("frames required without codewords")
+        frames = cw.shape[0]
+    cfg.frames = int(frames)
+    cfg.first_frame = int(first_frame)
+    cfg.snr = float(snr)
+    cfg.seed = int(seed)
+    cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
+    cap = int(cap)
+    nwords = (code.n + 31) // 32
+    ev = np.zeros(max(cap, 0), dtype=EVENT_DTYPE)
+    wd = np.zeros((max(cap, 0), nwords), dtype=np.uint32) if words else None
+    res = McDetail()
+    check(lib().acg_ldpc_mc_run_detail(h, C.byref(cfg), C.byref(res), ev.ctypes.data if cap > 0 else None,
+                                       wd.ctypes.data if (wd is not None and cap > 0) else None, cap))
+    return detail_from_struct(res, code.n, cap, ev, wd)
+
+
+def detail_from_struct(res, n, cap, events, words):
+    """ExperimentDetail of a filled _lib.McDetail and the buffers the call wrote"""
+    kw = {f: getattr(res.base, f) for f in ExperimentResult.FIELDS}
+    kw.update({f: getattr(res, f) for f in ExperimentDetail.DETAIL_FIELDS})
+    ns = int(res.n_stored)
+    return ExperimentDetail(n=n, cap=cap, events=events[:ns].copy(), words=None if words is None else words[:ns].copy(),
+                            time_sec=res.base.time_sec, kernel_ms=res.base.kernel_ms, min_pseudo_weight=res.min_pseudo_weight,
+                            min_pseudo_frame=res.min_pseudo_frame, **kw)
 
 
 def run_experiment_grid(decoder, codewords, H, snr, alphas, mus, frames=None, first_frame=0, noise="host", seed=1):

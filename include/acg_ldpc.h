@@ -232,6 +232,67 @@ int acg_ldpc_mc_run(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, acg_ldpc_
 /* merge_exp_results (experiment.h:70-78): a += b (used to combine per-GPU shards on the host) */
 void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b);
 
+/* ---- Monte-Carlo detail run: bit errors and a log of the frames that are not correct ------- */
+
+/* The classification of exp() (experiment.h:109-120) sorts a frame into correct / pseudo-codeword / everything else and keeps
+ * counters only.  The detail run extends it (build-added; the reference has no post-decoding bit error count):
+ * the frames that are not correct are split by what the decoder returned, their bit errors are counted, and the first `cap`
+ * of them are written out as events a caller can replay (device noise is keyed on the global frame index alone).
+ *
+ * A frame whose decoder returned NO word (flag false: BP ran out of iterations, bp.h:198; the QP-ADMM guard fired,
+ * qp_admm.h:112-114) contributes NOTHING to bit_errors — the reference returns an empty vector there and no word is invented
+ * for it.  bit_errors / (total * n) is therefore the bit error rate over RETURNED words: the undetected bit errors for BP
+ * (its returned words are codewords: correct or pseudo), all bit errors for QP-ADMM (which returns a word for every frame
+ * unless the guard fires).  word_frames is the denominator for a rate per returned word: bit_errors / (word_frames * n). */
+typedef struct acg_ldpc_mc_detail {
+    acg_ldpc_mc_result base;      /* field for field what acg_ldpc_mc_run returns for the same cfg (the two times aside) */
+    int64_t word_frames;          /* frames whose decoder returned a word (flag set): BP correct + pseudo; QP-ADMM all but guard */
+    int64_t bit_errors;           /* sum over word_frames of d_H(word, sent), bits >= n masked off */
+    int64_t noncodeword_frames;   /* flag set but H*word != 0 (QP-ADMM; 0 for BP, whose flag IS the zero syndrome) */
+    int64_t sum_syndrome_weight;  /* unsatisfied checks summed over noncodeword_frames */
+    int64_t n_events;             /* frames that are not correct = total - correct */
+    int64_t n_stored;             /* events written to the caller's buffers = min(n_events, cap) */
+    int64_t min_pseudo_frame;     /* lowest global frame attaining min_pseudo_weight, -1 if none */
+    int32_t min_pseudo_weight;    /* min d_H(word, sent) over pseudo frames, -1 if none.  word ^ sent is a non-zero codeword
+                                     there: an upper bound on the minimum distance of the code */
+    int32_t reserved;
+} acg_ldpc_mc_detail;
+
+/* kind of an event: the "else" branch of experiment.h:110-119 and its pseudo branch, told apart */
+enum {
+    ACG_LDPC_EVENT_PSEUDO = 1,     /* flag set, zero syndrome, word != sent (experiment.h:115-116) */
+    ACG_LDPC_EVENT_NO_WORD = 2,    /* flag false: no word was returned */
+    ACG_LDPC_EVENT_NONCODEWORD = 3 /* flag set, H*word != 0 (QP-ADMM always reports true, qp_admm.h:177) */
+};
+
+typedef struct acg_ldpc_mc_event { /* 32 bytes */
+    int64_t frame;            /* GLOBAL frame index */
+    int32_t kind;             /* ACG_LDPC_EVENT_* */
+    int32_t iters;            /* sweeps executed, as acg_ldpc_decode_batch reports them */
+    int32_t raw_errors;       /* raw-channel hard-decision errors of the frame (the reference's Hamming figure, experiment.h:25-47) */
+    int32_t bit_errors;       /* d_H(word, sent); 0 for NO_WORD */
+    int32_t syndrome_weight;  /* unsatisfied checks; 0 unless NONCODEWORD */
+    int32_t reserved;
+} acg_ldpc_mc_event;
+
+/* acg_ldpc_mc_run plus the above, for every decoder the library creates and both noise modes.
+ *   events  host, cap entries (may be NULL when cap == 0)
+ *   words   host, cap * ((n+31)/32) uint32, or NULL: row k = (returned word) XOR (sent word) of event k, packed as
+ *           acg_ldpc_decode_batch_dev packs bits; all-zero for a NO_WORD event; bits >= n are zero
+ * Deterministic: the stored events are those of the `cap` LOWEST global frame indices among the frames that are not correct,
+ * in ascending frame order, whatever the chunking, the launch shape or the order in which wavefronts finish; n_events counts
+ * all of them.  Every frame goes noise kernel -> plain decode -> classification kernel (device noise; decoders with a fused
+ * Monte-Carlo kernel do not use it here, so the call is slower than acg_ldpc_mc_run for them), or host noise -> decode ->
+ * host classification (ACG_LDPC_NOISE_HOST_MT19937).  A QP-ADMM guard decoder is not refused: every frame is a NO_WORD event.
+ * Errors (non-zero, message in acg_ldpc_last_error, nothing launched): null dec, cfg or out; cap < 0; cap > 0 with null
+ * events; a bad cfg as for acg_ldpc_mc_run. */
+int acg_ldpc_mc_run_detail(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out,
+                           acg_ldpc_mc_event *events, uint32_t *words, int64_t cap);
+/* a += b for shards, as acg_ldpc_mc_merge does for base: counters add; min_pseudo_weight is the smaller one (-1 = none is
+ * ignored, and so is the 0 of an accumulator the caller zeroed), on a tie the lower frame.  n_stored is left as it is: the caller owns the shards' event buffers (concatenate,
+ * sort by frame, cut to cap). */
+void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b);
+
 /* replaces the double loop of qpadmm_params.cpp:64-77: acg_ldpc_mc_run for n_points parameter pairs (alpha[k], mu[k]) of
  * a QP-ADMM decoder on ONE handle.  dec's own alpha and mu are ignored in this call; its max_iter, eps_stop, early_exit,
  * precision, engine and device apply.  Every point simulates the same global frames [first_frame, first_frame + frames)

@@ -10,6 +10,7 @@
 // hands a NEW H per proposal to one shared decoder (optimize_H.cpp:16-25,89-104).
 #pragma once
 
+#include <algorithm>
 #include <cassert>
 #include <cstdint>
 #include <cstdio>
@@ -79,6 +80,54 @@ public:
     acg_ldpc_decoder *handle(const TMatrix &H) {
         std::lock_guard<std::mutex> lk(mu_);
         return lookup(H)->dec;
+    }
+
+    // acg_ldpc_mc_run_detail (the classification of experiment.h:109-120, extended): the counters of a Monte-Carlo run plus
+    // the bit errors of the returned words and the first `cap` frames that are not correct, in ascending global frame order.
+    // words[k] (only when want_words) = returned word XOR sent word of events[k], (n+31)/32 packed words per row.
+    struct McDetail {
+        acg_ldpc_mc_detail d;
+        int64_t cap = 0;
+        int n = 0;
+        std::vector<acg_ldpc_mc_event> events;
+        std::vector<uint32_t> words;
+        double BER() const { return (double) d.bit_errors / ((double) d.base.total * n); }  // over returned words, see acg_ldpc.h
+    };
+    McDetail run_detail(const TMatrix &H, const acg_ldpc_mc_cfg &cfg, int64_t cap, bool want_words = false) {
+        Lease l(this, H);
+        McDetail o;
+        o.cap = cap;
+        o.n = (int) H[0].size();
+        const size_t nwords = (size_t) (o.n + 31) / 32;
+        o.events.resize((size_t) cap);
+        if (want_words) o.words.resize((size_t) cap * nwords);
+        check(acg_ldpc_mc_run_detail(l.dec(), &cfg, &o.d, cap ? o.events.data() : nullptr, want_words && cap ? o.words.data() : nullptr, cap));
+        o.events.resize((size_t) o.d.n_stored);
+        if (want_words) o.words.resize((size_t) o.d.n_stored * nwords);
+        return o;
+    }
+    // shards: acg_ldpc_mc_detail_merge for the counters; the event lists concatenated, sorted by frame, cut to a.cap
+    static void merge_details(McDetail &a, const McDetail &b) {
+        acg_ldpc_mc_detail_merge(&a.d, &b.d);
+        const size_t nwords = (size_t) (a.n + 31) / 32, na = a.events.size(), nb = b.events.size();
+        const bool w = a.words.size() == na * nwords && b.words.size() == nb * nwords;
+        std::vector<acg_ldpc_mc_event> ev(a.events);
+        ev.insert(ev.end(), b.events.begin(), b.events.end());
+        std::vector<size_t> order(ev.size());
+        for (size_t i = 0; i < order.size(); i++) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return ev[x].frame < ev[y].frame; });
+        if (order.size() > (size_t) a.cap) order.resize((size_t) a.cap);
+        std::vector<uint32_t> words;
+        a.events.clear();
+        for (size_t i : order) {
+            a.events.push_back(ev[i]);
+            if (w) {
+                const uint32_t *row = i < na ? a.words.data() + i * nwords : b.words.data() + (i - na) * nwords;
+                words.insert(words.end(), row, row + nwords);
+            }
+        }
+        a.words.swap(words);
+        a.d.n_stored = (int64_t) a.events.size();
     }
 
     size_t live_handles() const {

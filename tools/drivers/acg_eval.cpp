@@ -6,6 +6,11 @@
 //            [--gpus N]   (one decoder handle + host thread per GPU, contiguous frame ranges, counters summed)
 //            [--minsum-iters N [--ms-scale 0.75] [--layered] [--ms-f16]]   also evaluate the build-added normalised min-sum
 //                         (NOT in the reference: parity unpinned), flooding or with the layered schedule
+//            [--detail [--detail-out report_detail.csv]]   also write post-decoding bit errors and the pseudo / non-codeword
+//                         figures of every (decoder, SNR) through acg_ldpc_mc_run_detail
+//            [--events-out FILE --events-cap N]   log the N lowest frames that are not correct, one line per event
+//                         (a frame index replays the frame: device noise is keyed on it)
+//            Without these three the driver runs acg_ldpc_mc_run and its output is what it always was.
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -22,6 +27,14 @@ int main(int argc, char **argv) {
     const int64_t tests = a.integer("--tests", 10000);                     // TESTS_NUM, main.cpp:25
     std::vector<double> snrs = drv::parse_list(a.get("--snrs", "-5,-4.5,-4,-3.5,-3,-2.5,-2,-1.5,-1,-0.5,0"));  // main.cpp:27
     const int noise = std::strcmp(a.get("--noise", "host"), "device") ? ACG_LDPC_NOISE_HOST_MT19937 : ACG_LDPC_NOISE_DEVICE_PHILOX;
+    // detail run: checked before anything is loaded or launched
+    const bool want_events = a.has("--events-out") || a.has("--events-cap");
+    const bool detail = a.has("--detail") || a.has("--detail-out") || want_events;
+    const int64_t events_cap = want_events ? a.integer("--events-cap", 0) : 0;
+    if (want_events && (!a.get("--events-out") || events_cap <= 0)) {
+        std::fprintf(stderr, "acg_eval: --events-out FILE and --events-cap N (N > 0) go together\n");
+        return 2;
+    }
     acg_ldpc_code *code = nullptr;
     if (acg_ldpc_code_load_txt(hpath, &code)) drv::die("read_pcm");
     int m, n, E;
@@ -72,11 +85,32 @@ int main(int argc, char **argv) {
     std::ofstream fdata(a.get("--out", "report.csv"));
     fdata << "Method,SNR,Sigma,FER,Time,AvgHamming,AvgHammingCorrect,AvgHammingWrong" << std::endl;  // main.cpp:48
     fdata << std::fixed << std::setprecision(12);
+    std::ofstream fdetail, fevents;
+    if (detail) {
+        fdetail.open(a.get("--detail-out", "report_detail.csv"));
+        fdetail << "Method,SNR,Frames,FER,BER,WordFrames,BitErrors,Pseudo,MinPseudoWeight,MinPseudoFrame,NonCodewordFrames,AvgSyndromeWeight" << std::endl;
+        fdetail << std::fixed << std::setprecision(12);
+    }
+    if (want_events) {
+        fevents.open(a.get("--events-out"));
+        fevents << "Method,SNR,Frame,Kind,Iters,RawErrors,BitErrors,SyndromeWeight" << std::endl;
+    }
     for (double snr : snrs) std::cerr << "snr=" << snr << ": var=" << acg_ldpc_llr_variance(snr) << std::endl;
     for (auto &d : decs) {
         std::cout << "Algo: " << d.name() << std::endl;
         for (double snr : snrs) {
-            drv::McOut r = d.run(cws, n, snr, tests, noise, (uint64_t) a.integer("--seed", 1));
+            drv::McOut r;
+            if (detail) {
+                drv::DetailOut dt = d.run_detail(cws, n, snr, tests, noise, (uint64_t) a.integer("--seed", 1), events_cap);
+                r.r = dt.d.base;
+                fdetail << d.name() << "," << snr << "," << dt.d.base.total << "," << dt.fer() << "," << dt.ber(n) << "," << dt.d.word_frames
+                        << "," << dt.d.bit_errors << "," << dt.d.base.pseudo << "," << dt.d.min_pseudo_weight << ","
+                        << dt.d.min_pseudo_frame << "," << dt.d.noncodeword_frames << "," << dt.avg_syndrome_weight() << std::endl;
+                for (const acg_ldpc_mc_event &e : dt.events)
+                    fevents << d.name() << "," << snr << "," << e.frame << "," << drv::event_kind_name(e.kind) << "," << e.iters << ","
+                            << e.raw_errors << "," << e.bit_errors << "," << e.syndrome_weight << std::endl;
+            } else
+                r = d.run(cws, n, snr, tests, noise, (uint64_t) a.integer("--seed", 1));
             std::cout << "\tSNR: " << snr << ", FER: " << r.fer() << ", (time=" << r.avg_time() << "s)" << std::endl;
             std::cerr << "\t\tAverage hamming distance: " << r.mean_hamming() << std::endl;
             fdata << d.name() << "," << snr << "," << std::sqrt(acg_ldpc_llr_variance(snr)) << "," << r.fer() << ","

@@ -2,6 +2,7 @@
 // reference's main.cpp / qpadmm_params.cpp / optimize_H.cpp loops.  No decoding logic lives here.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -82,6 +83,38 @@ inline McOut run_mc(acg_ldpc_decoder *dec, const std::vector<uint8_t> &codewords
     McOut o;
     if (acg_ldpc_mc_run(dec, &cfg, &o.r)) die("acg_ldpc_mc_run");
     return o;
+}
+
+// acg_ldpc_mc_run_detail: the counters, and the stored events with their XOR rows left out (the drivers log records only)
+struct DetailOut {
+    acg_ldpc_mc_detail d;
+    std::vector<acg_ldpc_mc_event> events;
+    double fer() const { return (double) (d.base.total - d.base.correct) / (double) d.base.total; }
+    double ber(int n) const { return (double) d.bit_errors / ((double) d.base.total * (double) n); }  // over returned words (acg_ldpc.h)
+    double avg_syndrome_weight() const {
+        return (double) d.sum_syndrome_weight / (double) (d.noncodeword_frames > 1 ? d.noncodeword_frames : 1);
+    }
+};
+
+// shards -> one result: acg_ldpc_mc_detail_merge for the counters; events concatenated, sorted by frame, cut to cap
+inline DetailOut merge_details(const std::vector<DetailOut> &part, int64_t cap) {
+    DetailOut tot;
+    std::memset(&tot.d, 0, sizeof tot.d);
+    tot.d.min_pseudo_weight = -1;
+    tot.d.min_pseudo_frame = -1;
+    for (const DetailOut &p : part) {
+        acg_ldpc_mc_detail_merge(&tot.d, &p.d);
+        tot.events.insert(tot.events.end(), p.events.begin(), p.events.end());
+    }
+    std::stable_sort(tot.events.begin(), tot.events.end(),
+                     [](const acg_ldpc_mc_event &x, const acg_ldpc_mc_event &y) { return x.frame < y.frame; });
+    if ((int64_t) tot.events.size() > cap) tot.events.resize((size_t) cap);
+    tot.d.n_stored = (int64_t) tot.events.size();
+    return tot;
+}
+
+inline const char *event_kind_name(int32_t kind) {
+    return kind == ACG_LDPC_EVENT_PSEUDO ? "PSEUDO" : kind == ACG_LDPC_EVENT_NO_WORD ? "NO_WORD" : kind == ACG_LDPC_EVENT_NONCODEWORD ? "NONCODEWORD" : "?";
 }
 
 // codewords the way every reference driver makes them: G = GetOrtogonal(H) (or a G file), gen_random_codewords(G, mt19937(seed))
@@ -171,6 +204,46 @@ struct MultiGpu {
             acg_ldpc_mc_merge(&tot.r, &part[(size_t) r].r);
         }
         tot.r.time_sec = wall;  // shards run concurrently: the slowest one is the wall time
+        return tot;
+    }
+
+    // the same through acg_ldpc_mc_run_detail: every shard keeps up to cap events of its own range, merged as merge_details says
+    DetailOut run_detail(const std::vector<uint8_t> &codewords, int n, double snr, int64_t frames, int noise, uint64_t seed,
+                         int64_t cap) const {
+        const int W = (int) dec.size();
+        std::vector<DetailOut> part((size_t) W);
+        std::vector<std::string> err((size_t) W);
+        std::vector<std::thread> th;
+        for (int r = 0; r < W; r++)
+            th.emplace_back([&, r] {
+                const int64_t lo = frames * r / W, hi = frames * (r + 1) / W;
+                acg_ldpc_mc_cfg cfg;
+                std::memset(&cfg, 0, sizeof cfg);
+                cfg.frames = hi - lo;
+                cfg.first_frame = lo;
+                cfg.snr = snr;
+                cfg.seed = seed;
+                cfg.noise = noise;
+                cfg.codewords = codewords.empty() ? nullptr : codewords.data();
+                cfg.n_codewords = codewords.empty() ? 0 : (int64_t) (codewords.size() / (size_t) n);
+                DetailOut &o = part[(size_t) r];
+                o.events.resize((size_t) cap);
+                if (acg_ldpc_mc_run_detail(dec[(size_t) r], &cfg, &o.d, cap ? o.events.data() : nullptr, nullptr, cap))
+                    err[(size_t) r] = acg_ldpc_last_error();
+                else
+                    o.events.resize((size_t) o.d.n_stored);
+            });
+        for (auto &t : th) t.join();
+        double wall = 0;
+        for (int r = 0; r < W; r++) {
+            if (!err[(size_t) r].empty()) {
+                std::fprintf(stderr, "acg_ldpc_mc_run_detail (shard %d): %s\n", r, err[(size_t) r].c_str());
+                std::exit(1);
+            }
+            wall = wall > part[(size_t) r].d.base.time_sec ? wall : part[(size_t) r].d.base.time_sec;
+        }
+        DetailOut tot = merge_details(part, cap);
+        tot.d.base.time_sec = wall;
         return tot;
     }
 };
