@@ -1,0 +1,234 @@
+// The handles behind include/acg_ldpc.h and what the host files of the library share: the types a decoder handle holds, the
+// guard of the extern "C" boundary, and one declaration of every host function that one of api.hip / decode.hip / mc.hip /
+// debug.hip defines and another calls.  As with launchers.hpp, the defining file includes it too, so a definition that
+// drifts from its declaration does not compile.  Not part of the ABI.
+#pragma once
+
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+
+#include "device_mem.hpp"
+#include "launchers.hpp"
+
+namespace acg {
+
+const std::string &last_error();  // the calling thread's error text (acg_ldpc_last_error)
+
+// a describe string into the caller's buffer (cut to cap - 1 characters) -> the size a complete copy needs
+inline int32_t copy_text(const std::string &s, char *buf, int32_t cap) {
+    if (buf && cap > 0) {
+        const size_t k = std::min<size_t>(s.size(), (size_t) cap - 1);
+        std::memcpy(buf, s.data(), k);
+        buf[k] = 0;
+    }
+    return (int32_t) s.size() + 1;
+}
+
+// No C++ exception may cross the extern "C" boundary (std::bad_alloc from a vector, std::system_error from std::thread, ...):
+// every entry point that can throw runs its body through guarded() and reports an error code + message instead.
+template <class F>
+int guarded(F &&body) noexcept {
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return 12;
+    } catch (const std::exception &e) {
+        set_error(std::string("internal exception: ") + e.what());
+        return 13;
+    } catch (...) {
+        set_error("internal exception");
+        return 13;
+    }
+}
+
+// Double-buffered staging of acg_ldpc_decode_batch / _f32: while the GPU works on chunk c (H2D, kernel, D2H on stream c % 2)
+// the host threads fill the pinned buffer of chunk c + 1 and unpack chunk c - 1.
+struct HostPipe {
+    static constexpr int NBUF = 2;
+    int64_t chunk = 0;       // frames per chunk the buffers are sized for
+    size_t y_bytes = 0;      // bytes per frame of the symbol buffers
+    PinnedBuf pin_y[NBUF], pin_out[NBUF];  // out: [frames][nwords] words | [frames] sweep counts | [frames] flags of the chunk in
+    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight: one region, so the results come back in ONE device-to-host copy
+    hipStream_t stream[NBUF] = {};
+    hipEvent_t done[NBUF] = {};
+    void release() {
+        for (int b = 0; b < NBUF; b++) pin_y[b].reset(), pin_out[b].reset(), dev_y[b].reset(), dev_out[b].reset();
+        chunk = 0;
+    }
+    ~HostPipe() {
+        for (int b = 0; b < NBUF; b++) {
+            if (done[b]) (void) hipEventDestroy(done[b]);
+            if (stream[b]) (void) hipStreamDestroy(stream[b]);
+        }
+    }
+};
+
+// Workspace of the streamed engine as separately created physical chunks mapped into one virtual range in a shuffled order
+// (HIP virtual-memory-management API).  Why: see decoder_setup_streamed — a physically CONTIGUOUS backing of the slabs is the
+// slow mode of bp_streamed_ring_kernel on slabs beyond the Infinity Cache (181 ms against 158 ms per launch on configs[4]),
+// and plain hipMalloc hands out either kind depending on the allocation history of the process.
+// Move-only owner; adopt() makes it the owner of one plain allocation instead (the small-workspace and fallback path).
+struct ScatteredAlloc {
+    void *va = nullptr;
+    size_t bytes = 0, chunk = 0;
+    std::vector<hipMemGenericAllocationHandle_t> handles;
+    std::vector<char> mapped;
+    bool plain = false;  // va is ONE allocation (adopt), released by hipFree
+    ScatteredAlloc() = default;
+    ScatteredAlloc(ScatteredAlloc &&o) noexcept { *this = std::move(o); }
+    ScatteredAlloc &operator=(ScatteredAlloc &&o) noexcept {
+        release();
+        va = o.va, bytes = o.bytes, chunk = o.chunk;
+        handles = std::move(o.handles), mapped = std::move(o.mapped), plain = o.plain;
+        o.va = nullptr;
+        return *this;
+    }
+    ~ScatteredAlloc() { release(); }
+    void adopt(void *p, size_t n) {
+        release();
+        va = p, bytes = n, plain = true;
+    }
+    void release() {
+        if (!va) return;
+        if (plain) {
+            (void) hipFree(va);
+            va = nullptr, plain = false;
+            return;
+        }
+        for (size_t i = 0; i < handles.size(); i++) {
+            if (mapped[i]) (void) hipMemUnmap((char *) va + i * chunk, chunk);
+        }
+        for (auto &h : handles) (void) hipMemRelease(h);
+        (void) hipMemAddressFree(va, bytes);
+        va = nullptr;
+        handles.clear();
+        mapped.clear();
+    }
+    // -> true on success (va usable, read/write from `dev`)
+    // spread > 1: `spread` times as many physical chunks are created and only every spread-th is kept (the others are released
+    // again at once), so the kept ones are spaced out over a `spread` times larger part of the device memory
+    bool create(size_t want, size_t chunk_bytes, int dev, bool shuffle, int spread = 1);  // api.hip
+};
+
+}  // namespace acg
+
+struct acg_ldpc_code {
+    acg::Code c;
+};
+
+struct acg_ldpc_decoder {
+    acg::Code c;  // private copy: the handle outlives the code object safely
+    acg_ldpc_params p;
+    int device = 0;
+    int cu_count = 256;
+    hipStream_t stream = nullptr;
+    bool own_stream = true;  // false: the stream is an evaluator's (acg_ldpc_mc_run_codes, per-code path) and outlives the handle
+    bool ev_valid = false;
+    std::recursive_mutex mu;  // (recursive: acg_ldpc_mc_run_grid holds it across the per-point runs of its sequential path)
+    std::string name;
+    // BP
+    acg::BpLayout lay;
+    acg::BpTables tab{};
+    std::vector<acg::DeviceBuf> dev_allocs;  // the device copies of the tables below
+    int maxd = 0, f64 = 0, L = 64;
+    int block = 256, frames_per_block = 0;
+    int grid_cap[2] = {0, 0};          // [mc] resident blocks: occupancy x CUs
+    const void *kernel[2] = {nullptr, nullptr};
+    size_t lds_block = 0;
+    int variant = -1;       // wave-group kernels: 0 / 1 / 2 (see bp_inst_*.hip); -1 = workgroup-per-frame
+    bool phi_memo = false;  // DecodeArgs::phi_memo (the SAT instances read it)
+    // the SAT instances' freeze of latched frames whose state recurs (bp_fused_body): one snapshot slot per resident frame
+    // group behind a small head with the debug counter (DecodeArgs::freeze_ws), allocated at the first launch
+    bool freeze = false;
+    bool freeze_count = false;  // acg_ldpc_debug_freeze_stats asked for the counter
+    int freeze_first = 0, freeze_period = 0;
+    size_t freeze_slot_words = 0;
+    acg::DeviceBuf freeze_ws;
+    bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
+    bool blk_idxlds = false, blk_idxreg = false;
+    // layered min-sum (bp_layered.hip)
+    bool layered = false;
+    acg::LayeredLayout llay;
+    acg::LayerTables ltab{};
+    // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory
+    bool layered_block = false;
+    acg::LayeredBlockLayout lblay;
+    acg::LayerBlockTables lbtab{};
+    acg::DeviceBuf lb_step, lb_pos;
+    // streamed BP engine
+    bool streamed = false;
+    acg::StreamTables stab{};
+    const void *skernel = nullptr;
+    const void *sring = nullptr;  // LDS-DMA ring variant (fp32), null = not available for this code
+    int sring_per_cu = 2;
+    bool sring_nt = false;  // ring instance with non-temporal slab accesses (slabs beyond the Infinity Cache)
+    acg::ScatteredAlloc sws;  // the slabs: shuffled physical chunks, or one plain allocation
+    std::vector<float> sws_probe_ms;  // probe time of every workspace candidate that was tried (the fastest was kept)
+    int sws_spread = 1;               // the kept physical chunks are every sws_spread-th of those created
+    int sgrid = 0;
+    // ADMM
+    struct AdmmDrop { void operator()(acg::AdmmDevice *a) const { acg::admm_device_destroy(a); } };
+    std::unique_ptr<acg::AdmmDevice, AdmmDrop> admm;
+    // staging for the host API (ensure_staging)
+    acg::DeviceBuf st_y, st_bits, st_ok, st_iters;
+    std::unique_ptr<acg::HostPipe> pipe;  // pipelined staging of the host-buffer entry points (created on first use)
+    // MC through engines without an in-kernel generator (streamed): chunk buffers
+    acg::DeviceBuf mc_y;
+    // MC
+    acg::DeviceBuf cw_dev;
+    int64_t cw_count = 0;
+    uint64_t cw_hash = 0;
+    acg::DeviceBuf counters;
+    // detail run (acg_ldpc_mc_run_detail), allocated by its first call: DET_NCOUNTERS counters, one kind byte per frame of a
+    // chunk with its pinned copy, the chunk-relative frames selected as events, their records and XOR rows
+    acg::DeviceBuf det_counters, det_kind, det_sel, det_events, det_words;
+    acg::PinnedBuf det_kind_h, det_sel_h, det_counters_h;
+    // parameter grid (acg_ldpc_mc_run_grid): counters[point][MC_NCOUNTERS] and the per-point tables of the chunk in flight
+    acg::DeviceBuf grid_counters, grid_tab;
+    // Per-launch work counters: every launch takes the next slot of a small ring of device words (the dynamic frame /
+    // tile hand-out of the kernels), so launches of one handle that overlap on different streams never share one.
+    // ring_ev[k] is recorded behind the launch that used slot k; the next user of the slot — and, for the streamed
+    // engine, whose HBM slabs belong to the handle, every launch on a different stream — waits on it on the device.
+    // Timing: every launch also owns the (start, stop) event pair of its slot, so two launches of one handle in flight on
+    // two streams never pair each other's events; ring_ev[k] IS the stop event of slot k.
+    static constexpr int WORK_RING = 32;
+    acg::DeviceBuf work_ring;
+    hipEvent_t ring_ev0[WORK_RING] = {};
+    hipEvent_t ring_ev[WORK_RING] = {};
+    bool ring_used[WORK_RING] = {};
+    uint64_t launch_seq = 0;
+    int last_slot = -1;
+    hipStream_t last_stream = nullptr;
+
+    unsigned long long *counters_dev() const { return counters.as<unsigned long long>(); }
+    unsigned long long *work_counter(int slot) const { return work_ring.as<unsigned long long>() + slot; }
+};
+
+namespace acg {
+
+// owned until handed out: an exception or an error releases the streams, events and device memory made so far
+struct DecoderDrop { void operator()(acg_ldpc_decoder *x) const { acg_ldpc_decoder_destroy(x); } };
+using DecoderPtr = std::unique_ptr<acg_ldpc_decoder, DecoderDrop>;
+
+// ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own) ----
+int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
+                                 hipStream_t on_stream = nullptr);
+
+// ---- decode.hip ----
+double channel_sigma(double snr);
+void fill_channel(DecodeArgs &a, double snr);
+int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s);
+int ensure_staging(acg_ldpc_decoder *d, int64_t frames);
+void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a);
+DecodeArgs decode_args(const void *y, int y_is_f64, int64_t frames, double snr);
+struct Chunk {  // one decode on the handle's stream: its arguments and its event slot
+    DecodeArgs a;
+    int slot;
+};
+int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c);
+float chunk_ms(const acg_ldpc_decoder *d, const Chunk &c);
+
+}  // namespace acg

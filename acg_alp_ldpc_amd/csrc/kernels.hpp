@@ -76,7 +76,7 @@ struct DecodeArgs {
 constexpr int FREEZE_WS_HEAD = 4;
 constexpr int FREEZE_STATS_SHIFT = 40;
 
-// One code of a batch (acg_ldpc_mc_run_codes) as the classification and symbol kernels of bp_kernels.hip see it
+// One code of a batch (acg_ldpc_mc_run_codes) as the classification and symbol kernels of mc_kernels.hip see it
 struct CodeRef {
     const uint32_t *cw_packed;     // n_cw * nwords sent words of THIS code, null = the all-zero word
     int64_t n_cw;

@@ -30,12 +30,10 @@ hipError_t bp_launch(const void *kernel, const BpTables &t, const DecodeArgs &a,
                      hipStream_t s);
 hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s);
 hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s);
+
+// ---- mc_kernels.hip ----
 hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,
                        const uint32_t *cw_packed, int64_t n_cw, float sigma, hipStream_t s);
-hipError_t classify_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
-                           int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
-                           unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
-                           hipStream_t s);
 // detail run (acg_ldpc_mc_run_detail): counters = DET_NCOUNTERS words, kind = one byte per frame of the chunk
 hipError_t classify_detail_launch(const float *y, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames,
                                   int n, int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw,
@@ -45,6 +43,7 @@ hipError_t gather_events_launch(const int32_t *sel, int n_sel, const float *y, c
                                 const int32_t *iters, const uint8_t *kind, int n, int nwords, int64_t first_frame,
                                 const uint32_t *cw_packed, int64_t n_cw, const int32_t *row_ptr, const int32_t *edge_var, int m,
                                 acg_ldpc_mc_event *events, uint32_t *words, hipStream_t s);
+// classification of units x frames virtual frames: the codes of a batch; the points of a grid (one point: acg_ldpc_mc_run)
 hipError_t classify_codes_launch(const void *y, int y_is_f64, const uint32_t *bits, const uint8_t *ok, const int32_t *iters,
                                  int64_t frames, int64_t codes, int n, int nwords, int64_t first_frame, const CodeRef *refs, int m,
                                  hipStream_t s);

@@ -1,0 +1,971 @@
+// C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo.  acg_ldpc_mc_run, the detail run, the QP-ADMM
+// parameter grid, the evaluator of a batch of codes, and the generators (device AWGN, host codewords and transmit).
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+
+#include "handle.hpp"
+
+using namespace acg;
+
+extern "C" {
+
+// ---------------------------------------------------------------- Monte-Carlo
+static int check_mc_cfg(const acg_ldpc_mc_cfg *cfg) {
+    if (!(cfg->frames < 0 || (cfg->codewords && cfg->n_codewords <= 0))) return 0;
+    set_error("bad mc cfg");
+    return 1;
+}
+
+// one byte per bit -> packed words, ORed into out[n_codewords][(n + 31) / 32] (the caller zeroes it)
+static void pack_codewords(const uint8_t *codewords, int64_t n_codewords, int n, uint32_t *out) {
+    const int nwords = (n + 31) / 32;
+    for (int64_t f = 0; f < n_codewords; f++)
+        for (int v = 0; v < n; v++)
+            if (codewords[(size_t) f * n + v]) out[(size_t) f * nwords + (v >> 5)] |= 1u << (v & 31);
+}
+
+static int ensure_codewords(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg) {
+    if (!cfg->codewords || cfg->n_codewords <= 0) return 0;
+    // the device copy is keyed on the CONTENT of the host array (a pointer can be recycled for different words)
+    // (hashed 8 bytes at a time in four independent lanes: the byte-wise loop took 2.5 ms for 8192 x 280 codewords — more than
+    // an early-exit launch over a million frames — on every Monte-Carlo call)
+    uint64_t h = 1469598103934665603ull;
+    {
+        const uint8_t *pb = cfg->codewords;
+        const size_t nb = (size_t) cfg->n_codewords * (size_t) d->c.n;
+        uint64_t hl[4] = {h, h ^ 0x9E3779B97F4A7C15ull, h ^ 0xC2B2AE3D27D4EB4Full, h ^ 0x165667B19E3779F9ull};
+        size_t i = 0;
+        for (; i + 32 <= nb; i += 32)
+            for (int k = 0; k < 4; k++) {
+                uint64_t w;
+                std::memcpy(&w, pb + i + 8 * k, 8);
+                // any non-zero byte means bit 1 (the reference reads '1' cells, others are 0): normalise every byte to 0 / 1
+                w |= w >> 4;
+                w |= w >> 2;
+                w |= w >> 1;
+                w &= 0x0101010101010101ull;
+                hl[k] = (hl[k] ^ w) * 1099511628211ull;
+                hl[k] ^= hl[k] >> 29;
+            }
+        for (; i < nb; i++) hl[0] = (hl[0] ^ (uint64_t) (pb[i] != 0)) * 1099511628211ull;
+        h = ((hl[0] * 31 + hl[1]) * 31 + hl[2]) * 31 + hl[3];
+    }
+    if (d->cw_dev.p && d->cw_hash == h && d->cw_count == cfg->n_codewords) return 0;
+    d->cw_dev.reset();  // (hipFree waits for the device: no launch still reads the old words when the new ones are copied)
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    std::vector<uint32_t> packed((size_t) cfg->n_codewords * nwords, 0u);
+    pack_codewords(cfg->codewords, cfg->n_codewords, n, packed.data());
+    if (int rc = d->cw_dev.reserve(packed.size() * sizeof(uint32_t))) return rc;
+    HIP_OK(hipMemcpy(d->cw_dev.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    d->cw_hash = h;
+    d->cw_count = cfg->n_codewords;
+    return 0;
+}
+
+// the sent words as the kernels take them: (packed device copy, count), or (null, 1) for the all-zero word
+struct SentWords {
+    const uint32_t *dev;
+    int64_t n;
+};
+static SentWords sent_words(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg) {
+    if (!cfg->codewords) return {nullptr, 1};
+    return {d->cw_dev.as<uint32_t>(), cfg->n_codewords};
+}
+
+static void counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *r) {
+    r->correct = (int64_t) c[MC_CORRECT];
+    r->pseudo = (int64_t) c[MC_PSEUDO];
+    r->total = (int64_t) c[MC_TOTAL];
+    r->sum_hamming = (int64_t) c[MC_HAM];
+    r->sum_hamming_ok = (int64_t) c[MC_HAM_OK];
+    r->sum_hamming_wrong = (int64_t) c[MC_HAM_WRONG];
+    r->sum_iters = (int64_t) c[MC_ITERS];
+}
+
+// The noise of experiment.h:90-99 (single-threaded order): frame g (0-based global index) is seeded mt19937(g+1) and draws its
+// n deviates from libstdc++ normal_distribution(0, sigma) in index order (channel.h:18-26)
+static void noise_host(int n, int64_t first, int64_t fc, double snr, double *out) {
+    const double sigma = channel_sigma(snr);
+    for (int64_t f = 0; f < fc; f++) {
+        std::mt19937 rnd((uint32_t) (first + f + 1));
+        std::normal_distribution<double> dst(0, sigma);
+        for (int i = 0; i < n; i++) out[(size_t) f * n + i] = dst(rnd);
+    }
+}
+
+// Bit-exact transmit of experiment.h:90-99: that noise, and per symbol the single IEEE addition (+-1.0) + deviate
+// (channel.h:24); codewords == null sends the all-zero word
+static void transmit_host(const uint8_t *codewords, int64_t n_codewords, int n, int64_t first_frame, int64_t frames, double snr,
+                          double *y) {
+    noise_host(n, first_frame, frames, snr, y);
+    for (int64_t f = 0; f < frames; f++) {
+        const uint8_t *cw = codewords ? codewords + (size_t) ((first_frame + f) % n_codewords) * n : nullptr;
+        for (int i = 0; i < n; i++) y[(size_t) f * n + i] = ((cw && cw[i]) ? -1.0 : 1.0) + y[(size_t) f * n + i];
+    }
+}
+
+void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
+    // merge_exp_results, experiment.h:70-78
+    a->correct += b->correct;
+    a->pseudo += b->pseudo;
+    a->total += b->total;
+    a->sum_hamming += b->sum_hamming;
+    a->sum_hamming_ok += b->sum_hamming_ok;
+    a->sum_hamming_wrong += b->sum_hamming_wrong;
+    a->sum_iters += b->sum_iters;
+    a->time_sec += b->time_sec;
+    a->kernel_ms += b->kernel_ms;
+}
+
+// ACG_MC_DETAIL_CHUNK=<frames>: developer / test switch that lowers the chunk of a detail run (README, developer variables)
+static int64_t mc_detail_chunk(int64_t chunk) {
+    const char *e = getenv("ACG_MC_DETAIL_CHUNK");
+    const int64_t v = e ? atoll(e) : 0;
+    return v > 0 ? std::min(chunk, v) : chunk;
+}
+
+// where a detail run (acg_ldpc_mc_run_detail) collects what goes beyond the seven counters
+struct DetailSink {
+    acg_ldpc_mc_detail *out;
+    acg_ldpc_mc_event *events;
+    uint32_t *words;
+    int64_t cap;
+};
+
+// a pseudo frame of weight w >= 1: the running minimum keeps the lowest frame among equal weights (a weight <= 0 in *o means
+// "none yet": -1 as the API reports it, or 0 in an accumulator the caller zeroed)
+static void detail_min_pseudo(acg_ldpc_mc_detail *o, int32_t w, int64_t frame) {
+    if (o->min_pseudo_weight <= 0 || w < o->min_pseudo_weight || (w == o->min_pseudo_weight && frame < o->min_pseudo_frame)) {
+        o->min_pseudo_weight = w;
+        o->min_pseudo_frame = frame;
+    }
+}
+
+static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res, DetailSink *ds = nullptr) {
+    // Bit-exact experiment.h:80-123: transmit_host, decoded on the device, classified on the host.
+    const int n = d->c.n;
+    const int64_t chunk_max = ds ? mc_detail_chunk(1 << 16) : 1 << 16;
+    std::vector<double> y;
+    std::vector<uint8_t> bits, ok;
+    std::vector<int32_t> iters;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk_max) {
+        const int64_t fc = std::min(chunk_max, cfg->frames - f0);
+        y.resize((size_t) fc * n);
+        bits.resize((size_t) fc * n);
+        ok.resize((size_t) fc);
+        iters.resize((size_t) fc);
+        transmit_host(cfg->codewords, cfg->n_codewords, n, cfg->first_frame + f0, fc, cfg->snr, y.data());
+        if (int rc = acg_ldpc_decode_batch(d, y.data(), fc, cfg->snr, bits.data(), ok.data(), iters.data())) return rc;
+        res->kernel_ms += acg_ldpc_decoder_last_kernel_ms(d);
+        for (int64_t f = 0; f < fc; f++) {
+            const int64_t gidx = cfg->first_frame + f0 + f;
+            const uint8_t *cw = cfg->codewords ? cfg->codewords + (size_t) (gidx % cfg->n_codewords) * n : nullptr;
+            const uint8_t *b = &bits[(size_t) f * n];
+            bool is_correct = false, is_pseudo = false;
+            if (ok[f] && code_is_codeword(d->c, b)) {  // experiment.h:110-111
+                bool eq = true;
+                for (int i = 0; i < n; i++) eq &= (b[i] == (cw ? cw[i] : 0));
+                if (eq) {
+                    res->correct++;
+                    is_correct = true;
+                } else {
+                    res->pseudo++;
+                    is_pseudo = true;
+                }
+            }
+            res->total++;
+            int h = 0;
+            for (int i = 0; i < n; i++) {
+                const bool c1 = cw && cw[i];
+                const double yv = y[(size_t) f * n + i];
+                if (!c1 && yv <= 0) h++;
+                if (c1 && yv > 0) h++;
+            }
+            res->sum_hamming += h;
+            if (is_correct) res->sum_hamming_ok += h;
+            else res->sum_hamming_wrong += h;
+            res->sum_iters += iters[f];
+            if (ds) {   // the detail run's extension of experiment.h:109-120
+                acg_ldpc_mc_detail *o = ds->out;
+                int dist = 0, synw = 0;
+                if (ok[f]) {
+                    o->word_frames++;
+                    for (int i = 0; i < n; i++) dist += (b[i] != 0) != (cw && cw[i]);
+                    o->bit_errors += dist;
+                    if (!is_correct && !is_pseudo) {
+                        for (int c = 0; c < d->c.m; c++) {
+                            int sy = 0;
+                            for (int e = d->c.row_ptr[c]; e < d->c.row_ptr[c + 1]; e++) sy ^= b[d->c.edge_var[e]] != 0;
+                            synw += sy;
+                        }
+                        o->noncodeword_frames++;
+                        o->sum_syndrome_weight += synw;
+                    }
+                }
+                if (is_pseudo) detail_min_pseudo(o, dist, gidx);
+                if (!is_correct && o->n_stored < ds->cap) {
+                    const int64_t k = o->n_stored++;
+                    acg_ldpc_mc_event &ev = ds->events[k];
+                    ev.frame = gidx;
+                    ev.kind = is_pseudo ? ACG_LDPC_EVENT_PSEUDO : ok[f] ? ACG_LDPC_EVENT_NONCODEWORD : ACG_LDPC_EVENT_NO_WORD;
+                    ev.iters = iters[f];
+                    ev.raw_errors = h;
+                    ev.bit_errors = dist;
+                    ev.syndrome_weight = synw;
+                    ev.reserved = 0;
+                    if (ds->words) {
+                        const int nwords = (n + 31) / 32;
+                        uint32_t *row = ds->words + (size_t) k * nwords;
+                        std::fill(row, row + nwords, 0u);
+                        if (ok[f])
+                            for (int i = 0; i < n; i++)
+                                if ((b[i] != 0) != (cw && cw[i])) row[i >> 5] |= 1u << (i & 31);
+                    }
+                }
+            }
+        }
+    }
+    return 0;
+}
+
+static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
+    if (!d || !cfg || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    std::memset(res, 0, sizeof(*res));
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = 0;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
+        rc = mc_run_host_noise(d, cfg, res);
+    } else if (d->streamed || d->pair || d->layered_block || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
+        // AWGN kernel -> decode -> classify kernel, in bounded chunks, all on the device.  Used by the streamed BP
+        // engine and the workgroup-per-frame layered engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
+        // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
+        const int32_t *csr_row = nullptr, *csr_col = nullptr;
+        if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
+        HIP_OK(hipSetDevice(d->device));
+        if ((rc = ensure_codewords(d, cfg))) return rc;
+        const int n = d->c.n, nwords = (n + 31) / 32;
+        int64_t chunk = std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4)));
+        if ((rc = d->mc_y.reserve((size_t) chunk * n * sizeof(float)))) return rc;
+        if ((rc = ensure_staging(d, std::min<int64_t>(chunk, std::max<int64_t>(cfg->frames, 1))))) return rc;
+        HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+        const SentWords cw = sent_words(d, cfg);
+        float *mc_y = d->mc_y.as<float>();
+        float kms = 0;
+        for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+            const int64_t fc = std::min(chunk, cfg->frames - f0);
+            HIP_OK(awgn_launch(mc_y, fc, n, nwords, cfg->first_frame + f0, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
+            Chunk c;
+            if ((rc = decode_chunk(d, mc_y, 0, fc, cfg->snr, c))) return rc;
+            HIP_OK(classify_grid_launch(mc_y, 0, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, 1, n, nwords, cfg->first_frame + f0, cw.dev,
+                                        cw.n, d->counters_dev(), csr_row, csr_col, d->c.m, d->stream));
+            HIP_OK(hipStreamSynchronize(d->stream));
+            kms += chunk_ms(d, c);
+        }
+        unsigned long long h[MC_NCOUNTERS];
+        HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
+        counters_to_result(h, res);
+        res->kernel_ms = kms;
+    } else {
+        std::lock_guard<std::recursive_mutex> lk(d->mu);
+        HIP_OK(hipSetDevice(d->device));
+        if ((rc = ensure_codewords(d, cfg))) return rc;
+        HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+        DecodeArgs a = decode_args(nullptr, 0, cfg->frames, cfg->snr);
+        a.mc = 1;
+        a.seed = cfg->seed;
+        a.first_frame = cfg->first_frame;
+        a.cw_packed = sent_words(d, cfg).dev;
+        a.n_cw = sent_words(d, cfg).n;
+        a.counters = d->counters_dev();
+        if ((rc = launch_decode(d, a, d->stream))) return rc;
+        const int slot = d->last_slot;   // this launch's own event pair (d->mu is held)
+        unsigned long long h[MC_NCOUNTERS];
+        HIP_OK(hipMemcpyAsync(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        counters_to_result(h, res);
+        float ms = 0;
+        if (cfg->frames > 0 && slot >= 0 && hipEventElapsedTime(&ms, d->ring_ev0[slot], d->ring_ev[slot]) == hipSuccess) res->kernel_ms = ms;
+    }
+    res->time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int acg_ldpc_mc_run(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_impl(d, cfg, res); });
+}
+
+// ---------------------------------------------------------------- Monte-Carlo detail run
+// Device noise: per chunk AWGN kernel -> plain decode (launch_decode with a.y set: every engine has it) -> classify_detail_kernel,
+// the chunks of the unfused branch of acg_ldpc_mc_run.  Events: the kernel leaves one kind byte per frame; while fewer than
+// cap events are stored the host reads those bytes, takes the lowest non-correct frames of the chunk, and gather_events_kernel
+// writes their records and XOR rows from the chunk's still-resident symbols and outputs.  Chunks run in ascending frame
+// order, so the stored events are the cap lowest frames whatever the chunk size.  Caller holds nothing; d->mu is taken here.
+static int mc_run_detail_device(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, DetailSink &ds) {
+    acg_ldpc_mc_detail *o = ds.out;
+    const int32_t *csr_row = nullptr, *csr_col = nullptr;
+    if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    int rc = 0;
+    if ((rc = ensure_codewords(d, cfg))) return rc;
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    const int64_t chunk = mc_detail_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4))));
+    const size_t fcap = (size_t) chunk;
+    if ((rc = d->mc_y.reserve(fcap * n * sizeof(float)))) return rc;
+    if ((rc = d->st_bits.reserve(fcap * nwords * sizeof(uint32_t)))) return rc;
+    if ((rc = d->st_ok.reserve(fcap))) return rc;
+    if ((rc = d->st_iters.reserve(fcap * sizeof(int32_t)))) return rc;
+    if ((rc = d->det_counters.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
+    if ((rc = d->det_counters_h.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
+    if ((rc = d->det_kind.reserve(fcap))) return rc;
+    if (ds.cap > 0) {
+        const size_t ecap = (size_t) std::min<int64_t>(ds.cap, chunk);   // events one chunk can add
+        if ((rc = d->det_kind_h.reserve(fcap))) return rc;
+        if ((rc = d->det_sel.reserve(ecap * sizeof(int32_t)))) return rc;
+        if ((rc = d->det_sel_h.reserve(ecap * sizeof(int32_t)))) return rc;
+        if ((rc = d->det_events.reserve(ecap * sizeof(acg_ldpc_mc_event)))) return rc;
+        if (ds.words && (rc = d->det_words.reserve(ecap * nwords * sizeof(uint32_t)))) return rc;
+    }
+    unsigned long long *cnt = d->det_counters.as<unsigned long long>(), *cnt_h = d->det_counters_h.as<unsigned long long>();
+    HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DET_NCOUNTERS, d->stream));
+    const SentWords cw = sent_words(d, cfg);
+    float *mc_y = d->mc_y.as<float>();
+    uint8_t *kind = d->det_kind.as<uint8_t>();
+    float kms = 0;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+        HIP_OK(hipMemsetAsync(cnt + DET_MIN_PSEUDO, 0xFF, sizeof(unsigned long long), d->stream));
+        HIP_OK(awgn_launch(mc_y, fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
+        Chunk c;
+        if ((rc = decode_chunk(d, mc_y, 0, fc, cfg->snr, c))) return rc;
+        const DecodeArgs &a = c.a;
+        HIP_OK(classify_detail_launch(mc_y, a.out_bits, a.out_ok, a.out_iters, fc, n, nwords, first, cw.dev, cw.n, cnt, kind, csr_row,
+                                      csr_col, d->c.m, d->stream));
+        const bool want_events = o->n_stored < ds.cap;
+        if (want_events) HIP_OK(hipMemcpyAsync(d->det_kind_h.p, kind, (size_t) fc, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipMemcpyAsync(cnt_h, cnt, sizeof(unsigned long long) * DET_NCOUNTERS, hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        kms += chunk_ms(d, c);
+        if (cnt_h[DET_MIN_PSEUDO] != ~0ull)
+            detail_min_pseudo(o, (int32_t) (cnt_h[DET_MIN_PSEUDO] >> 32), first + (int64_t) (cnt_h[DET_MIN_PSEUDO] & 0xFFFFFFFFull));
+        if (want_events) {
+            const uint8_t *kh = d->det_kind_h.as<uint8_t>();
+            int32_t *sel = d->det_sel_h.as<int32_t>();
+            const int64_t room = ds.cap - o->n_stored;
+            int n_sel = 0;
+            for (int64_t f = 0; f < fc && n_sel < room; f++)
+                if (kh[f]) sel[n_sel++] = (int32_t) f;
+            if (n_sel > 0) {
+                HIP_OK(hipMemcpyAsync(d->det_sel.p, sel, (size_t) n_sel * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(gather_events_launch(d->det_sel.as<int32_t>(), n_sel, mc_y, a.out_bits, a.out_ok, a.out_iters, kind, n, nwords, first,
+                                            cw.dev, cw.n, csr_row, csr_col, d->c.m, d->det_events.as<acg_ldpc_mc_event>(),
+                                            ds.words ? d->det_words.as<uint32_t>() : nullptr, d->stream));
+                HIP_OK(hipMemcpyAsync(ds.events + o->n_stored, d->det_events.p, (size_t) n_sel * sizeof(acg_ldpc_mc_event),
+                                      hipMemcpyDeviceToHost, d->stream));
+                if (ds.words)
+                    HIP_OK(hipMemcpyAsync(ds.words + (size_t) o->n_stored * nwords, d->det_words.p, (size_t) n_sel * nwords * sizeof(uint32_t),
+                                          hipMemcpyDeviceToHost, d->stream));
+                HIP_OK(hipStreamSynchronize(d->stream));
+                o->n_stored += n_sel;
+            }
+        }
+    }
+    if (cfg->frames > 0) {
+        counters_to_result(cnt_h, &o->base);
+        o->word_frames = (int64_t) cnt_h[DET_WORD_FRAMES];
+        o->bit_errors = (int64_t) cnt_h[DET_BIT_ERRORS];
+        o->noncodeword_frames = (int64_t) cnt_h[DET_NONCODEWORD];
+        o->sum_syndrome_weight = (int64_t) cnt_h[DET_SYNDROME];
+    }
+    o->base.kernel_ms = kms;
+    return 0;
+}
+
+static int acg_ldpc_mc_run_detail_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out,
+                                       acg_ldpc_mc_event *events, uint32_t *words, int64_t cap) {
+    if (!d || !cfg || !out) {
+        set_error("null argument");
+        return 1;
+    }
+    if (cap < 0 || (cap > 0 && !events)) {
+        set_error("acg_ldpc_mc_run_detail: cap must be >= 0, and events non-null when cap > 0");
+        return 1;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    std::memset(out, 0, sizeof(*out));
+    out->min_pseudo_weight = -1;
+    out->min_pseudo_frame = -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    DetailSink ds{out, events, words, cap};
+    int rc = 0;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) rc = mc_run_host_noise(d, cfg, &out->base, &ds);
+    else rc = mc_run_detail_device(d, cfg, ds);
+    out->n_events = out->base.total - out->base.correct;
+    out->base.time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int acg_ldpc_mc_run_detail(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out, acg_ldpc_mc_event *events,
+                           uint32_t *words, int64_t cap) {
+    return guarded([&] { return acg_ldpc_mc_run_detail_impl(d, cfg, out, events, words, cap); });
+}
+
+void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b) {
+    acg_ldpc_mc_merge(&a->base, &b->base);
+    a->word_frames += b->word_frames;
+    a->bit_errors += b->bit_errors;
+    a->noncodeword_frames += b->noncodeword_frames;
+    a->sum_syndrome_weight += b->sum_syndrome_weight;
+    a->n_events += b->n_events;
+    if (b->min_pseudo_weight > 0) detail_min_pseudo(a, b->min_pseudo_weight, b->min_pseudo_frame);
+    if (a->min_pseudo_weight <= 0) a->min_pseudo_weight = -1, a->min_pseudo_frame = -1;
+}
+
+// ---------------------------------------------------------------- Monte-Carlo over a QP-ADMM parameter grid
+// virtual frames (points x frames) one launch of the grid path covers, and so the size of its per-frame outputs: the
+// staging of a 65536-frame decode.  ACG_MC_GRID_BUDGET: developer / test override (README, developer variables).
+static int64_t mc_grid_budget() {
+    const char *e = getenv("ACG_MC_GRID_BUDGET");
+    const int64_t v = e ? atoll(e) : 0;
+    return v > 0 ? std::min<int64_t>(v, (int64_t) 1 << 30) : 65536;
+}
+
+// channel symbols of global frames [first, first + fc) into d->st_y: doubles from mt19937 (experiment.h:90-99, as
+// mc_run_host_noise) or floats from the device generator (as the unfused path of acg_ldpc_mc_run).  Caller holds d->mu.
+static int mc_grid_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, std::vector<double> &yh) {
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
+        yh.resize((size_t) fc * n);
+        transmit_host(cfg->codewords, cfg->n_codewords, n, first, fc, cfg->snr, yh.data());
+        HIP_OK(hipMemcpyAsync(d->st_y.p, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
+    } else {
+        const SentWords cw = sent_words(d, cfg);
+        HIP_OK(awgn_launch(d->st_y.as<float>(), fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
+    }
+    return 0;
+}
+
+static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
+                                     int32_t n_points, acg_ldpc_mc_result *res) {
+    if (!d || !cfg) {
+        set_error("null argument");
+        return 1;
+    }
+    if (!d->admm) {
+        set_error("acg_ldpc_mc_run_grid needs a QP-ADMM decoder");
+        return 1;
+    }
+    if (n_points < 1) {
+        set_error("acg_ldpc_mc_run_grid: n_points must be >= 1");
+        return 1;
+    }
+    if (!alpha || !mu || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::memset(res, 0, sizeof(*res) * (size_t) n_points);
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    const double e_min = admm_device_e_min(d->admm.get());
+    std::vector<int32_t> run;  // the points that decode; the others are guard points (qp_admm.h:108-114)
+    for (int32_t k = 0; k < n_points; k++)
+        if (!(e_min * mu[k] <= alpha[k])) run.push_back(k);
+    const int64_t n_run = (int64_t) run.size();
+    const bool any_guard = n_run < n_points;
+    const bool single_launch = admm_device_has_grid_kernel(d->admm.get());
+    int rc = 0;
+    if (cfg->frames > 0 && (any_guard || (single_launch && n_run > 0))) {
+        if ((rc = ensure_codewords(d, cfg))) return rc;
+        const int n = d->c.n, nwords = (n + 31) / 32;
+        const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+        const int32_t *csr_row = nullptr, *csr_col = nullptr;
+        (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
+        const SentWords cw = sent_words(d, cfg);
+        // frames in blocks of fb, points in chunks of npc: one launch covers npc * fb <= budget virtual frames (or one
+        // point's fb frames); its outputs use the handle's staging buffers
+        const int64_t budget = mc_grid_budget();
+        const int64_t fb = std::min<int64_t>(cfg->frames, budget);
+        const int64_t npc = single_launch ? std::max<int64_t>(1, std::min<int64_t>(budget / fb, std::max<int64_t>(n_run, 1))) : 1;
+        if ((rc = ensure_staging(d, npc * fb))) return rc;
+        // counters: row j < n_run = point run[j], row n_run = every guard point
+        const size_t counter_bytes = (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long);
+        if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
+        unsigned long long *counters = d->grid_counters.as<unsigned long long>();
+        HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
+        std::vector<double> yh, ca, cm;
+        std::vector<unsigned char> pt, inv;
+        for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
+            const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
+            if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
+            if (any_guard)
+                HIP_OK(classify_grid_launch(d->st_y.p, host, nullptr, nullptr, nullptr, fc, 1, n, nwords, first, cw.dev, cw.n,
+                                            counters + (size_t) n_run * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+            for (int64_t c0 = 0; single_launch && c0 < n_run; c0 += npc) {
+                const int64_t np = std::min(npc, n_run - c0);
+                ca.resize((size_t) np);
+                cm.resize((size_t) np);
+                for (int64_t j = 0; j < np; j++) {
+                    ca[(size_t) j] = alpha[run[(size_t) (c0 + j)]];
+                    cm[(size_t) j] = mu[run[(size_t) (c0 + j)]];
+                }
+                admm_grid_tables(d->admm.get(), ca.data(), cm.data(), (int) np, pt, inv);
+                const size_t pt_bytes = (pt.size() + 255) & ~(size_t) 255;
+                if ((rc = d->grid_tab.reserve(pt_bytes + inv.size()))) return rc;
+                unsigned char *tab = d->grid_tab.as<unsigned char>();
+                // (the stream is idle here: the previous chunk ended with a synchronisation, so pt / inv may be rewritten)
+                HIP_OK(hipMemcpyAsync(tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
+                HIP_OK(hipMemcpyAsync(tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
+                Chunk c;
+                admm_grid_bind(d->admm.get(), tab, tab + pt_bytes, (uint32_t) fc);
+                rc = decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c);
+                admm_grid_bind(d->admm.get(), nullptr, nullptr, 0);
+                if (rc) return rc;
+                HIP_OK(classify_grid_launch(d->st_y.p, host, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
+                                            counters + (size_t) c0 * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
+                HIP_OK(hipStreamSynchronize(d->stream));
+                const float ms = chunk_ms(d, c);
+                for (int64_t j = 0; j < np; j++) res[run[(size_t) (c0 + j)]].kernel_ms += (double) ms / (double) np;
+            }
+            HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
+        }
+        std::vector<unsigned long long> h((size_t) (n_run + 1) * MC_NCOUNTERS);
+        HIP_OK(hipMemcpy(h.data(), counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        std::vector<char> is_run((size_t) n_points, 0);
+        for (int64_t j = 0; j < n_run; j++) {
+            is_run[(size_t) run[(size_t) j]] = 1;
+            if (single_launch) counters_to_result(&h[(size_t) j * MC_NCOUNTERS], &res[run[(size_t) j]]);
+        }
+        for (int32_t k = 0; k < n_points; k++)
+            if (!is_run[(size_t) k]) counters_to_result(&h[(size_t) n_run * MC_NCOUNTERS], &res[k]);
+    }
+    if (!single_launch && n_run > 0) {
+        // one point after another on this handle: acg_ldpc_mc_run with the handle re-parameterised in place
+        HIP_OK(hipStreamSynchronize(d->stream));
+        const double alpha0 = d->p.alpha, mu0 = d->p.mu;
+        std::string err;
+        for (int64_t j = 0; j < n_run && !rc; j++) {
+            const int32_t k = run[(size_t) j];
+            if (!admm_device_set_point(d->admm.get(), alpha[k], mu[k], err)) {
+                set_error(err);
+                rc = 10;
+                break;
+            }
+            rc = acg_ldpc_mc_run_impl(d, cfg, &res[k]);  // (synchronises the stream before it returns)
+        }
+        const std::string first_err = rc ? last_error() : std::string();
+        if (!admm_device_set_point(d->admm.get(), alpha0, mu0, err) && !rc) {
+            set_error(err);
+            rc = 10;
+        } else if (rc) {
+            set_error(first_err);
+        }
+    }
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int32_t k = 0; k < n_points; k++) res[k].time_sec = wall;
+    return rc;
+}
+
+int acg_ldpc_mc_run_grid(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu, int32_t n_points,
+                         acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_grid_impl(d, cfg, alpha, mu, n_points, res); });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- Monte-Carlo over a batch of parity-check matrices
+// The local search of optimize_H.cpp:89-104 scores a fresh H per proposal.  An evaluator scores a batch of them in one
+// call: the codes that the workgroup-per-frame QP-ADMM kernel accepts decode in ONE launch per launch shape (codes
+// instance of admm_block_kernel, virtual frame g = code * frames + f), with their tables in one device buffer written by
+// one copy; nothing is allocated, created or destroyed per code.
+struct acg_ldpc_evaluator {
+    acg_ldpc_params p;
+    int device = 0;
+    int cu_count = 256;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the decode launch of the chunk in flight
+    mutable std::mutex mu;  // (mutable: acg_ldpc_evaluator_describe reads `last` under it)
+    static constexpr int WORK_RING = 32;  // per-launch work counters, as acg_ldpc_decoder::work_ring
+    DeviceBuf work_ring;
+    uint64_t launch_seq = 0;
+    DeviceBuf st_y, st_bits, st_ok, st_iters;  // symbols [code][frame][n] and decode outputs of the chunk in flight
+    DeviceBuf noise;     // host-noise mode: the deviates [frame][n] of the frame block in flight, shared by every code
+    PinnedBuf pin_tab;   // host image of tab
+    DeviceBuf tab;       // the chunk in flight: AdmmDevTables[codes] | CodeRef[codes] | per code: its tables, its sent words
+    DeviceBuf counters;  // [codes of the call][MC_NCOUNTERS]
+    std::string last = "qpadmm mc_codes=none";  // what the last run did (acg_ldpc_evaluator_describe)
+};
+
+static int acg_ldpc_evaluator_create_impl(const acg_ldpc_params *params, acg_ldpc_evaluator **out) {
+    if (!params || !out) {
+        set_error("null argument");
+        return 1;
+    }
+    if (params->algo != ACG_LDPC_QPADMM) {
+        set_error("acg_ldpc_evaluator_create needs QP-ADMM parameters");
+        return 1;
+    }
+    if (params->max_iter < 0) {
+        set_error("max_iter must be >= 0");
+        return 1;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device available: libacg_ldpc_hip has no CPU fallback");
+        return 20;
+    }
+    int dev = params->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (dev >= ndev) {
+        set_error("device ordinal out of range");
+        return 1;
+    }
+    struct Drop { void operator()(acg_ldpc_evaluator *x) const { acg_ldpc_evaluator_destroy(x); } };
+    std::unique_ptr<acg_ldpc_evaluator, Drop> own(new acg_ldpc_evaluator());
+    acg_ldpc_evaluator *ev = own.get();
+    ev->p = *params;
+    ev->p.fast_setup = 1;  // (the contract: every code as on a decoder created with fast_setup = 1)
+    ev->device = dev;
+    HIP_OK(hipSetDevice(dev));
+    hipDeviceProp_t prop;
+    HIP_OK(hipGetDeviceProperties(&prop, dev));
+    ev->cu_count = prop.multiProcessorCount;
+    HIP_OK(hipStreamCreateWithFlags(&ev->stream, hipStreamNonBlocking));
+    HIP_OK(hipEventCreate(&ev->ev0));
+    HIP_OK(hipEventCreate(&ev->ev1));
+    if (int rc = ev->work_ring.reserve(sizeof(unsigned long long) * acg_ldpc_evaluator::WORK_RING)) return rc;
+    *out = own.release();
+    return 0;
+}
+
+static int acg_ldpc_mc_run_codes_impl(acg_ldpc_evaluator *ev, const acg_ldpc_code *const *codes, int32_t n_codes,
+                                      const acg_ldpc_mc_cfg *cfgs, acg_ldpc_mc_result *res) {
+    if (n_codes < 1) {
+        set_error("acg_ldpc_mc_run_codes: n_codes must be >= 1");
+        return 1;
+    }
+    if (!ev || !codes || !cfgs || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    for (int32_t k = 0; k < n_codes; k++) {
+        if (!codes[k]) {
+            set_error("null argument");
+            return 1;
+        }
+        if (codes[k]->c.m != codes[0]->c.m || codes[k]->c.n != codes[0]->c.n) {
+            set_error("acg_ldpc_mc_run_codes: codes of different m or n");
+            return 1;
+        }
+        if (check_mc_cfg(&cfgs[k])) return 1;
+        if (cfgs[k].frames != cfgs[0].frames || cfgs[k].first_frame != cfgs[0].first_frame || !(cfgs[k].snr == cfgs[0].snr) ||
+            cfgs[k].seed != cfgs[0].seed || cfgs[k].noise != cfgs[0].noise) {
+            set_error("acg_ldpc_mc_run_codes: frames, first_frame, snr, seed and noise must be equal in every cfg");
+            return 1;
+        }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::memset(res, 0, sizeof(*res) * (size_t) n_codes);
+    std::lock_guard<std::mutex> lk(ev->mu);
+    HIP_OK(hipSetDevice(ev->device));
+    const acg_ldpc_params &p = ev->p;
+    const acg_ldpc_mc_cfg &cfg = cfgs[0];
+    const int n = codes[0]->c.n, m = codes[0]->c.m, nwords = (n + 31) / 32;
+    const int host = cfg.noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+    // parameters whose decoder handle runs the workgroup-per-frame kernel on the codes that kernel accepts
+    const bool eligible = p.engine != ACG_LDPC_ENGINE_STREAMED && (p.lanes_per_frame == 0 || p.lanes_per_frame == 256) && p.max_iter > 0 &&
+                          p.precision != ACG_LDPC_PREC_F16;
+    struct Item {
+        int32_t k;
+        std::unique_ptr<AdmmDevice, acg_ldpc_decoder::AdmmDrop> plan;
+        std::vector<unsigned char> blob;
+    };
+    std::vector<Item> items;                 // the codes that decode in shared launches
+    std::vector<int32_t> guard, per_code;    // guard codes (qp_admm.h:108-114); codes that take a decoder handle of their own
+    for (int32_t k = 0; k < n_codes && cfg.frames > 0; k++) {
+        const Code &c = codes[k]->c;
+        double e_min = 1e9;
+        for (double e : c.admm.e) e_min = std::min(e_min, e);
+        if (e_min * p.mu <= p.alpha) {
+            guard.push_back(k);
+            continue;
+        }
+        Item it;
+        it.k = k;
+        std::string why;
+        if (eligible) it.plan.reset(admm_codes_plan(c, p, it.blob, why));
+        if (it.plan) items.push_back(std::move(it));
+        else per_code.push_back(k);
+    }
+    // launch groups: the codes of one launch shape, in the order given; group -1 = the guard codes (classified, never decoded)
+    std::vector<std::pair<int, std::vector<const Item *>>> groups;
+    for (const Item &it : items) {
+        const int shape = admm_codes_shape(it.plan.get());
+        size_t g = 0;
+        while (g < groups.size() && groups[g].first != shape) g++;
+        if (g == groups.size()) groups.push_back({shape, {}});
+        groups[g].second.push_back(&it);
+    }
+    const int n_groups = (int) groups.size();
+    std::vector<Item> guard_items(guard.size());
+    if (!guard.empty()) {
+        groups.push_back({-1, {}});
+        for (size_t j = 0; j < guard.size(); j++) {
+            guard_items[j].k = guard[j];
+            groups.back().second.push_back(&guard_items[j]);
+        }
+    }
+    int rc = 0, n_chunks = 0;
+    if (!groups.empty()) {
+        const int64_t budget = mc_grid_budget();
+        const int64_t fb = std::min<int64_t>(cfg.frames, budget);
+        const size_t counter_bytes = (size_t) n_codes * MC_NCOUNTERS * sizeof(unsigned long long);
+        if ((rc = ev->counters.reserve(counter_bytes))) return rc;
+        unsigned long long *counters = ev->counters.as<unsigned long long>();
+        HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, ev->stream));
+        const size_t TB = admm_codes_tables_bytes();
+        auto up = [](size_t x) { return (x + 255) & ~(size_t) 255; };
+        // (one block is kept: with frames <= budget — the search's 1000 — it is drawn and uploaded once per call.  With more
+        // frames than the budget a chunk is one code and every code redraws the blocks: correct, and not the case this serves)
+        std::vector<double> nz;          // host noise of the frame block [nz_first, nz_first + nz_fc)
+        int64_t nz_first = -1, nz_fc = 0;
+        bool nz_on_device = false;
+        std::vector<size_t> blob_off, cw_off;
+        for (const auto &grp : groups) {
+            const bool decode = grp.first >= 0;
+            const int64_t n_grp = (int64_t) grp.second.size();
+            const int64_t npc = std::max<int64_t>(1, std::min<int64_t>(budget / fb, n_grp));
+            for (int64_t c0 = 0; c0 < n_grp; c0 += npc) {
+                const int64_t np = std::min(npc, n_grp - c0);
+                const Item *const *chunk = grp.second.data() + c0;
+                // ---- the chunk's tables: one host image, one copy (the stream is idle here: every chunk ends with a synchronisation)
+                size_t total = up((size_t) np * TB) + up((size_t) np * sizeof(CodeRef)), lds = 0;
+                blob_off.assign((size_t) np, 0);
+                cw_off.assign((size_t) np, 0);
+                for (int64_t j = 0; j < np; j++) {
+                    const acg_ldpc_mc_cfg &cj = cfgs[chunk[j]->k];
+                    blob_off[(size_t) j] = total;
+                    total += up(chunk[j]->blob.size());
+                    cw_off[(size_t) j] = total;
+                    if (cj.codewords) total += up((size_t) cj.n_codewords * nwords * sizeof(uint32_t));
+                    if (decode) lds = std::max(lds, admm_codes_lds(chunk[j]->plan.get()));
+                }
+                if ((rc = ev->tab.reserve(total)) || (rc = ev->pin_tab.reserve(total))) return rc;
+                unsigned char *hp = ev->pin_tab.as<unsigned char>(), *dp = ev->tab.as<unsigned char>();
+                std::memset(hp, 0, total);
+                CodeRef *refs_h = reinterpret_cast<CodeRef *>(hp + up((size_t) np * TB));
+                const CodeRef *refs = reinterpret_cast<const CodeRef *>(dp + up((size_t) np * TB));
+                for (int64_t j = 0; j < np; j++) {
+                    const Item &it = *chunk[j];
+                    const acg_ldpc_mc_cfg &cj = cfgs[it.k];
+                    CodeRef &r = refs_h[j];
+                    r.cw_packed = nullptr;
+                    r.n_cw = 1;
+                    r.row_ptr = r.edge_var = nullptr;
+                    r.counters = counters + (size_t) it.k * MC_NCOUNTERS;
+                    if (decode) {
+                        std::memcpy(hp + blob_off[(size_t) j], it.blob.data(), it.blob.size());
+                        admm_codes_tables(it.plan.get(), (uintptr_t) (dp + blob_off[(size_t) j]), hp + (size_t) j * TB);
+                        size_t rp = 0, evr = 0;
+                        admm_codes_csr(it.plan.get(), &rp, &evr);
+                        r.row_ptr = reinterpret_cast<const int32_t *>(dp + blob_off[(size_t) j] + rp);
+                        r.edge_var = reinterpret_cast<const int32_t *>(dp + blob_off[(size_t) j] + evr);
+                    }
+                    if (cj.codewords) {
+                        pack_codewords(cj.codewords, cj.n_codewords, n, reinterpret_cast<uint32_t *>(hp + cw_off[(size_t) j]));
+                        r.cw_packed = reinterpret_cast<const uint32_t *>(dp + cw_off[(size_t) j]);
+                        r.n_cw = cj.n_codewords;
+                    }
+                }
+                HIP_OK(hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, ev->stream));
+                int grid_cap = 0;
+                if (decode) {
+                    std::string why;
+                    grid_cap = admm_codes_grid_cap(chunk[0]->plan.get(), lds, ev->cu_count, why);
+                    if (grid_cap <= 0) {
+                        set_error(why);
+                        return 10;
+                    }
+                    n_chunks++;
+                }
+                const size_t vf = (size_t) (np * fb);
+                if ((rc = ev->st_y.reserve(vf * n * (host ? sizeof(double) : sizeof(float))))) return rc;
+                if (decode && ((rc = ev->st_bits.reserve(vf * nwords * sizeof(uint32_t))) || (rc = ev->st_ok.reserve(vf)) ||
+                               (rc = ev->st_iters.reserve(vf * sizeof(int32_t)))))
+                    return rc;
+                for (int64_t f0 = 0; f0 < cfg.frames; f0 += fb) {
+                    const int64_t fc = std::min(fb, cfg.frames - f0), first = cfg.first_frame + f0;
+                    // ---- symbols [code][frame][n]: one noise block serves every code
+                    if (host) {
+                        if (nz_first != first || nz_fc != fc) {
+                            nz.resize((size_t) fc * n);
+                            noise_host(n, first, fc, cfg.snr, nz.data());
+                            nz_first = first;
+                            nz_fc = fc;
+                            nz_on_device = false;
+                        }
+                        if (!nz_on_device) {
+                            if ((rc = ev->noise.reserve(nz.size() * sizeof(double)))) return rc;
+                            HIP_OK(hipMemcpyAsync(ev->noise.p, nz.data(), nz.size() * sizeof(double), hipMemcpyHostToDevice, ev->stream));
+                            nz_on_device = true;
+                        }
+                        HIP_OK(codes_symbols_launch(ev->noise.as<double>(), ev->st_y.as<double>(), fc, np, n, nwords, first, refs, ev->stream));
+                    } else {
+                        for (int64_t j = 0; j < np; j++)
+                            HIP_OK(awgn_launch(ev->st_y.as<float>() + (size_t) j * fc * n, fc, n, nwords, first, cfg.seed, refs_h[j].cw_packed,
+                                               refs_h[j].n_cw, (float) channel_sigma(cfg.snr), ev->stream));
+                    }
+                    if (!decode) {
+                        HIP_OK(classify_codes_launch(ev->st_y.p, host, nullptr, nullptr, nullptr, fc, np, n, nwords, first, refs, m, ev->stream));
+                        HIP_OK(hipStreamSynchronize(ev->stream));
+                        continue;
+                    }
+                    DecodeArgs a = decode_args(ev->st_y.p, host, np * fc, cfg.snr);
+                    a.out_bits = ev->st_bits.as<uint32_t>();
+                    a.out_ok = ev->st_ok.as<uint8_t>();
+                    a.out_iters = ev->st_iters.as<int32_t>();
+                    a.max_iter = p.max_iter;
+                    a.early_exit = p.early_exit;
+                    a.ms_scale = (float) p.ms_scale;
+                    a.work_counter = ev->work_ring.as<unsigned long long>() + (ev->launch_seq++ % acg_ldpc_evaluator::WORK_RING);
+                    HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), ev->stream));
+                    HIP_OK(hipEventRecord(ev->ev0, ev->stream));
+                    HIP_OK(admm_codes_launch(chunk[0]->plan.get(), dp, (uint32_t) fc, lds, grid_cap, a, ev->stream));
+                    HIP_OK(hipEventRecord(ev->ev1, ev->stream));
+                    HIP_OK(classify_codes_launch(ev->st_y.p, host, a.out_bits, a.out_ok, a.out_iters, fc, np, n, nwords, first, refs, m, ev->stream));
+                    HIP_OK(hipStreamSynchronize(ev->stream));
+                    float ms = 0;
+                    if (hipEventElapsedTime(&ms, ev->ev0, ev->ev1) == hipSuccess)
+                        for (int64_t j = 0; j < np; j++) res[chunk[j]->k].kernel_ms += (double) ms / (double) np;
+                }
+            }
+        }
+        std::vector<unsigned long long> h((size_t) n_codes * MC_NCOUNTERS);
+        HIP_OK(hipMemcpy(h.data(), counters, counter_bytes, hipMemcpyDeviceToHost));
+        for (const auto &grp : groups)
+            for (const Item *it : grp.second) {
+                const double kms = res[it->k].kernel_ms;
+                counters_to_result(&h[(size_t) it->k * MC_NCOUNTERS], &res[it->k]);
+                res[it->k].kernel_ms = kms;
+            }
+    }
+    // codes the shared launches do not take: a decoder handle of their own, on this evaluator's stream
+    for (size_t j = 0; j < per_code.size() && !rc; j++) {
+        const int32_t k = per_code[j];
+        acg_ldpc_decoder *d = nullptr;
+        if ((rc = acg_ldpc_decoder_create_impl(codes[k], &p, &d, ev->stream))) break;
+        rc = acg_ldpc_mc_run_impl(d, &cfgs[k], &res[k]);
+        const std::string keep = rc ? last_error() : std::string();
+        acg_ldpc_decoder_destroy(d);
+        if (rc) set_error(keep);
+    }
+    char b[256];
+    if (n_groups > 0 || (eligible && per_code.empty()))
+        snprintf(b, sizeof b, "qpadmm mc_codes=single-launch groups=%d chunks=%d codes=%d guard=%d per_code=%d", n_groups, n_chunks, (int) n_codes,
+                 (int) guard.size(), (int) per_code.size());
+    else
+        snprintf(b, sizeof b, "qpadmm mc_codes=per-code codes=%d guard=%d per_code=%d", (int) n_codes, (int) guard.size(), (int) per_code.size());
+    ev->last = b;
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int32_t k = 0; k < n_codes; k++) res[k].time_sec = wall;
+    return rc;
+}
+
+extern "C" {
+
+int acg_ldpc_evaluator_create(const acg_ldpc_params *params, acg_ldpc_evaluator **out) {
+    return guarded([&] { return acg_ldpc_evaluator_create_impl(params, out); });
+}
+
+void acg_ldpc_evaluator_destroy(acg_ldpc_evaluator *ev) {
+    if (!ev) return;
+    (void) hipSetDevice(ev->device);
+    if (ev->stream) (void) hipStreamSynchronize(ev->stream);
+    if (ev->ev0) (void) hipEventDestroy(ev->ev0);
+    if (ev->ev1) (void) hipEventDestroy(ev->ev1);
+    if (ev->stream) (void) hipStreamDestroy(ev->stream);
+    delete ev;  // (the buffers belong to its members)
+}
+
+int acg_ldpc_mc_run_codes(acg_ldpc_evaluator *ev, const acg_ldpc_code *const *codes, int32_t n_codes, const acg_ldpc_mc_cfg *cfgs,
+                          acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_codes_impl(ev, codes, n_codes, cfgs, res); });
+}
+
+int32_t acg_ldpc_evaluator_describe(const acg_ldpc_evaluator *ev, char *buf, int32_t cap) {
+    if (!ev) return 0;
+    std::string s;
+    {
+        std::lock_guard<std::mutex> lk(ev->mu);  // (a run on another thread writes it)
+        s = ev->last;
+    }
+    return copy_text(s, buf, cap);
+}
+
+static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
+    if (!d || !cfg || !y_dev) {
+        set_error("null argument");
+        return 1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    if (int rc = ensure_codewords(d, cfg)) return rc;
+    const SentWords cw = sent_words(d, cfg);
+    HIP_OK(awgn_launch(y_dev, cfg->frames, d->c.n, (d->c.n + 31) / 32, cfg->first_frame, cfg->seed, cw.dev, cw.n,
+                       (float) channel_sigma(cfg->snr), stream ? (hipStream_t) stream : d->stream));
+    return 0;
+}
+
+int acg_ldpc_awgn_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
+    return guarded([&] { return acg_ldpc_awgn_dev_impl(d, cfg, y_dev, stream); });
+}
+
+// ---------------------------------------------------------------- host generators
+static int acg_ldpc_gen_codewords_impl(const uint8_t *G, int32_t k, int32_t n, uint32_t seed, int64_t count, uint8_t *out) {
+    if (!G || !out || k <= 0 || n <= 0 || count < 0) {
+        set_error("bad argument");
+        return 1;
+    }
+    std::mt19937 rnd(seed);  // main.cpp:63
+    for (int64_t f = 0; f < count; f++) {
+        uint8_t *res = out + (size_t) f * n;
+        std::memset(res, 0, (size_t) n);
+        for (int i = 0; i < k; i++)
+            if (rnd() % 2 == 0) {  // channel.h:33
+                const uint8_t *row = G + (size_t) i * n;
+                for (int j = 0; j < n; j++) res[j] ^= (row[j] ? 1 : 0);
+            }
+    }
+    return 0;
+}
+
+int acg_ldpc_gen_codewords(const uint8_t *G, int32_t k, int32_t n, uint32_t seed, int64_t count, uint8_t *out) {
+    return guarded([&] { return acg_ldpc_gen_codewords_impl(G, k, n, seed, count, out); });
+}
+
+static int acg_ldpc_transmit_host_impl(const uint8_t *codewords, int64_t n_codewords, int32_t n, int64_t first_frame,
+                           int64_t frames, double snr, double *y) {
+    if (!y || n <= 0 || frames < 0 || (codewords && n_codewords <= 0)) {
+        set_error("bad argument");
+        return 1;
+    }
+    transmit_host(codewords, n_codewords, n, first_frame, frames, snr, y);
+    return 0;
+}
+
+int acg_ldpc_transmit_host(const uint8_t *codewords, int64_t n_codewords, int32_t n, int64_t first_frame,
+                           int64_t frames, double snr, double *y) {
+    return guarded([&] { return acg_ldpc_transmit_host_impl(codewords, n_codewords, n, first_frame, frames, snr, y); });
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-"""numpy restatement of the device AWGN generator (Philox4x32-10 + Box-Muller; awgn_kernel in bp_kernels.hip and its in-kernel
+"""numpy restatement of the device AWGN generator (Philox4x32-10 + Box-Muller; awgn_kernel in mc_kernels.hip and its in-kernel
 copies in bp_core.inc, bp_block.hip, bp_layered.hip and admm_kernels.hip) and of the Monte-Carlo classification.
 
 Every step up to the three transcendental instructions is an integer or IEEE fp32 operation and is reproduced bit for bit: the

@@ -9,7 +9,7 @@ kernels), csrc/bp_streamed.hip (StreamPass) and csrc/bp_pair.hip (pair_check / p
   storage type T    float32 / float64 (bp_core.inc, bp_streamed.hip), float16 (bp_pair.hip)
   domain            every LLR-domain quantity times Dom<T>::scale: log2(e) for float32, 1 for float64 and float16
   channel LLR       double symbols  T(2 * y / var * scale), left to right in double   (float16: half(float(2 * y / var)))
-                    float symbols   T(double(y) * (inv_var2 * scale)), inv_var2 = 2.0 / var as api.hip fill_channel forms it
+                    float symbols   T(double(y) * (inv_var2 * scale)), inv_var2 = 2.0 / var as decode.hip fill_channel forms it
                                     (float16: half(float(double(y) * inv_var2)))
   message word      sign | magnitude with its LSB cleared | LSB = posterior hard decision of the sending variable
   first sweep       every outgoing word of a variable is |llr| (LSB cleared), sign = hard = (llr <= 0)
@@ -39,7 +39,7 @@ _UINT = {np.dtype(np.float16): np.uint16, np.dtype(np.float32): np.uint32, np.dt
 
 
 def llr_variance(snr):
-    return 10.0 ** (-(snr / 10.0)) / 2.0        # channel.h:12; api.hip fill_channel
+    return 10.0 ** (-(snr / 10.0)) / 2.0        # channel.h:12; decode.hip fill_channel
 
 
 def channel_llr(y, snr, dtype):

@@ -2,7 +2,6 @@
 acg_ldpc_awgn_dev (device noise) or acg_ldpc_transmit_host (host noise), decoded through decode_batch_dev / decode_batch on
 the same decoder parameters, classified by the numpy restatement tests/mc_detail_ref.py.  Every field of the struct except
 the two times, every event and every bit of the XOR rows must be equal."""
-import ctypes as C
 import os
 import sys
 
@@ -13,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA = os.path.join(ROOT, "data")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mc_detail_ref as R  # noqa: E402
+from mc_decode_path import decode_device_noise, sent_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -52,41 +52,6 @@ def _chunk_env():
     chunked(300)
     yield
     chunked(None)
-
-
-def sent_words(cws, n, first, frames):
-    if cws is None:
-        return np.zeros((frames, n), dtype=np.uint8)
-    return cws[(first + np.arange(frames, dtype=np.int64)) % len(cws)]
-
-
-def mc_cfg(A, cws, snr, frames, first, seed, noise):
-    from acg_alp_ldpc_amd import _lib
-    cfg = _lib.McCfg()
-    cfg.frames, cfg.first_frame, cfg.snr, cfg.seed = frames, first, snr, seed
-    cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
-    if cws is not None:
-        cfg.codewords, cfg.n_codewords = cws.ctypes.data, cws.shape[0]
-    return cfg
-
-
-def decode_device_noise(A, dec, H, cws, snr, frames, first, seed):
-    """(y, packed words, ok, iters) of global frames [first, first + frames): awgn_dev + decode_batch_dev"""
-    import torch
-    from acg_alp_ldpc_amd._lib import check, lib
-    h, _ = dec.handle(H)
-    nw = (H.n + 31) // 32
-    y = torch.empty((max(frames, 1), H.n), dtype=torch.float32, device="cuda")
-    bits = torch.zeros((max(frames, 1), nw), dtype=torch.int32, device="cuda")
-    ok = torch.zeros(max(frames, 1), dtype=torch.uint8, device="cuda")
-    it = torch.zeros(max(frames, 1), dtype=torch.int32, device="cuda")
-    if frames:
-        cfg = mc_cfg(A, cws, snr, frames, first, seed, "device")
-        check(lib().acg_ldpc_awgn_dev(h, C.byref(cfg), y.data_ptr(), None))
-        dec.sync(H)
-        dec.decode_batch_dev(H, y.data_ptr(), False, frames, snr, bits.data_ptr(), ok.data_ptr(), it.data_ptr())
-        dec.sync(H)
-    return (y.cpu().numpy()[:frames], bits.cpu().numpy().view(np.uint32)[:frames], ok.cpu().numpy()[:frames], it.cpu().numpy()[:frames])
 
 
 def expectation(A, dec, H, Hd, cws, snr, frames, first, seed, noise, cap):
