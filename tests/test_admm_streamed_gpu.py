@@ -68,7 +68,7 @@ def test_large_code_decodes_through_the_default_engine(A, oracle, ref, big):
         bits, ok, _ = f32.decode_batch(H, y, snr)
         same += int((bits == words[snr]).all(axis=1).sum())
     f32.close()
-    assert same >= 22, same
+    assert same >= 22, same   # (fp32 against fp64; fp32 against its own restatement: tests/test_admm_f32_exact_gpu.py)
 
 
 @pytest.mark.parametrize("name", MATS)

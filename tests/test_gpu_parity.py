@@ -289,7 +289,8 @@ def test_qpadmm_mixed_check_degrees_and_long_lists(A, oracle):
 
 
 def test_qpadmm_fp32_fer_only(A, oracle, matrices, pcm):
-    """fp32 QP-ADMM: FER-level agreement only (the 1/(mu*e-alpha)=20x gain amplifies rounding)"""
+    """fp32 QP-ADMM: FER-level agreement only (the 1/(mu*e-alpha)=20x gain amplifies rounding)
+    (against the fp64 oracle; tests/test_admm_f32_exact_gpu.py holds the fp32 kernels to their float32 restatement, frame by frame)"""
     from acg_alp_ldpc_amd import _lib
     Hm, H = matrices["optimalH"], pcm["optimalH"]
     G, _ = oracle.get_orthogonal(Hm)
