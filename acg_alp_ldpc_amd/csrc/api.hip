@@ -757,7 +757,12 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     // sweeps executed; ACG_BP_NO_FREEZE=1 runs them all (A/B runs).  The cadence is in sweeps behind the latch: the first
     // snapshot, then a compare (and a new snapshot) every `period` (tools/freeze_census.cpp, profiles/r09_freeze_summary.md).
     d->freeze = sat && algo == 0 && !d->f64 && d->maxd <= 8 && idxlds && llr_regs && getenv("ACG_BP_NO_FREEZE") == nullptr;
-    d->freeze_first = 10;  // measured best on the headline among 3 ... 12 / 1 ... 4 (profiles/r09_freeze_summary.md)
+    // a detection loads the snapshot and compares only where the lanes' checksums of their words allow a recurrence, and
+    // otherwise only writes the new one; ACG_BP_FREEZE_NO_GATE=1 loads and compares at every detection behind a group's first
+    d->freeze_gate = getenv("ACG_BP_FREEZE_NO_GATE") == nullptr;
+    // measured best on the headline among 3 ... 12 / 1 ... 4 (profiles/r09_freeze_summary.md), and again with the gate among
+    // 1 ... 12 / 1 ... 4 (profiles/r12_freeze_gate_summary.md)
+    d->freeze_first = 10;
     d->freeze_period = 1;
     if (const char *e = getenv("ACG_BP_FREEZE_CADENCE")) {  // "first,period" (tuning runs)
         int f = 0, q = 0;
@@ -926,7 +931,8 @@ static std::string describe(const acg_ldpc_decoder *d) {
         if (d->variant >= 0 && !d->layered && !d->pair && !d->p.early_exit) {
             // fixed-work decoders: whether latched frames whose state recurs stop sweeping, and on which cadence
             std::string t = b;
-            if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period);
+            if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period) +
+                                    " freeze_gate=" + (d->freeze_gate ? "1" : "0");
             else t += " freeze=0";
             return t;
         }

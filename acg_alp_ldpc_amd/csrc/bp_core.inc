@@ -1008,6 +1008,8 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     // fz = 0 until the frame latches (it takes the place of `latched` in these instances), then
     //      sweeps until the next detection << 2 | the slot holds a snapshot taken since the latch << 1 | 1.
     int fz = 0;
+    // the gate in front of the compare: the sum of this lane's words at the snapshot in the slot (valid while fz & 2)
+    typename Core::U fc = 0;
     int ham = 0;  // raw-channel errors of the current frame (MC)
     // per-group MC accumulators (flushed once at the end)
     unsigned int acc_correct = 0, acc_pseudo = 0, acc_total = 0;
@@ -1266,8 +1268,8 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                 fz -= cand ? 4 : 0;
                 const bool due = cand && fz < 4 && it + 1 < a.max_iter;  // (nothing left to save behind the last sweep)
                 if (__ballot(due) != 0ull) {
-                    // moved: a word differs from the snapshot, or there is none to compare with (or the group is not due)
-                    typename Core::U moved = (due && (fz & 2)) ? 0 : 1;
+                    // moved: a word differs from the snapshot, or the group did not compare (or is not due)
+                    typename Core::U moved = 1;
                     if (due) {
                         // the slot's address is formed here, from values the compiler cannot trace back to the loop-invariant
                         // thread and block ids: hoisted out of the sweep loop it would hold registers the sweeps need
@@ -1275,26 +1277,72 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                         asm volatile("" : "+v"(tid), "+s"(bid));
                         const uint32_t slot = bid * (blockDim.x / L) + tid / L;  // (the host keeps the workspace below 2^31 words)
                         uint32_t *snap = a.freeze_ws + FREEZE_WS_HEAD + (size_t) (slot * (uint32_t) (t.a_words + Core::NAP * L));
+                        const int lo = (int) (tid % L);  // (= l, as opaque as the address; no trip-count set-up to hoist)
+                        // A pass costs what it issues, not what it moves (profiles/r12_freeze_gate_summary.md), so every pass goes
+                        // over the state four words at a time: a lane owns the quads lo, lo + L, ... of the message array (a_words
+                        // is a multiple of 4, frames and slots start on 16 bytes) and its own absorbed words.
+                        static_assert(sizeof(T) == 4 && sizeof(typename Core::U) == 4, "the freeze passes read the message array as uint4");
+                        const uint4 *A4 = reinterpret_cast<const uint4 *>(A);
+                        uint4 *snap4 = reinterpret_cast<uint4 *>(snap);
+                        const int nq = t.a_words >> 2;
+                        // the gate: the sum of the words this lane would compare, read from LDS alone.  Equal states have equal
+                        // sums, so a lane whose sum differs from the one it took at the previous snapshot proves that the state
+                        // moved, and the group then only writes the new snapshot: no load, no wait for one.
+                        typename Core::U cs = 0;
+                        if (!(a.freeze_cfg & FREEZE_CFG_NO_GATE)) {
 #pragma unroll 1
-                        for (int w = (int) (tid % L); w < t.a_words; w += 4 * L) {  // (tid % L = l, as opaque as the address; no trip-count set-up to hoist)
-                            typename Core::U cur[4], old[4];
+                            for (int q = lo; q < nq; q += 2 * L) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) old[k] = w + k * L < t.a_words ? snap[w + k * L] : 0;  // four loads in flight
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) cur[k] = w + k * L < t.a_words ? FpBits<T>::to(A[w + k * L]) : 0;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                moved |= cur[k] ^ old[k];
-                                if (w + k * L < t.a_words) snap[w + k * L] = cur[k];
+                                for (int k = 0; k < 2; ++k) {
+                                    if (q + k * L < nq) {
+                                        const uint4 c = A4[q + k * L];
+                                        cs += (c.x + c.y) + (c.z + c.w);
+                                    }
+                                }
                             }
-                        }
 #pragma unroll
-                        for (int q = 0; q < Core::NAP; ++q) {
-                            if (q < core.n_apass()) {
-                                moved |= aw[q] ^ snap[t.a_words + q * L + (int) (tid % L)];
-                                snap[t.a_words + q * L + (int) (tid % L)] = aw[q];
-                            }
+                            for (int q = 0; q < Core::NAP; ++q)
+                                if (q < core.n_apass()) cs += aw[q];
                         }
+                        // (the first detection behind a latch has nothing to compare with: it only writes)
+                        const bool differs = !(fz & 2) || cs != fc;
+                        fc = cs;
+                        const bool cmp = !group_any<L>(differs, g);
+                        if (cmp) {
+                            moved = 0;
+#pragma unroll 1
+                            for (int q = lo; q < nq; q += 2 * L) {
+                                uint4 cur[2], old[2];
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) old[k] = q + k * L < nq ? snap4[q + k * L] : uint4{0, 0, 0, 0};  // two loads in flight
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) cur[k] = q + k * L < nq ? A4[q + k * L] : uint4{0, 0, 0, 0};
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) {
+                                    moved |= ((cur[k].x ^ old[k].x) | (cur[k].y ^ old[k].y)) | ((cur[k].z ^ old[k].z) | (cur[k].w ^ old[k].w));
+                                    if (q + k * L < nq) snap4[q + k * L] = cur[k];
+                                }
+                            }
+#pragma unroll
+                            for (int q = 0; q < Core::NAP; ++q) {
+                                if (q < core.n_apass()) {
+                                    moved |= aw[q] ^ snap[t.a_words + q * L + lo];
+                                    snap[t.a_words + q * L + lo] = aw[q];
+                                }
+                            }
+                        } else {
+#pragma unroll 1
+                            for (int q = lo; q < nq; q += 2 * L) {
+#pragma unroll
+                                for (int k = 0; k < 2; ++k)
+                                    if (q + k * L < nq) snap4[q + k * L] = A4[q + k * L];
+                            }
+#pragma unroll
+                            for (int q = 0; q < Core::NAP; ++q)
+                                if (q < core.n_apass()) snap[t.a_words + q * L + lo] = aw[q];
+                        }
+                        if ((int32_t) a.freeze_cfg < 0 && lo == 0)
+                            atomicAdd(reinterpret_cast<unsigned long long *>(a.freeze_ws) + (cmp ? FREEZE_WS_COMPARES : FREEZE_WS_STORES), 1ull);
                         fz = (int) (((a.freeze_cfg >> 12) & 0xFFFu) << 2) | 3;
                     }
                     if (!group_any<L>(moved != 0, g)) {

@@ -250,6 +250,32 @@ int acg_ldpc_debug_freeze_stats(acg_ldpc_decoder *d, int32_t enable, int64_t *fr
     return guarded([&] { return acg_ldpc_debug_freeze_stats_impl(d, enable, frames_frozen, sweeps_not_run); });
 }
 
+static int acg_ldpc_debug_freeze_passes_impl(acg_ldpc_decoder *d, int64_t *store_passes, int64_t *compare_passes) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    HIP_OK(hipStreamSynchronize(d->stream));
+    for (int k = 0; k < acg_ldpc_decoder::WORK_RING; k++)
+        if (d->ring_used[k]) HIP_OK(hipEventSynchronize(d->ring_ev[k]));
+    unsigned long long h[2] = {0, 0};
+    static_assert(FREEZE_WS_COMPARES == FREEZE_WS_STORES + 1 && (FREEZE_WS_COMPARES + 1) * 2 <= FREEZE_WS_HEAD, "the two counts are adjacent words of the head");
+    if (d->freeze_ws.p) {
+        unsigned long long *p = d->freeze_ws.as<unsigned long long>() + FREEZE_WS_STORES;
+        HIP_OK(hipMemcpy(h, p, sizeof(h), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemset(p, 0, sizeof(h)));
+    }
+    if (store_passes) *store_passes = (int64_t) h[0];
+    if (compare_passes) *compare_passes = (int64_t) h[1];
+    return 0;
+}
+
+int acg_ldpc_debug_freeze_passes(acg_ldpc_decoder *d, int64_t *store_passes, int64_t *compare_passes) {
+    return guarded([&] { return acg_ldpc_debug_freeze_passes_impl(d, store_passes, compare_passes); });
+}
+
 int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n) {
     return guarded([&] { return acg_ldpc_debug_phi_sat_impl(x_host, out_host, n); });
 }

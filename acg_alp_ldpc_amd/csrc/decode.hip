@@ -174,7 +174,8 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
                     HIP_OK(hipMemsetAsync(d->freeze_ws.p, 0, FREEZE_WS_HEAD * sizeof(uint32_t), s));
                 }
                 a.freeze_ws = d->freeze_ws.as<uint32_t>();
-                a.freeze_cfg = (uint32_t) d->freeze_first | ((uint32_t) d->freeze_period << 12) | (d->freeze_count ? 0x80000000u : 0u);
+                a.freeze_cfg = (uint32_t) d->freeze_first | ((uint32_t) d->freeze_period << 12) | (d->freeze_gate ? 0u : FREEZE_CFG_NO_GATE) |
+                               (d->freeze_count ? 0x80000000u : 0u);
             }
         }
         HIP_OK(bp_launch(d->kernel[mc], d->tab, a, grid, d->block, d->lds_block, s));

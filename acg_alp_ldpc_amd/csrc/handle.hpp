@@ -143,7 +143,8 @@ struct acg_ldpc_decoder {
     // the SAT instances' freeze of latched frames whose state recurs (bp_fused_body): one snapshot slot per resident frame
     // group behind a small head with the debug counter (DecodeArgs::freeze_ws), allocated at the first launch
     bool freeze = false;
-    bool freeze_count = false;  // acg_ldpc_debug_freeze_stats asked for the counter
+    bool freeze_count = false;  // acg_ldpc_debug_freeze_stats asked for the counters
+    bool freeze_gate = true;    // a per-lane checksum decides whether a detection loads and compares (ACG_BP_FREEZE_NO_GATE=1: always)
     int freeze_first = 0, freeze_period = 0;
     size_t freeze_slot_words = 0;
     acg::DeviceBuf freeze_ws;

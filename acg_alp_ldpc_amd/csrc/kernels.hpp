@@ -66,14 +66,18 @@ struct DecodeArgs {
     void *dbg_post;
     // fused fixed-work sum-product (the SAT instances of bp_fused_body): a latched frame whose state recurs stops sweeping.
     // (Last in the block: the kernels that do not read them keep every argument offset.)
-    // freeze_ws: FREEZE_WS_HEAD words (the first two: a debug counter, += frames frozen << FREEZE_STATS_SHIFT | sweeps not run),
+    // freeze_ws: FREEZE_WS_HEAD words (three 64-bit debug counters: += frames frozen << FREEZE_STATS_SHIFT | sweeps not run, then
+    // at FREEZE_WS_STORES / FREEZE_WS_COMPARES the detections that only wrote a snapshot / that loaded and compared one),
     // then one snapshot slot of a_words + BP_MAX_APASS * L words per resident frame group [grid * groups per block]; null = off.
     // freeze_cfg: bits 0-11 sweeps between the latch and the first snapshot (>= 1), bits 12-23 sweeps between a snapshot and
-    // the compare against it (>= 1), bit 31 count.  (Three scalar registers in all: the kernel has none to spare.)
+    // the compare against it (>= 1), bit 30 no checksum gate in front of the compare (FREEZE_CFG_NO_GATE), bit 31 count.  (Three scalar registers in all: the kernel has none to spare.)
     uint32_t *freeze_ws;
     uint32_t freeze_cfg;
 };
-constexpr int FREEZE_WS_HEAD = 4;
+constexpr int FREEZE_WS_HEAD = 8;       // 32-bit words
+constexpr int FREEZE_WS_STORES = 1;     // 64-bit words from the head's start
+constexpr int FREEZE_WS_COMPARES = 2;
+constexpr uint32_t FREEZE_CFG_NO_GATE = 0x40000000u;
 constexpr int FREEZE_STATS_SHIFT = 40;
 
 // One code of a batch (acg_ldpc_mc_run_codes) as the classification and symbol kernels of mc_kernels.hip see it

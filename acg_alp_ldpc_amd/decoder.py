@@ -197,6 +197,14 @@ class Decoder:
         check(lib().acg_ldpc_debug_freeze_stats(h, 1 if enable else 0, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def freeze_passes(self, H):
+        """(store passes, compare passes): the freeze path's detections that only wrote a snapshot / that loaded and compared
+        one, counted since the previous call while freeze_stats has counting on (acg_ldpc_debug_freeze_passes)."""
+        h, _ = self.handle(H)
+        a, b = C.c_int64(), C.c_int64()
+        check(lib().acg_ldpc_debug_freeze_passes(h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def layout(self, H):
         h, _ = self.handle(H)
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()

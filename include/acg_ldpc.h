@@ -368,6 +368,13 @@ int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n);
  * not execute), then clears the counters.  enable != 0: later launches count (no effect on a handle without the path: both
  * figures stay 0); enable == 0: counting stops.  A launch counts at most 2^24 - 1 frozen frames. */
 int acg_ldpc_debug_freeze_stats(acg_ldpc_decoder *d, int32_t enable, int64_t *frames_frozen, int64_t *sweeps_not_run);
+/* diagnostics: the detections of the freeze path, counted while acg_ldpc_debug_freeze_stats has counting on.  A detection (one
+ * per frame and snapshot cadence point behind the latch) either only writes the frame's state to its snapshot slot (store pass:
+ * the first behind a latch, and every one at which a lane's checksum of its words differs from the one it took at the
+ * previous snapshot) or loads the snapshot and compares it word for word (compare pass; ACG_BP_FREEZE_NO_GATE=1 at handle
+ * creation: every detection behind the first).  Only a compare pass can freeze a frame.  Waits for the handle's launches,
+ * returns the two counts since the previous call and clears them. */
+int acg_ldpc_debug_freeze_passes(acg_ldpc_decoder *d, int64_t *store_passes, int64_t *compare_passes);
 /* diagnostics: soft state of the device sum-product decoder after `iters` full iterations of bp.h:183-199 without
  * the exit test, for 1..64 frames (y: frames*n doubles).  Outputs are frames*E (edge order: check-major, variables
  * ascending) / frames*n doubles: c2v = messages check->variable, (v2c_mag, v2c_sgn) = the (phi(|x|), sign) pairs

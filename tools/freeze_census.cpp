@@ -1,6 +1,6 @@
 // Developer tool: census of the freeze path of the fixed-work fused sum-product kernels (bp_fused_body FREEZE).
 //   g++ -O2 -std=c++17 -Iinclude tools/freeze_census.cpp acg_alp_ldpc_amd/csrc/code.cpp -o /tmp/freeze_census
-//   /tmp/freeze_census data/H05.txt [frames=300] [sweeps=50] [L=32] [first=6] [period=2] [snr ...]   (default SNRs: -3 -2 +2)
+//   /tmp/freeze_census data/H05.txt [frames=300] [sweeps=50] [L=32] [first=6] [period=2] [snr ... | constsum]   (default SNRs: -3 -2 +2)
 // The run of tools/phi_census.cpp: a float flooding run in the library's wave-group layout (bp_layout_build with absorption),
 // all-zero codeword, AWGN from std::mt19937 per frame, the SAT instances' arithmetic with phi from the host's log2f / exp2f
 // (a few results differ in the last bit from the device).  The state of a frame after a sweep is what the kernel compares:
@@ -9,6 +9,14 @@
 //   repeat:  the first sweep whose state equals the previous sweep's, bit for bit (latched frames only)
 //   cadence: with the first snapshot `first` sweeps behind the latch and a compare + new snapshot every `period` sweeps (the
 //            kernel's schedule: no detection behind the last sweep), the sweeps a frame executes and the detections it pays
+//   gate:    the kernel's detection in full, for the cadence given and for every cadence of the grid the built-in one was chosen
+//            from.  A lane sums the words it would compare (the quads l, l + L, ... of A and its own aw); the first detection
+//            behind a latch only writes; a later one is "rejected" when a lane's sum differs from the one taken at the snapshot
+//            (the group only writes) and "passed" otherwise (the group loads and compares).  A passed detection whose compare
+//            fails is a collision of the sum.  With the word `constsum` among the SNRs every lane's sum is a constant, so every
+//            detection passes: the sweep at which a frame stops must not depend on it (the compare alone decides).
+//            Rows: "gate <snr> <first>,<period> <sweeps run> <frozen frames> <first> <rejected> <passed> <collisions>" (totals
+//            over the frames, sweeps run as a mean).
 // and the property the kernel's freeze stands on in this model: a frame stopped at its first exact repeat has, after the last
 // sweep, the hard decisions it latched ("stopped frames whose final decisions differ from the latch": must be 0).
 #include <algorithm>
@@ -39,6 +47,19 @@ static float flt(uint32_t u) {
 }
 static const uint32_t SIGN = 0x80000000u, ONE = 1u;
 
+// one cadence of the kernel's detection with the checksum gate in front of the compare
+struct Cadence {
+    int first, period;
+    // per frame
+    int due = 0, stop = 0;
+    bool have = false;
+    std::vector<uint32_t> snap, sum;
+    // totals
+    long run = 0, frozen = 0, n_first = 0, n_rejected = 0, n_passed = 0, n_collisions = 0;
+};
+static const int GRID[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 1}, {4, 1}, {4, 2}, {5, 3}, {6, 1}, {6, 2}, {7, 2}, {8, 1}, {8, 2},
+                              {8, 3}, {8, 4}, {9, 2}, {10, 1}, {10, 2}, {12, 4}};
+
 // Dom<float>::phi (bp_core.inc) with the host's log2 / exp2, and the fast path's constants (BpPass::phi_c / phi_v)
 static float phi(float x) {
     const float w = x * x;
@@ -62,7 +83,11 @@ int main(int argc, char **argv) {
     const int frames = argc > 2 ? atoi(argv[2]) : 300, sweeps = argc > 3 ? atoi(argv[3]) : 50, L = argc > 4 ? atoi(argv[4]) : 32;
     const int first = argc > 5 ? atoi(argv[5]) : 6, period = argc > 6 ? atoi(argv[6]) : 2;
     std::vector<double> snrs;
-    for (int i = 7; i < argc; i++) snrs.push_back(atof(argv[i]));
+    bool constsum = false;
+    for (int i = 7; i < argc; i++) {
+        if (!strcmp(argv[i], "constsum")) constsum = true;
+        else snrs.push_back(atof(argv[i]));
+    }
     if (snrs.empty()) snrs = {-3.0, -2.0, 2.0};
     if (frames < 1 || sweeps < 1 || first < 1 || period < 1) return fprintf(stderr, "frames, sweeps, first, period must be >= 1\n"), 1;
     std::vector<uint8_t> Hd;
@@ -82,7 +107,15 @@ int main(int argc, char **argv) {
            "sweeps run, stop at first repeat | sweeps run, cadence | frozen, cadence | detections per frame, cadence |\n");
     printf("|---|---|---|---|---|---|---|---|---|---|\n");
     long differ_total = 0;
+    std::string gate_rows;
     for (double snr : snrs) {
+        std::vector<Cadence> cads(1);
+        cads[0].first = first, cads[0].period = period;
+        for (const auto &gp : GRID)
+            if (gp[0] != first || gp[1] != period) {
+                cads.emplace_back();
+                cads.back().first = gp[0], cads.back().period = gp[1];
+            }
         const double var = std::pow(10, -(snr / 10)) / 2, inv_var2 = 2.0 / var, sigma = std::sqrt(var);
         long fails = 0, latched_n = 0, repeat_n = 0, frozen_n = 0, detections = 0, differ = 0;
         double latch_sum = 0, run_first = 0, run_cad = 0;
@@ -112,6 +145,7 @@ int main(int argc, char **argv) {
                 aw[s] = v >= 0 ? (bits(phi(fabsf(al[s]))) & ~SIGN & ~ONE) | (al[s] <= 0 ? (ONE | SIGN) : 0u) : 0u;
             }
             int latch = 0, repeat = 0, stop_cad = 0, due = 0, ndet = 0;  // sweep numbers, 1-based; 0 = never
+            for (auto &cd : cads) cd.due = cd.stop = 0, cd.have = false;
             bool have_snap = false;
             std::vector<uint8_t> est(n, 0), est_latch;
             prev.clear();
@@ -198,6 +232,7 @@ int main(int argc, char **argv) {
                         latch = it;
                         est_latch = est;
                         due = it + first;
+                        for (auto &cd : cads) cd.due = it + cd.first;
                     }
                 }
                 // ---- the state the kernel compares
@@ -211,8 +246,37 @@ int main(int argc, char **argv) {
                     have_snap = true;
                     due = it + period;
                 }
+                // ---- the same detection as the kernel runs it: the lanes' sums first, the compare only where they allow it
+                std::vector<uint32_t> sum;
+                for (auto &cd : cads) {
+                    if (!latch || it != cd.due || it >= sweeps || cd.stop) continue;
+                    if (sum.empty()) {
+                        sum.assign(L, constsum ? 0x5EEDu : 0u);
+                        if (!constsum) {
+                            for (int q = 0; q < lay.a_words / 4; q++)
+                                for (int e = 0; e < 4; e++) sum[q % L] += A[4 * q + e];
+                            for (size_t x = 0; x < aw.size(); x++) sum[x % L] += aw[x];
+                        }
+                    }
+                    if (!cd.have) cd.n_first++;
+                    else if (sum != cd.sum) cd.n_rejected++;
+                    else {
+                        cd.n_passed++;
+                        if (cur == cd.snap) cd.stop = it;
+                        else cd.n_collisions++;
+                    }
+                    cd.snap = cur;
+                    cd.sum = sum;
+                    cd.have = true;
+                    cd.due = it + cd.period;
+                }
                 prev.swap(cur);
             }
+            for (auto &cd : cads) {
+                cd.run += cd.stop ? cd.stop : sweeps;
+                cd.frozen += cd.stop != 0;
+            }
+            if (cads[0].stop != stop_cad) return fprintf(stderr, "frame %d: the gated detection stops at %d, the plain one at %d\n", f, cads[0].stop, stop_cad), 2;
             fails += !latch;
             if (latch) {
                 latched_n++;
@@ -238,7 +302,15 @@ int main(int argc, char **argv) {
                (double) detections / frames);
         fflush(stdout);
         differ_total += differ;
+        for (const auto &cd : cads) {
+            char row[200];
+            snprintf(row, sizeof row, "gate %+.0f %d,%d %.3f %ld %ld %ld %ld %ld\n", snr, cd.first, cd.period, (double) cd.run / frames, cd.frozen,
+                     cd.n_first, cd.n_rejected, cd.n_passed, cd.n_collisions);
+            gate_rows += row;
+        }
     }
     printf("\nstopped frames whose final decisions differ from the latch: %ld\n", differ_total);
+    printf("\ngate (%s), %d frames: snr first,period sweeps-run frozen first rejected passed collisions\n%s", constsum ? "constant sum" : "sum of the lane's words",
+           frames, gate_rows.c_str());
     return 0;
 }
