@@ -97,6 +97,7 @@ SYMBOLS = {
     "acg_ldpc_debug_ring_tasks": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _i64, _vp]),
     "acg_ldpc_debug_layers": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_block": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
+    "acg_ldpc_debug_layers_wide": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_phi": (C.c_int, [_vp, _vp, _i32, _i32]),
     "acg_ldpc_debug_phi_sat": (C.c_int, [_vp, _vp, _i32]),
     "acg_ldpc_debug_freeze_stats": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -72,6 +72,15 @@ class ParityCheckMatrix:
         check(lib().acg_ldpc_debug_layers_block(self._h, C.byref(nl), C.byref(w), C.byref(Z), chk.ctypes.data, chk.size))
         return Z.value, chk
 
+    def layers_wide(self):
+        """the sets of layers_block() for the wide-check layered engine (SCHEDULE_LAYERED on a code whose largest check has
+        9 ... 32 variables, bp_layered_wide_kernel): the same rule and the same return value, check degree up to 32"""
+        nl, w, Z = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().acg_ldpc_debug_layers_wide(self._h, C.byref(nl), C.byref(w), C.byref(Z), None, 0))
+        chk = np.full((nl.value, w.value), -1, dtype=np.int32)
+        check(lib().acg_ldpc_debug_layers_wide(self._h, C.byref(nl), C.byref(w), C.byref(Z), chk.ctypes.data, chk.size))
+        return Z.value, chk
+
     def is_codeword(self, bits):
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         assert b.shape[-1] == self.n

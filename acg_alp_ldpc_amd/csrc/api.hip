@@ -394,11 +394,14 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
 // schedule = LAYERED with one workgroup of L = 256, 512 or 1024 threads per frame (bp_layered_block.hip): the layered engine for
 // codes whose frame is too large for a wavefront group.  Its only size limit is the LDS of a CU: posteriors + messages +
 // output word of ONE frame.
-static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L) {
+// wide: the code has a check of degree 9 ... 32 — the same tables under bp_layered_wide_kernel (bp_layered_wide.hip); L = 0 then
+// stands for the smallest workgroup that takes the largest set in one pass, else 1024.
+static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L, bool wide = false) {
     const Code &c = d->c;
     const bool f16 = d->p.precision == ACG_LDPC_PREC_F16;
-    if (!bp_layered_block_build(c, d->lblay)) return 3;
+    if (!bp_layered_block_build(c, d->lblay, wide ? 32 : 8)) return 3;
     const LayeredBlockLayout &ll = d->lblay;
+    if (wide && L == 0) L = ll.width <= 256 ? 256 : (ll.width <= 512 ? 512 : 1024);
     LayerBlockTables &t = d->lbtab;
     t.n = c.n;
     t.nwords = (c.n + 31) / 32;
@@ -408,7 +411,7 @@ static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L) {
     t.r_words = f16 ? (ll.e + 1) / 2 : ll.e;
     const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
     const int algo = d->p.algo == ACG_LDPC_BP_MINSUM ? 1 : 0;
-    const void *kp = bp_layered_block_kernel_ptr(L, f16, algo);
+    const void *kp = wide ? bp_layered_wide_kernel_ptr(L, f16, algo) : bp_layered_block_kernel_ptr(L, f16, algo);
     if (!kp) {
         set_error("no layered workgroup-per-frame kernel instance for this lanes_per_frame");
         return 3;
@@ -429,6 +432,7 @@ static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L) {
     t.pos = d->lb_pos.as<const int32_t>();
     t.n_steps = (int) (step.size() / 8);
     d->layered_block = true;
+    d->layered_wide = wide;
     d->L = L;
     d->f64 = 0;
     d->block = L;
@@ -455,6 +459,18 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
     // 256, 512, 1024: one workgroup per frame.  0 keeps the wavefront-group kernel for every code it accepts and falls
     // through to a workgroup of 1024 only where that kernel refuses for size (n >= 16000 here, a frame beyond LDS below)
     const int want_L = d->p.lanes_per_frame;
+    // a check of degree 9 ... 32: the wide-check workgroup engine, whatever lanes_per_frame of its own (0 included) was asked for
+    if (c.max_cdeg > 8) {
+        if (c.max_cdeg > 32) {
+            set_error("layered schedule: check degree above 32 is not supported");
+            return 3;
+        }
+        if (want_L != 0 && want_L != 256 && want_L != 512 && want_L != 1024) {
+            set_error("layered schedule: lanes_per_frame is chosen by the layering (pass 0), or 256, 512, 1024 for one workgroup per frame");
+            return 3;
+        }
+        return decoder_setup_layered_block(d, want_L, true);
+    }
     if (want_L == 256 || want_L == 512 || want_L == 1024) return decoder_setup_layered_block(d, want_L);
     if (want_L == 0 && c.n >= 16000) return decoder_setup_layered_block(d, 1024);
     if (!bp_layered_build(c, d->llay)) return 3;
@@ -917,9 +933,9 @@ static std::string describe(const acg_ldpc_decoder *d) {
             return t;
         }
     } else if (d->layered_block) {
-        snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_block_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
+        snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
                                "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=%s",
-                 algo, d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width,
+                 algo, d->layered_wide ? "bp_layered_wide_kernel" : "bp_layered_block_kernel", d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width,
                  d->p.precision == ACG_LDPC_PREC_F16 ? "fp16" : "fp32");
     } else {
         snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=%d block=%d frames_per_block=%d lds_block=%zu grid_cap=%d "

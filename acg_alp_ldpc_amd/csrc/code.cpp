@@ -804,14 +804,15 @@ bool bp_layered_build(const Code &c, LayeredLayout &o) {
 }
 
 // Sets of the workgroup-per-frame layered schedule (see LayeredBlockLayout).
-bool bp_layered_block_build(const Code &c, LayeredBlockLayout &o) {
+bool bp_layered_block_build(const Code &c, LayeredBlockLayout &o, int max_degree) {
     o = LayeredBlockLayout();
     if (c.m <= 0 || c.n <= 0) {
         set_error("layered schedule: the matrix has no checks");
         return false;
     }
-    if (c.max_cdeg > 8) {
-        set_error("layered schedule: check degree above 8 is not supported");
+    if (c.max_cdeg > max_degree) {
+        set_error(max_degree == 8 ? "layered schedule: check degree above 8 is not supported"
+                                  : "layered schedule: check degree above " + std::to_string(max_degree) + " is not supported");
         return false;
     }
     struct Set { int deg; std::vector<int> chk; };

@@ -163,14 +163,14 @@ int acg_ldpc_debug_ring_tasks(const acg_ldpc_code *code, int32_t *n_ctask, int32
     });
 }
 
-int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
+static int debug_layers_block(const acg_ldpc_code *code, int max_degree, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
     return guarded([&]() -> int {
         if (!code) {
             set_error("null argument");
             return 1;
         }
         LayeredBlockLayout ll;
-        if (!bp_layered_block_build(code->c, ll)) return 3;
+        if (!bp_layered_block_build(code->c, ll, max_degree)) return 3;
         if (n_layers) *n_layers = ll.n_sets;
         if (width) *width = ll.width;
         if (qc_Z) *qc_Z = ll.qc ? ll.Z : 0;
@@ -178,6 +178,14 @@ int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, in
             for (int64_t i = 0; i < std::min<int64_t>(cap, (int64_t) ll.chk.size()); i++) chk[i] = ll.chk[(size_t) i];
         return 0;
     });
+}
+
+int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
+    return debug_layers_block(code, 8, n_layers, width, qc_Z, chk, cap);
+}
+
+int acg_ldpc_debug_layers_wide(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
+    return debug_layers_block(code, 32, n_layers, width, qc_Z, chk, cap);
 }
 
 int acg_ldpc_debug_layers(const acg_ldpc_code *code, int32_t *lanes, int32_t *n_layers, int32_t *qc_Z, int32_t *chk, int64_t cap) {

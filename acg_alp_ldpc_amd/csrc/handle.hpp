@@ -156,6 +156,7 @@ struct acg_ldpc_decoder {
     acg::LayerTables ltab{};
     // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory
     bool layered_block = false;
+    bool layered_wide = false;  // (with layered_block) the kernel is bp_layered_wide_kernel: check degree up to 32, same tables
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;

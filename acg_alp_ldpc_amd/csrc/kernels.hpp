@@ -117,7 +117,8 @@ struct LayerTables {
 };
 
 // Workgroup-per-frame layered BP (bp_layered_block.hip; LayeredBlockLayout in ldpc_internal.hpp).  Both tables live in device
-// memory; a workgroup's LDS holds the state of its frame and nothing else.
+// memory; a workgroup's LDS holds the state of its frame and nothing else.  bp_layered_wide.hip (check degree up to 32) reads the
+// same tables: degree is then 1 ... 32, and that kernel fetches the position entries of a step 8 edges at a time.
 struct LayerBlockTables {
     // [n_steps][8]: the (set, pass) pairs of one iteration in processing order =
     //   {degree, 1 = barrier behind the step (the last pass of a set; 0 behind the last set: the round's OR is its barrier),

@@ -66,6 +66,11 @@ const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo);
 hipError_t bp_layered_block_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
                                    hipStream_t s);
 
+// ---- bp_layered_wide.hip (check degree up to 32; the tables of bp_layered_block.hip) ----
+const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo);
+hipError_t bp_layered_wide_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
+                                  hipStream_t s);
+
 // ---- bp_streamed.hip ----
 const void *bp_streamed_ptr(int algo, int f64);
 const void *bp_streamed_ring_ptr(int algo, bool nt);

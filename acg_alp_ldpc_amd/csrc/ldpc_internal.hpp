@@ -169,7 +169,8 @@ struct LayeredBlockLayout {
     std::vector<int32_t> chk;        // [n_sets*width] check id of (set, slot), -1 = none; occupied slots first
     std::vector<int32_t> pos;        // [e] variable of edge j (ascending variable order) of (set, slot) at offset + j * cnt + slot
 };
-bool bp_layered_block_build(const Code &c, LayeredBlockLayout &out);
+// max_degree: the largest check degree the engine that asks takes — 8 (bp_layered_block.hip) or 32 (bp_layered_wide.hip)
+bool bp_layered_block_build(const Code &c, LayeredBlockLayout &out, int max_degree = 8);
 // the (set, pass) steps of LayerBlockTables for a workgroup of L threads
 void bp_layered_block_steps(const LayeredBlockLayout &lay, int L, std::vector<int32_t> &step);
 

@@ -225,7 +225,9 @@ class MinSumDecoder(Decoder):
     """Build-added normalised min-sum (north_star).  Not in the reference: parity unpinned.
     schedule=SCHEDULE_LAYERED: layered (row-block sequential) schedule — about half the sweeps for the same FER.
     With it, lanes_per_frame=256 / 512 / 1024 selects the engine with one workgroup per frame (codes of tens of thousands of
-    edges: pass 1024); 0 takes it only where the wavefront-group kernel refuses the code for its size."""
+    edges: pass 1024); 0 takes it only where the wavefront-group kernel refuses the code for its size.
+    A code with a check of 9 ... 32 variables (high-rate codes) runs on the wide-check workgroup engine whatever
+    lanes_per_frame says: 256 / 512 / 1024 as given, 0 = the smallest of them that holds the largest set of checks."""
     _algo = _lib.ALGO_MINSUM
 
     def __init__(self, max_iter, scale=1.0, **kw):

@@ -79,14 +79,19 @@ enum {
                                        anyway); with ACG_LDPC_BP_SUMPRODUCT: the reference's check rule (bp.h:49-57) in the
                                        layered message order — the reference's FER at about half its iterations.  fp32
                                        posteriors; messages fp32, or fp16 with ACG_LDPC_PREC_F16.
-                                       Two engines.  lanes_per_frame 0: 16, 20, 32 or 64 lanes of a wavefront per frame
-                                       (bp_layered_kernel; check degree <= 8, n < 16000, a few thousand edges).
-                                       lanes_per_frame 256, 512 or 1024: one workgroup per frame (bp_layered_block_kernel) —
-                                       check degree <= 8, and posteriors + messages + output word of ONE frame within the
+                                       Three engines.  Check degree <= 8, lanes_per_frame 0: 16, 20, 32 or 64 lanes of a
+                                       wavefront per frame (bp_layered_kernel; n < 16000, a few thousand edges).
+                                       Check degree <= 8, lanes_per_frame 256, 512 or 1024: one workgroup per frame
+                                       (bp_layered_block_kernel) — posteriors + messages + output word of ONE frame within the
                                        160 KiB of LDS, i.e. (n + 4) * 4 + E * 4 (E * 2 with fp16 messages) + n / 8 bytes for E
                                        edges; a Monte-Carlo run on it goes noise kernel -> decode -> classification kernel.
                                        Pass 1024 for codes of tens of thousands of edges: 0 selects the workgroup engine by
-                                       itself only where the wavefront-group kernel refuses the code for its size. */
+                                       itself only where the wavefront-group kernel refuses the code for its size.
+                                       Largest check degree 9 ... 32 (high-rate codes): one workgroup per frame with wide
+                                       checks worked off in chunks of 8 edges (bp_layered_wide_kernel), for every
+                                       lanes_per_frame it takes — 256, 512, 1024, or 0 = the smallest of the three that holds
+                                       the largest set of checks, else 1024; the same LDS rule and Monte-Carlo path as the
+                                       other workgroup engine.  A check of more than 32 variables is refused. */
 };
 
 /* noise source for acg_ldpc_mc_run */
@@ -111,8 +116,9 @@ typedef struct acg_ldpc_params {
     int32_t device;     /* HIP device ordinal; -1 = current device */
     int32_t lanes_per_frame; /* 0 = auto; 16/32/64: that many lanes of a wavefront cooperate on one frame; 256 (BP also
                                 1024): one workgroup per frame (QP-ADMM then picks 128, 192 or 256 threads itself).
-                                ACG_LDPC_SCHEDULE_LAYERED: 0 (the layering picks the lanes of a wavefront group), or 256, 512,
-                                1024 = one workgroup of that many threads per frame */
+                                ACG_LDPC_SCHEDULE_LAYERED: 0 (check degree <= 8: the layering picks the lanes of a wavefront
+                                group; 9 ... 32: the smallest workgroup that holds the largest set), or 256, 512, 1024 = one
+                                workgroup of that many threads per frame (check degree <= 32) */
     int32_t engine;     /* ACG_LDPC_ENGINE_* (BP and QP-ADMM) */
     int32_t fast_setup; /* 0 = default: spend up to ~1 s per decoder on the static LDS placement of the QP-ADMM kernel
                            (bank-conflict search; cached per parity-check matrix inside the process);
@@ -408,6 +414,10 @@ int acg_ldpc_debug_layers(const acg_ldpc_code *code, int32_t *lanes, int32_t *n_
  * -1, at most cap entries.  Returns 0, or non-zero if the matrix cannot be layered (check degree above 8, no checks; message
  * in acg_ldpc_last_error). */
 int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap);
+
+/* diagnostics (host only, no device needed): the same sets by the same rule for the wide-check engine (bp_layered_wide_kernel):
+ * the contract of acg_ldpc_debug_layers_block with check degree up to 32 (non-zero for a check degree above 32). */
+int acg_ldpc_debug_layers_wide(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap);
 
 #ifdef __cplusplus
 }
