@@ -604,60 +604,39 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
         if (L == 0) L = (c.n <= 12 * 256) ? 256 : 1024;
         blockmode = true;
     }
-    if (!pair && L == 0 && d->maxd <= 8) {
-        const size_t ts0 = d->f64 ? 8 : 4;
-        const size_t wave_frame = ((size_t) c.E + 64 + ((size_t) c.n > 12 * 64 ? (size_t) c.n : 0)) * ts0;  // rough, L = 64
-        const int waves_cu = (int) std::min<size_t>(32, (160 * 1024) / std::max<size_t>(wave_frame, 1));
-        if (waves_cu < 12) {
-            // smallest workgroup that reaches >= 12 wavefronts per CU, else the largest
-            const size_t blk_frame = ((size_t) c.E * 5 / 4 + 256) * ts0;
-            L = (((160 * 1024) / std::max<size_t>(blk_frame, 1)) * 4 >= 12 && c.n <= 12 * 256) ? 256 : 1024;
-            blockmode = (c.n <= 12 * L);
-            if (!blockmode) L = 0;
-        }
+    if (!pair && L == 0) {
+        L = bp_default_lanes(c, d->f64 != 0);
+        if (L == 0) return 3;
+        blockmode = L >= 256;
     }
     if (blockmode && (d->maxd > 8 || c.n > 12 * L)) {
         set_error("workgroup-per-frame BP needs node degree <= 8 and n <= 12 * lanes_per_frame");
         return 3;
-    }
-    if (L == 0) {
-        // Auto: a pass costs its largest degree for all L lanes, so finer groups waste fewer padded
-        // message slots (H05: 79% useful at L=64, 94% at L=32).  Measured on MI355X (H05, 50 it): fixed work
-        // 19.0 M frames/s at L=32 vs 17.2 M at L=64; early exit 68.6 M vs 65.3 M at -2 dB, 296 M vs 285 M at +2 dB.
-        BpLayout l64, l32;
-        if (!bp_layout_build(c, 64, l64) || !bp_layout_build(c, 32, l32)) return 3;
-        auto slots = [](const BpLayout &y) {
-            long s = 0;
-            for (int v : y.c_maxdeg) s += (long) v * y.L;
-            for (int v : y.v_maxdeg) s += (long) v * y.L;
-            return (double) s;
-        };
-        const double gain = slots(l64) / std::max(1.0, slots(l32));
-        L = (gain > 1.05) ? 32 : 64;
     }
     d->L = L;
     if (!bp_layout_build(c, L, d->lay)) return 3;
     // fp32 sum-product wave-group kernels with register LLRs: degree-1 variables absorbed into their checks
     // (BpLayout::n_apass, BpPass::check_abs); taken when the absorbed layout runs that kernel variant
     if (!blockmode && !pair && !d->f64 && d->p.algo != ACG_LDPC_BP_MINSUM && d->maxd <= 8 && getenv("ACG_BP_NO_ABSORB") == nullptr) {
-        BpLayout la;
-        if (!bp_layout_build(c, L, la, BP_MAX_APASS)) return 3;
-        if (la.n_apass > 0 && la.n_vpass <= 12 && (size_t) std::max(la.a_words, (c.n + 3) & ~3) * 4 <= 65535) d->lay = std::move(la);
+        if (!bp_layout_absorb(c, L, d->lay)) return 3;
     }
     BpLayout &lay = d->lay;
     const int nwords = (c.n + 31) / 32;
     // the MC path stages n symbols in the message array before clearing it
     if (lay.a_words < ((c.n + 3) & ~3)) lay.a_words = (c.n + 3) & ~3;
     const size_t ts = d->f64 ? 8 : 4;
-    // channel LLRs: in registers when there are at most 12 variable passes (degree <= 8 kernels), else in LDS
-    // the fused kernels keep their LDS copy of the variable-side index table in BYTE offsets (16 bits): the message
-    // array of a frame has to stay below 64 KiB for that copy (and the register-LLR instances, which require it)
-    const bool a_fits16 = blockmode || (size_t) lay.a_words * ts <= 65535;
-    const bool llr_regs = blockmode || ((d->maxd <= 8) && (lay.n_vpass <= 12) && a_fits16);
-    const int llr_words = llr_regs ? 0 : lay.n_vpass * L;
-    size_t per_frame = (size_t) (lay.a_words + llr_words) * ts + (size_t) nwords * 4;
-    if (pair) per_frame = (size_t) lay.a_words * 4 + 2 * (size_t) nwords * 4;  // one 32-bit word per edge for TWO frames
-    per_frame = (per_frame + 15) & ~(size_t) 15;
+    // wavefront groups: LLRs in registers or LDS, the index table in LDS or global, the frame's LDS bytes and the wavefronts per
+    // workgroup are bp_wave_plan's decisions (code.cpp); a workgroup per frame keeps the LLRs in registers
+    BpWavePlan wp;
+    if (!blockmode) wp = bp_wave_plan(c, lay, d->f64 != 0);
+    const bool llr_regs = blockmode || wp.llr_regs;
+    const int llr_words = blockmode ? 0 : wp.llr_words;
+    size_t per_frame = wp.per_frame;
+    if (blockmode) {
+        per_frame = (size_t) lay.a_words * ts + (size_t) nwords * 4;
+        if (pair) per_frame = (size_t) lay.a_words * 4 + 2 * (size_t) nwords * 4;  // one 32-bit word per edge for TWO frames
+        per_frame = (per_frame + 15) & ~(size_t) 15;
+    }
 
     BpTables &t = d->tab;
     std::vector<int32_t> c_pass(2 * (size_t) lay.n_cpass), v_pass(2 * (size_t) lay.n_vpass);
@@ -687,7 +666,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     t.v_apos_len = lay.v_apos_len;
     // the variable-side index table is read by every wave in every iteration: keep a block-shared
     // copy in LDS unless it is large (then it is read through L1/L2)
-    bool idxlds = a_fits16 && ((size_t) lay.v_apos_len * 2 <= 16 * 1024 || (llr_regs && !blockmode));
+    bool idxlds = wp.idxlds;
     if (blockmode) idxlds = (size_t) lay.v_apos_len * 2 <= 32 * 1024 &&
                             (((size_t) lay.v_apos_len * 2 + 15) & ~(size_t) 15) + per_frame <= 158 * 1024;
     t.idx_lds_bytes = idxlds ? (int) (((size_t) lay.v_apos_len * 2 + 15) & ~(size_t) 15) : 0;
@@ -749,10 +728,8 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
         return 0;
     }
     const int fpw = 64 / L;
-    // waves per block: as many as fit in half the LDS (so at least two blocks share a CU), at most 4
-    int waves = 4;
-    while (waves > 1 && per_frame * fpw * waves + t.idx_lds_bytes > 160 * 1024 / 2) waves >>= 1;
-    if (per_frame * fpw * waves + t.idx_lds_bytes > 160 * 1024) {
+    const int waves = wp.waves;
+    if (waves == 0) {
         if (d->p.engine == ACG_LDPC_ENGINE_AUTO) {
             d->dev_allocs.clear();
             return decoder_setup_streamed(d);
@@ -786,12 +763,22 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     }
     d->freeze_slot_words = (size_t) lay.a_words + (size_t) BP_MAX_APASS * L;
     for (int mc = 0; mc < 2; mc++) {
-        const int variant = idxlds ? ((llr_regs) ? 2 : 1) : 0;
+        const int variant = wp.variant;
         d->variant = variant;
         const void *kp = bp_kernel_ptr(algo, d->f64, d->maxd, L, mc != 0, variant, sat);
         if (!kp) {
             set_error("no kernel instance for this configuration");
             return 3;
+        }
+        // the build-time instance with this layout's pass structure constant, where the library holds one (bp_inst_spec.hip:
+        // the fixed-work fp32 sum-product instances only; equal signature, whatever the matrix); ACG_BP_NO_SPEC=1 keeps
+        // the generic instance (A/B runs)
+        if (sat && algo == 0 && !d->f64 && d->maxd <= 8 && variant == 2 && getenv("ACG_BP_NO_SPEC") == nullptr) {
+            const char *name = nullptr;
+            if (const void *ks = bp_spec_kernel_ptr(lay, mc != 0, &name)) {
+                kp = ks;
+                d->spec = name;
+            }
         }
         if (int rc = bind_kernel(d, mc, kp)) return rc;
     }
@@ -944,12 +931,16 @@ static std::string describe(const acg_ldpc_decoder *d) {
                  d->frames_per_block, d->lds_block, d->grid_cap[0], d->variant < 0 ? (int) d->blk_idxlds : (d->variant > 0), (int) d->blk_idxreg,
                  d->p.schedule == ACG_LDPC_SCHEDULE_LAYERED ? (d->p.precision == ACG_LDPC_PREC_F16 ? "layered messages=fp16" : "layered messages=fp32")
                                                             : "flooding");
-        if (d->variant >= 0 && !d->layered && !d->pair && !d->p.early_exit) {
-            // fixed-work decoders: whether latched frames whose state recurs stop sweeping, and on which cadence
+        if (d->variant >= 0 && !d->layered && !d->pair) {
             std::string t = b;
-            if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period) +
-                                    " freeze_gate=" + (d->freeze_gate ? "1" : "0");
-            else t += " freeze=0";
+            if (!d->p.early_exit) {
+                // fixed-work decoders: whether latched frames whose state recurs stop sweeping, and on which cadence
+                if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period) +
+                                        " freeze_gate=" + (d->freeze_gate ? "1" : "0");
+                else t += " freeze=0";
+            }
+            // the build-time instance with the code's pass structure constant that this handle runs (bp_inst_spec.hip), or 0
+            t += std::string(" spec=") + (d->spec ? d->spec : "0");
             return t;
         }
     }

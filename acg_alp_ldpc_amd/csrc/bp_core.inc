@@ -70,6 +70,9 @@ __device__ __forceinline__ double phi_f(double x) {
 #ifndef ACG_IDX_BYTES
 #define ACG_IDX_BYTES 1
 #endif
+#ifndef ACG_SPEC_VIREG
+#define ACG_SPEC_VIREG 0
+#endif
 #ifndef ACG_FUSED_MERGED
 #define ACG_FUSED_MERGED 1
 #endif
@@ -459,6 +462,27 @@ struct BpPass {
     }
 };
 
+// ------------------------------------------------------------------------------------------
+// Pass structure policy: where a kernel takes the values that are the same for every lane of every frame of a code — the
+// pass tables (c_pass, v_pass), the degree histograms (c_cnt_ge, v_cnt_ge) and the pass counts.
+//   PassRuntime (the default): from BpTables, through scalar loads; one instance serves every code.
+//   a static policy (generated per code by tools/bp_spec_gen.cpp, see bp_inst_spec.hip): STATIC = true, the counts as
+//   constants n_cpass / n_apass / n_vpass and the tables as constexpr look-ups c_pass(i), v_pass(i), c_cnt_ge(j), v_cnt_ge(j).
+//   The pass loops are then unrolled at compile time: the switch on the degree, the table loads, the register indexing
+//   and every store predicate that is true (or false) for a whole pass fold away.  The index tables, the messages and
+//   all arithmetic are the run-time policy's, so the results are the same bit for bit.
+struct PassRuntime {
+    static constexpr bool STATIC = false;
+};
+// the pass loops: `for (p = 0 .. n - 1) BODY` as a loop (run-time policy) or as straight-line code (static policy: n is one
+// of its constants).  BODY is a macro that holds the braces of the loop body.
+#define ACG_PASS_LOOP(ST, p, n, BODY)                                                                          \
+    if constexpr (ST) {                                                                                        \
+        _Pragma("unroll") for (int p = 0; p < (n); ++p) BODY                                                   \
+    } else {                                                                                                   \
+        for (int p = 0; p < (n); ++p) BODY                                                                     \
+    }
+
 #define ACG_PASS_SWITCH(md, CALL)                                                                              \
     switch (md) {                                                                                              \
         case 1: CALL(1); break;                                                                                \
@@ -478,7 +502,8 @@ struct BpPass {
 // of 4 resident workgroups per CU.  NVP = 0 (more than NVP variable passes): LLRs in LDS.
 // IDXB: the table behind IDX holds byte offsets into A (see BpPass::at)
 // SAT: the phi fast path in the sweeps, see SATSKIP
-template <typename T, int MAXD, int L, int ALGO, bool IDXLDS, int NVP, bool IDXB = false, bool SAT = false>
+// PS: the pass structure policy (PassRuntime, or a code's constants)
+template <typename T, int MAXD, int L, int ALGO, bool IDXLDS, int NVP, bool IDXB = false, bool SAT = false, typename PS = PassRuntime>
 struct BpCore {
     using B = FpBits<T>;
     using U = typename B::U;
@@ -503,7 +528,28 @@ struct BpCore {
     static constexpr int NAP = (NVP > 0 && ALGO == 0 && sizeof(T) == 4 && MAXD <= 8 && L <= 64) ? BP_MAX_APASS : 0;
     using AbsLlr = T[NAP > 0 ? NAP : 1];
     using AbsWord = U[NAP > 0 ? NAP : 1];
-    __device__ __forceinline__ int n_apass() const { return NAP > 0 ? t.n_apass : 0; }
+    __device__ __forceinline__ int n_apass() const {
+        if constexpr (PS::STATIC) return NAP > 0 ? PS::n_apass : 0;
+        else return NAP > 0 ? t.n_apass : 0;
+    }
+    // the pass structure, by policy
+    static constexpr bool STATIC = PS::STATIC;
+    __device__ __forceinline__ int n_cpass() const {
+        if constexpr (PS::STATIC) return PS::n_cpass;
+        else return t.n_cpass;
+    }
+    __device__ __forceinline__ int n_vpass() const {
+        if constexpr (PS::STATIC) return PS::n_vpass;
+        else return t.n_vpass;
+    }
+    __device__ __forceinline__ int c_pass(int i) const {
+        if constexpr (PS::STATIC) return PS::c_pass(i);
+        else return sload(t.c_pass, i);
+    }
+    __device__ __forceinline__ int v_pass(int i) const {
+        if constexpr (PS::STATIC) return PS::v_pass(i);
+        else return sload(t.v_pass, i);
+    }
     __device__ __forceinline__ int abs_var(int q) const { return t.a_var[q * L + l]; }
     // the constant v->c word of an absorbed variable: var_init's word (its first sweep) for a variable of degree 1
     static __device__ __forceinline__ U abs_word(T llr) {
@@ -532,38 +578,46 @@ struct BpCore {
         : t(t_), A(A_), LLR(LLR_), OB(OB_), IDX(IDX_), l(l_), ms_scale((T) s_) {
 #pragma unroll
         for (int j = 0; j < MAXD + 2; ++j) {
-            ccnt[j] = sload(t.c_cnt_ge, j);
-            vcnt[j] = sload(t.v_cnt_ge, j);
+            if constexpr (PS::STATIC) {
+                ccnt[j] = PS::c_cnt_ge(j);
+                vcnt[j] = PS::v_cnt_ge(j);
+            } else {
+                ccnt[j] = sload(t.c_cnt_ge, j);
+                vcnt[j] = sload(t.v_cnt_ge, j);
+            }
         }
     }
 
     // XOR of the hard-decision bits of each check's variables -> true if any check of this lane fails
     __device__ __forceinline__ bool syndrome_bad(const AbsWord &aw) const {
         U acc = 0;
-        const int nc = t.n_cpass - n_apass();
+        const int nc = n_cpass() - n_apass();
 #pragma unroll
         for (int q = 0; q < NAP; ++q) {
             if (q < n_apass()) {
-                const int md = sload(t.c_pass, 2 * (nc + q));
-                const T *Ap = A + sload(t.c_pass, 2 * (nc + q) + 1) + l;
+                const int md = c_pass(2 * (nc + q));
+                const T *Ap = A + c_pass(2 * (nc + q) + 1) + l;
 #define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::syn_abs(Ap, aw[q])
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             }
         }
-        for (int p = 0; p < nc; ++p) {
-            const int md = sload(t.c_pass, 2 * p);
-            const T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
-            if (MAXD <= 8 || md <= 8) {
 #define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO>::syn(Ap)
-                ACG_PASS_SWITCH(md, ACG_CALL)
+#define ACG_BODY                                                       \
+    {                                                                  \
+        const int md = c_pass(2 * p);                                  \
+        const T *Ap = A + c_pass(2 * p + 1) + l;                       \
+        if (MAXD <= 8 || md <= 8) {                                    \
+            ACG_PASS_SWITCH(md, ACG_CALL)                              \
+        } else {                                                       \
+            U S = 0;                                                   \
+            for (int j = 0; j < md; ++j) S ^= B::to(Ap[j * L]);        \
+            acc |= S;                                                  \
+        }                                                              \
+    }
+        ACG_PASS_LOOP(STATIC, p, nc, ACG_BODY)
+#undef ACG_BODY
 #undef ACG_CALL
-            } else {
-                U S = 0;
-                for (int j = 0; j < md; ++j) S ^= B::to(Ap[j * L]);
-                acc |= S;
-            }
-        }
         return (acc & ONE) != 0;
     }
 
@@ -573,26 +627,29 @@ struct BpCore {
     // phi memo of the SATSKIP sweeps (abs_phi, wave-uniform mask am)
     __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar, const AbsLlr &ag, U am) {
         U acc = 0;
-        const int nc = t.n_cpass - n_apass();
-        for (int p = 0; p < nc; ++p) {
-            const int md = sload(t.c_pass, 2 * p);
-            T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
-            const int slot = p * L + l;
-            if (MAXD <= 8 || md <= 8) {
+        const int nc = n_cpass() - n_apass();
 #define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check(Ap, slot, ccnt, write, ms_scale)
-                ACG_PASS_SWITCH(md, ACG_CALL)
+#define ACG_BODY                                                       \
+    {                                                                  \
+        const int md = c_pass(2 * p);                                  \
+        T *Ap = A + c_pass(2 * p + 1) + l;                             \
+        const int slot = p * L + l;                                    \
+        if (MAXD <= 8 || md <= 8) {                                    \
+            ACG_PASS_SWITCH(md, ACG_CALL)                              \
+        } else {                                                       \
+            acc |= check_generic(Ap, slot, md, write);                 \
+        }                                                              \
+    }
+        ACG_PASS_LOOP(STATIC, p, nc, ACG_BODY)
+#undef ACG_BODY
 #undef ACG_CALL
-            } else {
-                acc |= check_generic(Ap, slot, md, write);
-            }
-        }
         // the absorbed passes (the last ones) with their register operands addressed directly: unrolled over q
 #pragma unroll
         for (int q = 0; q < NAP; ++q) {
             if (q < n_apass()) {
                 const int p = nc + q;
-                const int md = sload(t.c_pass, 2 * p);
-                T *Ap = A + sload(t.c_pass, 2 * p + 1) + l;
+                const int md = c_pass(2 * p);
+                T *Ap = A + c_pass(2 * p + 1) + l;
                 const int slot = p * L + l;
 #define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am)
                 ACG_PASS_SWITCH(md, ACG_CALL)
@@ -614,20 +671,23 @@ struct BpCore {
     }
 
     __device__ __forceinline__ void var_phase(const LlrRegs &lr, bool write) {
-        for (int p = 0; p < t.n_vpass; ++p) {
-            const int md = sload(t.v_pass, 2 * p);
-            const int ioff = sload(t.v_pass, 2 * p + 1);
-            const int slot = p * L + l;
-            const T llr = get_llr(lr, p, slot);
-            const uint16_t *ip = IDX + ioff + l;
-            if (MAXD <= 8 || md <= 8) {
 #define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write)
-                ACG_PASS_SWITCH(md, ACG_CALL)
+#define ACG_BODY                                                       \
+    {                                                                  \
+        const int md = v_pass(2 * p);                                  \
+        const int ioff = v_pass(2 * p + 1);                            \
+        const int slot = p * L + l;                                    \
+        const T llr = get_llr(lr, p, slot);                            \
+        const uint16_t *ip = IDX + ioff + l;                           \
+        if (MAXD <= 8 || md <= 8) {                                    \
+            ACG_PASS_SWITCH(md, ACG_CALL)                              \
+        } else {                                                       \
+            var_generic(ip, llr, slot, md, write);                     \
+        }                                                              \
+    }
+        ACG_PASS_LOOP(STATIC, p, n_vpass(), ACG_BODY)
+#undef ACG_BODY
 #undef ACG_CALL
-            } else {
-                var_generic(ip, llr, slot, md, write);
-            }
-        }
     }
 
     // var_phase that also returns the posterior hard decisions of this lane's variables (bit p = pass p); for the
@@ -796,25 +856,28 @@ struct BpCore {
     }
 
     __device__ __forceinline__ void var_init_phase(const LlrRegs &lr, bool write) {
-        for (int p = 0; p < t.n_vpass; ++p) {
-            const int md = sload(t.v_pass, 2 * p);
-            const int ioff = sload(t.v_pass, 2 * p + 1);
-            const int slot = p * L + l;
-            const T llr = get_llr(lr, p, slot);
-            const uint16_t *ip = IDX + ioff + l;
-            if (MAXD <= 8 || md <= 8) {
 #define ACG_CALL(D) BpPass<T, D, L, ALGO>::template var_init<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write)
-                ACG_PASS_SWITCH(md, ACG_CALL)
+#define ACG_BODY                                                                                       \
+    {                                                                                                  \
+        const int md = v_pass(2 * p);                                                                  \
+        const int ioff = v_pass(2 * p + 1);                                                            \
+        const int slot = p * L + l;                                                                    \
+        const T llr = get_llr(lr, p, slot);                                                            \
+        const uint16_t *ip = IDX + ioff + l;                                                           \
+        if (MAXD <= 8 || md <= 8) {                                                                    \
+            ACG_PASS_SWITCH(md, ACG_CALL)                                                              \
+        } else {                                                                                       \
+            const U hard = (llr <= (T) 0) ? ONE : (U) 0;                                               \
+            const T ax = B::from(B::to(llr) & ~SIGN);                                                  \
+            const T mg = (ALGO == 0) ? Dom<T>::phi(ax) : ax;                                           \
+            const U ob = (B::to(mg) & ~SIGN & ~ONE) | ((llr <= (T) 0) ? (hard | SIGN) : hard);         \
+            for (int k = 0; k < md; ++k)                                                               \
+                if (write && slot < vcnt[k + 1]) A[ip[k * L]] = B::from(ob);                           \
+        }                                                                                              \
+    }
+        ACG_PASS_LOOP(STATIC, p, n_vpass(), ACG_BODY)
+#undef ACG_BODY
 #undef ACG_CALL
-            } else {
-                const U hard = (llr <= (T) 0) ? ONE : (U) 0;
-                const T ax = B::from(B::to(llr) & ~SIGN);
-                const T mg = (ALGO == 0) ? Dom<T>::phi(ax) : ax;
-                const U ob = (B::to(mg) & ~SIGN & ~ONE) | ((llr <= (T) 0) ? (hard | SIGN) : hard);
-                for (int k = 0; k < md; ++k)
-                    if (write && slot < vcnt[k + 1]) A[ip[k * L]] = B::from(ob);
-            }
-        }
     }
 
     // ---- degree > 8: rolled loops (rare: high-rate codes); same arithmetic -------------------
@@ -882,7 +945,7 @@ struct BpCore {
     __device__ __forceinline__ uint32_t hard_bit(const LlrRegs &lr, int p) const {
         const int slot = p * L + l;
         if (slot < vcnt[1]) {
-            const int pos0 = IDX[sload(t.v_pass, 2 * p + 1) + l];
+            const int pos0 = IDX[v_pass(2 * p + 1) + l];
             return (uint32_t) (B::to(BpPass<T, 1, L, ALGO>::template at<IDXB>(A, pos0)) & ONE);
         }
         return (get_llr(lr, p, slot) <= (T) 0) ? 1u : 0u;  // isolated variable: estimate() == channel LLR
@@ -893,10 +956,13 @@ struct BpCore {
     __device__ __forceinline__ void pack_bits(const LlrRegs &lr, const VarIds &vi, const AbsWord &aw) {
         for (int w = l; w < t.nwords; w += L) OB[w] = 0u;
         group_sync<L>();
-        for (int p = 0; p < t.n_vpass; ++p) {
-            const int v = var_id<REGS>(vi, p);
-            if (v >= 0 && hard_bit(lr, p)) atomicOr(&OB[v >> 5], 1u << (v & 31));
-        }
+#define ACG_BODY                                                                   \
+    {                                                                              \
+        const int v = var_id<REGS>(vi, p);                                         \
+        if (v >= 0 && hard_bit(lr, p)) atomicOr(&OB[v >> 5], 1u << (v & 31));      \
+    }
+        ACG_PASS_LOOP(STATIC, p, n_vpass(), ACG_BODY)
+#undef ACG_BODY
 #pragma unroll
         for (int q = 0; q < NAP; ++q) {
             if (q < n_apass()) {
@@ -941,10 +1007,11 @@ constexpr int bp_min_waves() {
 // sweep and after the variable sweep of its LAST iteration (a.dbg_c2v / a.dbg_v2c: [frame][a_words]) together with the
 // channel LLRs in slot order (a.dbg_post: [frame][n_vpass * L]); the product instances are compiled with DBG = false.
 // SAT: the phi fast path of the sweeps (BpCore::SATSKIP; fixed-work decoders), see sat::bp_fused_kernel
-template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG, bool SAT>
+// PS: the pass structure policy (PassRuntime: any code; a static policy: the instances of bp_inst_spec.hip)
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG, bool SAT, typename PS = PassRuntime>
 __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using Core = BpCore<T, MAXD, L, ALGO, IDXLDS, NVP, IDXLDS && ACG_IDX_BYTES, SAT>;  // the LDS copy of the index table is in byte offsets
+    using Core = BpCore<T, MAXD, L, ALGO, IDXLDS, NVP, IDXLDS && ACG_IDX_BYTES, SAT, PS>;  // the LDS copy of the index table is in byte offsets
     constexpr int FPW = 64 / L;  // frames in flight per wavefront
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -967,13 +1034,14 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     // the instances with the freeze path (see `fz` below) and what they pay for its registers: the variable ids are read from the
     // table when a frame starts and when it is written out, not held for the whole kernel
     constexpr bool FREEZE = Core::SATSKIP && NVP > 0 && !DBG;  // (NVP > 0: the instances the host takes for fixed-work decoders)
-    constexpr bool VIREG = !FREEZE;
+    // (ACG_SPEC_VIREG: the static-policy instances, whose sweeps need fewer registers, hold them again — see DESIGN §3)
+    constexpr bool VIREG = !FREEZE || (PS::STATIC && ACG_SPEC_VIREG);
     typename Core::LlrRegs lr;
     typename Core::VarIds vi;
 #pragma unroll
     for (int p = 0; p < (NVP > 0 ? NVP : 1); ++p) {
         lr[p] = (T) 0;
-        vi[p] = (VIREG && NVP > 0 && p < t.n_vpass) ? t.v_var[p * L + l] : -1;
+        vi[p] = (VIREG && NVP > 0 && p < core.n_vpass()) ? t.v_var[p * L + l] : -1;
     }
     // absorbed degree-1 variables (BpPass::check_abs): LLR, v->c word, c->v word (debug trace only) per absorbed pass
     // and, in the SATSKIP instances, the phi memo of its check's other edges (Core::abs_phi; memo off: am = 0, ag = +inf)
@@ -1153,7 +1221,9 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
                     }
                     return llr;
                 };
-                for (int p = 0; p < t.n_vpass; ++p) core.set_llr(lr, p, p * L + l, chan_llr(core.template var_id<VIREG>(vi, p)));
+#define ACG_BODY core.set_llr(lr, p, p * L + l, chan_llr(core.template var_id<VIREG>(vi, p)));
+                ACG_PASS_LOOP(Core::STATIC, p, core.n_vpass(), ACG_BODY)
+#undef ACG_BODY
                 // absorbed variables: LLR and the constant v->c word (+0 for a lane without one)
 #pragma unroll
                 for (int q = 0; q < Core::NAP; ++q) {

@@ -326,6 +326,73 @@ bool bp_layout_build(const Code &c, int L, BpLayout &o, int max_apass) {
     return true;
 }
 
+// The lanes per frame a flooding decoder takes when the caller leaves them open: 256 / 1024 (one workgroup per frame) for a
+// code of node degree <= 8 whose message array leaves room for only a few wavefront-sized frames per CU, else the better of
+// 64 and 32.  0: a layout could not be built.
+int bp_default_lanes(const Code &c, bool f64) {
+    const int maxd = std::max(c.max_cdeg, c.max_vdeg);
+    if (maxd <= 8) {
+        const size_t ts0 = f64 ? 8 : 4;
+        const size_t wave_frame = ((size_t) c.E + 64 + ((size_t) c.n > 12 * 64 ? (size_t) c.n : 0)) * ts0;  // rough, L = 64
+        const int waves_cu = (int) std::min<size_t>(32, (160 * 1024) / std::max<size_t>(wave_frame, 1));
+        if (waves_cu < 12) {
+            // smallest workgroup that reaches >= 12 wavefronts per CU, else the largest
+            const size_t blk_frame = ((size_t) c.E * 5 / 4 + 256) * ts0;
+            const int L = (((160 * 1024) / std::max<size_t>(blk_frame, 1)) * 4 >= 12 && c.n <= 12 * 256) ? 256 : 1024;
+            if (c.n <= 12 * L) return L;
+        }
+    }
+    // A pass costs its largest degree for all L lanes, so finer groups waste fewer padded
+    // message slots (H05: 79% useful at L=64, 94% at L=32).  Measured on MI355X (H05, 50 it): fixed work
+    // 19.0 M frames/s at L=32 vs 17.2 M at L=64; early exit 68.6 M vs 65.3 M at -2 dB, 296 M vs 285 M at +2 dB.
+    BpLayout l64, l32;
+    if (!bp_layout_build(c, 64, l64) || !bp_layout_build(c, 32, l32)) return 0;
+    auto slots = [](const BpLayout &y) {
+        long s = 0;
+        for (int v : y.c_maxdeg) s += (long) v * y.L;
+        for (int v : y.v_maxdeg) s += (long) v * y.L;
+        return (double) s;
+    };
+    const double gain = slots(l64) / std::max(1.0, slots(l32));
+    return (gain > 1.05) ? 32 : 64;
+}
+
+// fp32 sum-product wave-group kernels with register LLRs: degree-1 variables absorbed into their checks (BpLayout::n_apass,
+// BpPass::check_abs).  `lay` becomes the absorbed layout when that layout runs that kernel variant, and stays as it is otherwise.
+bool bp_layout_absorb(const Code &c, int L, BpLayout &lay) {
+    BpLayout la;
+    if (!bp_layout_build(c, L, la, BP_MAX_APASS)) return false;
+    if (la.n_apass > 0 && la.n_vpass <= 12 && (size_t) std::max(la.a_words, (c.n + 3) & ~3) * 4 <= 65535) lay = std::move(la);
+    return true;
+}
+
+BpWavePlan bp_wave_plan(const Code &c, const BpLayout &lay, bool f64) {
+    BpWavePlan w;
+    const int maxd = std::max(c.max_cdeg, c.max_vdeg);
+    const size_t ts = f64 ? 8 : 4;
+    const int nwords = (c.n + 31) / 32;
+    // the MC path stages n symbols in the message array before clearing it
+    w.a_words = std::max(lay.a_words, (c.n + 3) & ~3);
+    // channel LLRs: in registers when there are at most 12 variable passes (degree <= 8 kernels), else in LDS
+    // the fused kernels keep their LDS copy of the variable-side index table in BYTE offsets (16 bits): the message
+    // array of a frame has to stay below 64 KiB for that copy (and the register-LLR instances, which require it)
+    w.a_fits16 = (size_t) w.a_words * ts <= 65535;
+    w.llr_regs = maxd <= 8 && lay.n_vpass <= 12 && w.a_fits16;
+    w.llr_words = w.llr_regs ? 0 : lay.n_vpass * lay.L;
+    w.per_frame = ((size_t) (w.a_words + w.llr_words) * ts + (size_t) nwords * 4 + 15) & ~(size_t) 15;
+    // the variable-side index table is read by every wave in every iteration: keep a block-shared
+    // copy in LDS unless it is large (then it is read through L1/L2)
+    w.idxlds = w.a_fits16 && ((size_t) lay.v_apos_len * 2 <= 16 * 1024 || w.llr_regs);
+    w.idx_lds_bytes = w.idxlds ? (int) (((size_t) lay.v_apos_len * 2 + 15) & ~(size_t) 15) : 0;
+    const int fpw = 64 / lay.L;
+    // waves per block: as many as fit in half the LDS (so at least two blocks share a CU), at most 4
+    w.waves = 4;
+    while (w.waves > 1 && w.per_frame * fpw * w.waves + w.idx_lds_bytes > 160 * 1024 / 2) w.waves >>= 1;
+    if (w.per_frame * fpw * w.waves + w.idx_lds_bytes > 160 * 1024) w.waves = 0;
+    w.variant = w.idxlds ? (w.llr_regs ? 2 : 1) : 0;
+    return w;
+}
+
 // ---------------------------------------------------------------- QP-ADMM groups
 // ConstructADMMProblem (qp_admm.h:13-102): a check of degree d >= 3 becomes the chain
 // (x1,x2,a1),(a1,x3,a2),...,(a_{d-3},x_{d-1},x_d) with auxiliaries numbered from n upward in row

@@ -148,6 +148,8 @@ struct acg_ldpc_decoder {
     int freeze_first = 0, freeze_period = 0;
     size_t freeze_slot_words = 0;
     acg::DeviceBuf freeze_ws;
+    // name of the build-time instance with this code's pass structure constant that the handle runs (bp_inst_spec.hip); null: the generic one
+    const char *spec = nullptr;
     bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
     bool blk_idxlds = false, blk_idxreg = false;
     // layered min-sum (bp_layered.hip)

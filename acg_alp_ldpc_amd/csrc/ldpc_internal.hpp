@@ -91,6 +91,23 @@ bool code_write_txt(const Code &c, const char *path);
 bool code_generator(const Code &c, uint8_t *G);
 bool code_is_codeword(const Code &c, const uint8_t *bits);
 bool bp_layout_build(const Code &c, int L, BpLayout &out, int max_apass = 0);
+int bp_default_lanes(const Code &c, bool f64);
+bool bp_layout_absorb(const Code &c, int L, BpLayout &lay);
+// What the handle set-up decides for a wavefront-group fused kernel (L = 16, 32, 64) from the code and its layout: where the
+// kernel keeps the LLRs and the index table, what a frame takes of LDS and how many wavefronts share a workgroup.  One
+// definition for the set-up (api.hip) and for the generator of the build-time instances (tools/bp_spec_gen.cpp).
+struct BpWavePlan {
+    int a_words = 0;        // message words: the layout's, or the n symbols (rounded up to 4) that the MC path stages there
+    bool a_fits16 = false;  // the message array stays below 64 KiB: 16-bit byte offsets address it
+    bool llr_regs = false;  // channel LLRs in registers (degree <= 8, at most 12 variable passes), else in LDS
+    bool idxlds = false;    // block-shared LDS copy of the variable-side index table
+    int llr_words = 0;
+    size_t per_frame = 0;   // LDS bytes per frame
+    int idx_lds_bytes = 0;
+    int waves = 0;          // wavefronts per workgroup (4, 2, 1); 0: one wavefront's frames do not fit in LDS
+    int variant = 0;        // kernel variant (bp_kernel_ptr): 0 index table global, 1 in LDS, 2 in LDS with the LLRs in registers
+};
+BpWavePlan bp_wave_plan(const Code &c, const BpLayout &lay, bool f64);
 void admm_layout_build(Code &c);
 // false (message via set_error) when the code exceeds the packing: >= 2^28 constraint rows or >= 2^30 variables
 bool admm_stream_tables_build(const Code &c, AdmmStreamTables &out);

@@ -1,6 +1,9 @@
 #!/bin/bash
 # Developer tool: disassembly of one kernel of the built library.
 #   tools/kernel_asm.sh <substring of the mangled kernel name> [library]
+# The instances of one kernel template differ in their namespace, which is part of the mangled name: bp_fused_kernelIfLi8ELi32E
+# matches the plain, the fixed-work (3sat15bp_fused_kernel...) and the build-time (12spec_H05_L3215bp_fused_kernel...) instances
+# alike and prints them one after the other, each under its own label; tools/kernel_regs.sh lists the names.
 set -e
 LIB=$(readlink -f "${2:-${ACG_LDPC_LIB:-$(dirname "$0")/../acg_alp_ldpc_amd/lib/libacg_ldpc_hip.so}}")
 TMP=$(mktemp -d)

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Developer tool: VGPR / SGPR / scratch / LDS of the kernels in the built library (from the code-object metadata).
 #   tools/kernel_regs.sh [name-filter]
+# The filter is a substring of the mangled OR of the demangled name: "sat::bp_fused_kernel<float, 8, 32" names the fixed-work
+# instances, "spec_H05_L32::" the build-time instances of one code (bp_inst_spec.hip), "spec_" all of those.
 set -e
 LIB=$(readlink -f "${ACG_LDPC_LIB:-$(dirname "$0")/../acg_alp_ldpc_amd/lib/libacg_ldpc_hip.so}")
 TMP=$(mktemp -d)
@@ -25,7 +27,7 @@ while True:
             mm = re.search(r"\." + key + r":\s+(\S+)", blk)
             return mm.group(1) if mm else "?"
         name = g("name")
-        if flt and flt not in name:
+        if flt and flt not in name and flt not in subprocess.run(["c++filt", name], capture_output=True, text=True).stdout:
             continue
         rows.append((name, g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size"), blk.split("\n")[0].strip()))
     pos = i + 4

@@ -11,6 +11,11 @@ kernel once — the sweep loops dominate the text of these kernels, and their bo
 masks), which bench.py reports next to the lower bound.
 
     python tools/valu_mix.py "bp_fused_kernel<float, 8, 32, 0, false, true, 12, false>" [library]
+
+The pattern is a substring of the demangled name.  Instances of one template in different namespaces (plain, sat:: for fixed
+work, spec_<name>:: with a code's pass structure constant) share everything behind the namespace: the command line reports
+every kernel that matches, each under its full name; put the namespace in front ("spec_H05_L32::bp_fused_kernel<float, 8, 32,
+0, false") to name one.  static_mix() keeps to the first match.
 """
 import os
 import re
@@ -85,21 +90,31 @@ def mix_of(insts):
             "cycles_per_valu": (CYC_FULL * n_full + CYC_HALF * n_half + CYC_TRANS * n_trans) / n}
 
 
-def static_mix(patterns, lib=None):
-    """patterns: {key: substring of the demangled kernel name} -> {key: mix dict of the first matching kernel}"""
+def static_mix(patterns, lib=None, namespace=None):
+    """patterns: {key: substring of the demangled kernel name} -> {key: mix dict of one matching kernel}: the first whose name
+    holds "<namespace>::" in front of the pattern's match when a namespace is given ("sat", "spec_H05_L32") and such a kernel
+    exists, else the first match"""
     kernels = disassemble(lib or default_lib())
     res = {}
     for key, pat in patterns.items():
-        for name, insts in kernels.items():
-            if pat in name:
-                m = mix_of(insts)
-                if m:
-                    m["kernel"] = name[:160]
-                    res[key] = m
-                break
+        names = [name for name in kernels if pat in name]
+        if namespace:
+            names = [name for name in names if (namespace + "::" + pat.split("<")[0].split("::")[-1]) in name] or names
+        for name in names[:1]:
+            m = mix_of(kernels[name])
+            if m:
+                m["kernel"] = name[:160]
+                res[key] = m
     return res
 
 
 if __name__ == "__main__":
-    r = static_mix({"k": sys.argv[1]}, sys.argv[2] if len(sys.argv) > 2 else None)
-    print(r.get("k", "no kernel matches"))
+    found = False
+    for name, insts in disassemble((sys.argv[2] if len(sys.argv) > 2 else None) or default_lib()).items():
+        m = mix_of(insts) if sys.argv[1] in name else None
+        if m:
+            m["kernel"] = name[:160]
+            print(m)
+            found = True
+    if not found:
+        print("no kernel matches")
