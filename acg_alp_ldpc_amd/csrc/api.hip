@@ -774,10 +774,11 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
         // the fixed-work fp32 sum-product instances only; equal signature, whatever the matrix); ACG_BP_NO_SPEC=1 keeps
         // the generic instance (A/B runs)
         if (sat && algo == 0 && !d->f64 && d->maxd <= 8 && variant == 2 && getenv("ACG_BP_NO_SPEC") == nullptr) {
-            const char *name = nullptr;
-            if (const void *ks = bp_spec_kernel_ptr(lay, mc != 0, &name)) {
+            const char *name = nullptr, *rows = nullptr;
+            if (const void *ks = bp_spec_kernel_ptr(lay, mc != 0, &name, &rows)) {
                 kp = ks;
                 d->spec = name;
+                d->spec_sat_rows = rows;
             }
         }
         if (int rc = bind_kernel(d, mc, kp)) return rc;
@@ -939,7 +940,9 @@ static std::string describe(const acg_ldpc_decoder *d) {
                                         " freeze_gate=" + (d->freeze_gate ? "1" : "0");
                 else t += " freeze=0";
             }
-            // the build-time instance with the code's pass structure constant that this handle runs (bp_inst_spec.hip), or 0
+            // the build-time instance with the code's pass structure constant that this handle runs (bp_inst_spec.hip), or 0; in
+            // front of it the rows of that instance that keep their phi fast-path test
+            if (d->spec && d->spec_sat_rows) t += std::string(" sat_rows=") + d->spec_sat_rows;
             t += std::string(" spec=") + (d->spec ? d->spec : "0");
             return t;
         }

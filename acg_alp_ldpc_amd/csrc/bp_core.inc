@@ -174,9 +174,28 @@ struct BpPass {
         if (!(ax >= (T) 66)) o = Dom<T>::phi(ax);
         return o;
     }
+    // The sweeps do not merge phi_c / phi_v's default value with phi's result: they form the word to store on both paths (the
+    // same bits; one copy of the default and the merge behind the branch less per row).
+    //   check side: sg = the sign of the outgoing message; the word is sg | magnitude bits of G, or of phi(s)
+    //   variable side: w = the sign and the hard-decision LSB; phi's magnitude bits are or-ed in unless phi is +0
+    // test: the row keeps its fast-path test (bit of the pass's row mask, see PassRuntime); without it phi is evaluated under
+    // the store predicate alone, which gives the same bits: phi(+0) = +inf, phi(>= 66) = +0, and the memo returns phi of the
+    // bits phi would see.
+    static __device__ __forceinline__ U word_c(T s, U mb, T G, U sg, bool test) {
+        if (!test) return (B::to(Dom<T>::phi(s)) & ~SIGN) | sg;
+        U w = (B::to(G) & ~SIGN) | sg;
+        if (B::to(s) != mb) w = (B::to(Dom<T>::phi(s)) & ~SIGN) | sg;
+        return w;
+    }
+    static __device__ __forceinline__ U word_v(T ax, U w, bool test) {
+        if (!test) return w | (B::to(Dom<T>::phi(ax)) & ~SIGN & ~ONE);
+        if (!(ax >= (T) 66)) w |= B::to(Dom<T>::phi(ax)) & ~SIGN & ~ONE;
+        return w;
+    }
 
     // check(), sum-product with the fast path: the exclude-self sums first, phi per edge under its store predicate
-    static __device__ __forceinline__ U check_sat(T *__restrict__ Ap, int slot, const int *cnt, bool write) {
+    // rows: bit j set = edge row j keeps its fast-path test (a constant of the pass: all ones, or a static policy's c_sat_rows)
+    static __device__ __forceinline__ U check_sat(T *__restrict__ Ap, int slot, const int *cnt, bool write, unsigned rows) {
         T x[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
@@ -199,10 +218,8 @@ struct BpPass {
         }
 #pragma unroll
         for (int j = 0; j < D; ++j) {
-            if (write && slot < cnt[j + 1]) {
-                const T o = phi_c(es[j]);
-                Ap[j * L] = B::from((B::to(o) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN));
-            }
+            if (write && slot < cnt[j + 1])
+                Ap[j * L] = B::from(word_c(es[j], (U) 0, (T) INFINITY, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u));
         }
         return S;
     }
@@ -235,8 +252,8 @@ struct BpPass {
     // UNI: every check of the code has degree D (the caller checked c_cnt_ge[D] == m): one write predicate for the whole
     // pass instead of one compare + EXEC mask + branch per edge
     template <bool UNI = false>
-    static __device__ __forceinline__ U check(T *__restrict__ Ap, int slot, const int *cnt, bool write, T ms_scale) {
-        if constexpr (SAT && ALGO == 0 && !UNI) return check_sat(Ap, slot, cnt, write);
+    static __device__ __forceinline__ U check(T *__restrict__ Ap, int slot, const int *cnt, bool write, T ms_scale, unsigned rows = ~0u) {
+        if constexpr (SAT && ALGO == 0 && !UNI) return check_sat(Ap, slot, cnt, write, rows);
         T x[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
@@ -313,9 +330,9 @@ struct BpPass {
     // SAT: the exclude-self sum of every edge but D - 1 contains aw's magnitude m, and once the check's other inputs have
     // saturated to +0 (or fall below half an ulp of m) it IS m, in every sweep that follows: the memo of phi_c holds m's
     // bits (aw & am; am = the magnitude mask, or 0 to turn the memo off) and ag = phi(m), built with aw (BpCore::abs_phi).
-    // Edge D - 1 keeps the +0 rule.
+    // Edge D - 1 keeps the +0 rule.  rows: as check_sat's, bit D - 1 is the register edge's.
     static __device__ __forceinline__ U check_abs(T *__restrict__ Ap, int slot, const int *cnt, bool write, U &aw, T allr, T &r_out,
-                                                  T ag = (T) INFINITY, U am = 0) {
+                                                  T ag = (T) INFINITY, U am = 0, unsigned rows = ~0u) {
         T x[D];
 #pragma unroll
         for (int j = 0; j < D - 1; ++j) x[j] = Ap[j * L];
@@ -342,13 +359,11 @@ struct BpPass {
             const U mb = aw & am;
 #pragma unroll
             for (int j = 0; j < D - 1; ++j) {
-                if (write && slot < cnt[j + 2]) {
-                    const T o = phi_c(out[j], mb, ag);
-                    Ap[j * L] = B::from((B::to(o) & ~SIGN) | ((S ^ B::to(x[j])) & SIGN));
-                }
+                if (write && slot < cnt[j + 2])
+                    Ap[j * L] = B::from(word_c(out[j], mb, ag, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u));
             }
             if (write && slot < cnt[1]) {
-                const T R = B::from((B::to(phi_c(out[D - 1])) & ~SIGN) | ((S ^ aw) & SIGN));
+                const T R = B::from(word_c(out[D - 1], (U) 0, (T) INFINITY, (S ^ aw) & SIGN, (rows >> (D - 1)) & 1u));
                 r_out = R;
                 aw = (aw & ~ONE) | ((allr + R <= (T) 0) ? ONE : (U) 0);
             }
@@ -381,17 +396,19 @@ struct BpPass {
         return BYTES ? *reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(A) + pos) : A[pos];
     }
     template <typename IdxPtr, bool BYTES = false>
-    static __device__ __forceinline__ U var(T *__restrict__ A, IdxPtr ip, T llr, int slot, const int *cnt, bool write) {
+    static __device__ __forceinline__ U var(T *__restrict__ A, IdxPtr ip, T llr, int slot, const int *cnt, bool write, unsigned rows = ~0u) {
         int pos[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) pos[k] = ip[k * L];
-        return var_at<false, BYTES>(A, pos, llr, slot, cnt, write);
+        return var_at<false, BYTES>(A, pos, llr, slot, cnt, write, rows);
     }
 
     // the same sweep with the D message positions already known (register-resident index table)
     // Returns the posterior hard decision (0 / 1).
+    // rows (SAT): bit k set = edge row k keeps its fast-path test, as check_sat's
     template <bool UNI = false, bool BYTES = false>
-    static __device__ __forceinline__ U var_at(T *__restrict__ A, const int (&pos)[D], T llr, int slot, const int *cnt, bool write) {
+    static __device__ __forceinline__ U var_at(T *__restrict__ A, const int (&pos)[D], T llr, int slot, const int *cnt, bool write,
+                                               unsigned rows = ~0u) {
         T c[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) c[k] = at<BYTES>(A, pos[k]);
@@ -415,10 +432,8 @@ struct BpPass {
             }
 #pragma unroll
             for (int k = 0; k < D; ++k) {
-                if (write && slot < cnt[k + 1]) {
-                    const T mg = phi_v(B::from(B::to(xs[k]) & ~SIGN));
-                    at<BYTES>(A, pos[k]) = B::from((B::to(mg) & ~SIGN & ~ONE) | ((xs[k] <= (T) 0) ? hard_neg : hard));
-                }
+                if (write && slot < cnt[k + 1])
+                    at<BYTES>(A, pos[k]) = B::from(word_v(B::from(B::to(xs[k]) & ~SIGN), (xs[k] <= (T) 0) ? hard_neg : hard, (rows >> k) & 1u));
             }
             return hard;
         }
@@ -471,8 +486,15 @@ struct BpPass {
 //   The pass loops are then unrolled at compile time: the switch on the degree, the table loads, the register indexing
 //   and every store predicate that is true (or false) for a whole pass fold away.  The index tables, the messages and
 //   all arithmetic are the run-time policy's, so the results are the same bit for bit.
+// The phi fast-path tests are a per-row property of the policy as well: c_sat_rows(p) / v_sat_rows(p), bit j set = edge row j
+// of check / variable pass p keeps its test (BpPass::word_c / word_v; in an absorbed pass bit D - 1 is the register edge, the
+// bits below it the memo rows).  The mask reaches the sweeps as an argument that is a constant once the unrolled pass loop is
+// inlined, like the pass tables.  The generator can clear rows from a census of the code (tools/bp_spec_gen.cpp -t); by default,
+// and in the run-time policy, every row keeps its test: on H05 no cleared row measured faster (DESIGN §3).
 struct PassRuntime {
     static constexpr bool STATIC = false;
+    static constexpr unsigned c_sat_rows(int) { return ~0u; }
+    static constexpr unsigned v_sat_rows(int) { return ~0u; }
 };
 // the pass loops: `for (p = 0 .. n - 1) BODY` as a loop (run-time policy) or as straight-line code (static policy: n is one
 // of its constants).  BODY is a macro that holds the braces of the loop body.
@@ -628,7 +650,7 @@ struct BpCore {
     __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar, const AbsLlr &ag, U am) {
         U acc = 0;
         const int nc = n_cpass() - n_apass();
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check(Ap, slot, ccnt, write, ms_scale)
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check(Ap, slot, ccnt, write, ms_scale, PS::c_sat_rows(p))
 #define ACG_BODY                                                       \
     {                                                                  \
         const int md = c_pass(2 * p);                                  \
@@ -651,7 +673,7 @@ struct BpCore {
                 const int md = c_pass(2 * p);
                 T *Ap = A + c_pass(2 * p + 1) + l;
                 const int slot = p * L + l;
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am)
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am, PS::c_sat_rows(p))
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             }
@@ -671,7 +693,7 @@ struct BpCore {
     }
 
     __device__ __forceinline__ void var_phase(const LlrRegs &lr, bool write) {
-#define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write)
+#define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write, PS::v_sat_rows(p))
 #define ACG_BODY                                                       \
     {                                                                  \
         const int md = v_pass(2 * p);                                  \

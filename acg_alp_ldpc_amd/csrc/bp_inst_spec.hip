@@ -24,11 +24,12 @@ struct BpSpecEntry {
 
 static const BpSpecEntry spec_entries[] = {ACG_BP_SPEC_ENTRIES {{nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr}}};
 
-// the instance whose signature equals the layout's (bp_spec_matches), or null; *name: the entry's
-const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name) {
+// the instance whose signature equals the layout's (bp_spec_matches), or null; *name, *sat_rows: the entry's
+const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name, const char **sat_rows) {
     for (const BpSpecEntry *e = spec_entries; e->sig.name; ++e) {
         if (bp_spec_matches(e->sig, lay)) {
             if (name) *name = e->sig.name;
+            if (sat_rows) *sat_rows = e->sig.sat_rows;
             return e->kernel[mc ? 1 : 0];
         }
     }

@@ -23,6 +23,10 @@ struct BpSpecSig {
     const int32_t *v_pass;    // [n_vpass][2] = {largest degree, index-table offset}
     const int32_t *c_cnt_ge;  // [BP_SPEC_NCNT]
     const int32_t *v_cnt_ge;  // [BP_SPEC_NCNT]
+    // Not part of the match: the rows of the instance that keep their phi fast-path test (the policy's c_sat_rows / v_sat_rows,
+    // hexadecimal, one mask per pass: "c:7f,3f,30,1f,f/v:3f,...") with the census SNR and threshold they come from; results do
+    // not depend on them
+    const char *sat_rows = nullptr;
 };
 
 // the signature's tables of a layout, owned

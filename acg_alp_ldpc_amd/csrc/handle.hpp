@@ -150,6 +150,7 @@ struct acg_ldpc_decoder {
     acg::DeviceBuf freeze_ws;
     // name of the build-time instance with this code's pass structure constant that the handle runs (bp_inst_spec.hip); null: the generic one
     const char *spec = nullptr;
+    const char *spec_sat_rows = nullptr;  // that instance's fast-path row masks (BpSpecSig::sat_rows), for describe()
     bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
     bool blk_idxlds = false, blk_idxreg = false;
     // layered min-sum (bp_layered.hip)

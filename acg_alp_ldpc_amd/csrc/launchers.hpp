@@ -25,7 +25,7 @@ const void *bp_kernel_ptr_spa_f64_dbg(int L);
 
 // ---- bp_inst_spec.hip: build-time instances with a code's pass structure constant (bp_spec.hpp) ----
 struct BpLayout;  // ldpc_internal.hpp
-const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name);
+const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name, const char **sat_rows = nullptr);
 
 // ---- bp_kernels.hip ----
 const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat);

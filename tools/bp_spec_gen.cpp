@@ -2,13 +2,19 @@
 // the fused fixed-work sum-product kernel with the code's pass structure as compile-time constants (bp_core.inc, static pass
 // policy).  Host only; csrc/Makefile builds and runs it:
 //   g++ -O2 -std=c++17 -Iinclude tools/bp_spec_gen.cpp acg_alp_ldpc_amd/csrc/code.cpp -o bp_spec_gen
-//   bp_spec_gen [-o out.inc] [--print] <matrix.txt>[:L] ...          (L = 16, 32 or 64; 0 or none: the library's own choice)
+//   bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] <matrix.txt>[:L] ...
+//                                                                     (L = 16, 32 or 64; 0 or none: the library's own choice)
 // Per pair it calls bp_layout_build the way the handle set-up does (absorbed degree-1 variables included) and writes
 //   namespace spec_<name> { struct Pass (the constexpr tables); the kernel bp_fused_kernel<...>; the signature arrays }
 // and one line of the registry macro ACG_BP_SPEC_ENTRIES: name, L, signature, kernel pointers (MC off / on).  <name> is the
 // file's base name and the group width, e.g. H05_L32.  A pair whose layout does not take the fp32 sum-product, degree <= 8,
 // register-LLR fixed-work path is skipped with a message.  --print: the structure of every accepted pair as plain lines on
 // stdout (name / c_pass / v_pass / c_cnt_ge / v_cnt_ge / n_apass), the histograms as the layout holds them.
+// The policy also says which edge rows keep their phi fast-path test (c_sat_rows / v_sat_rows, bp_core.inc): the tool runs the census
+// of csrc/bp_sat_census.hpp on the layout (300 frames of at most 50 sweeps, stopped at their first state repeat, at -s dB; default
+// -2) and clears the bit of every row whose share of fully skipped units is below -t per cent (default: SAT_ROWS_T below).  -t 0
+// keeps every test without running the census, -t 101 clears all.  The masks, the SNR and the threshold stand in the include as a
+// comment, as the two look-ups and as the registry's sat_rows string.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -17,12 +23,29 @@
 #include <string>
 #include <vector>
 
+#include "../acg_alp_ldpc_amd/csrc/bp_sat_census.hpp"
 #include "../acg_alp_ldpc_amd/csrc/bp_spec.hpp"
 
 namespace acg {
 void set_error(const std::string &msg) { fprintf(stderr, "bp_spec_gen: %s\n", msg.c_str()); }
 }
 using namespace acg;
+
+// default of -t: every row keeps its test.  On H05 every threshold that clears a row measured slower than none at -3, -2 and
+// +2 dB (profiles/r15_satrows_summary.md), so clearing rows is an option for a code it is measured to pay on
+static const double SAT_ROWS_T = 0.0;
+static const int CENSUS_FRAMES = 300, CENSUS_SWEEPS = 50;
+
+static std::string hexlist(const std::vector<uint32_t> &v, const std::vector<int32_t> &pass) {
+    std::string s;
+    char b[16];
+    for (size_t p = 0; p < v.size(); p++) {
+        const int D = pass[2 * p];  // the rows the pass has
+        snprintf(b, sizeof b, "%s%x", p ? "," : "", (unsigned) (v[p] & (D >= 32 ? ~0u : ((1u << D) - 1u))));
+        s += b;
+    }
+    return s;
+}
 
 static std::string list(const std::vector<int32_t> &v) {
     std::string s;
@@ -47,14 +70,17 @@ static bool spec_layout(const Code &c, int L, BpLayout &lay, std::string &why) {
 int main(int argc, char **argv) {
     const char *out_path = nullptr;
     bool print = false;
+    double snr = -2.0, thr = SAT_ROWS_T;
     std::vector<std::string> pairs;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-o") && i + 1 < argc) out_path = argv[++i];
         else if (!strcmp(argv[i], "--print")) print = true;
+        else if (!strcmp(argv[i], "-s") && i + 1 < argc) snr = atof(argv[++i]);
+        else if (!strcmp(argv[i], "-t") && i + 1 < argc) thr = atof(argv[++i]);
         else pairs.push_back(argv[i]);
     }
     if (pairs.empty() && !out_path) {
-        fprintf(stderr, "usage: bp_spec_gen [-o out.inc] [--print] <matrix.txt>[:L] ...\n");
+        fprintf(stderr, "usage: bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] <matrix.txt>[:L] ...\n");
         return 2;
     }
     std::string text = "// generated by tools/bp_spec_gen.cpp from SPEC_CODES (csrc/Makefile): do not edit, do not commit\n";
@@ -93,9 +119,18 @@ int main(int argc, char **argv) {
             continue;
         }
         const BpSpecTables s = bp_spec_tables(lay);
+        // the rows that keep their fast-path test
+        SatRows rows;
+        if (thr > 0) rows = bp_sat_rows(bp_sat_census(c, lay, CENSUS_FRAMES, CENSUS_SWEEPS, snr, true), thr);
+        else rows = bp_sat_rows(bp_sat_census_empty(lay), 0);
+        char snr_s[24], thr_s[24];
+        snprintf(snr_s, sizeof snr_s, "%g", snr);
+        snprintf(thr_s, sizeof thr_s, "%g", thr);
+        const std::string rows_str = "c:" + hexlist(rows.c, s.c_pass) + "/v:" + hexlist(rows.v, s.v_pass) + "@" + snr_s + "dB,t" + thr_s;
         if (print) {
             printf("name = %s\nL = %d\nc_pass = %s\nv_pass = %s\nc_cnt_ge = %s\nv_cnt_ge = %s\nn_apass = %d\n", name.c_str(), L, list(s.c_pass).c_str(),
                    list(s.v_pass).c_str(), list(lay.c_cnt_ge).c_str(), list(lay.v_cnt_ge).c_str(), lay.n_apass);
+            fprintf(stderr, "bp_spec_gen: %s sat_rows %s\n", name.c_str(), rows_str.c_str());
         }
         const std::string ns = "spec_" + name;
         auto lookup = [&](const char *fn, const std::vector<int32_t> &v) {
@@ -107,6 +142,14 @@ int main(int argc, char **argv) {
         text += "    static constexpr int n_cpass = " + std::to_string(s.n_cpass) + ", n_apass = " + std::to_string(s.n_apass) +
                 ", n_vpass = " + std::to_string(s.n_vpass) + ";\n";
         text += lookup("c_pass", s.c_pass) + lookup("v_pass", s.v_pass) + lookup("c_cnt_ge", s.c_cnt_ge) + lookup("v_cnt_ge", s.v_cnt_ge);
+        auto ulookup = [&](const char *fn, const std::vector<uint32_t> &v) {
+            std::string l;
+            for (size_t i = 0; i < v.size(); i++) l += (i ? "," : "") + std::to_string(v[i]) + "u";
+            return "    static constexpr unsigned " + std::string(fn) + "(int p) {\n        constexpr unsigned v[] = {" + l + "};\n        return v[p];\n    }\n";
+        };
+        text += "    // rows that keep their phi fast-path test (bit j = edge row j of the pass): census at " + std::string(snr_s) + "dB, threshold " + thr_s +
+                " per cent of fully skipped units\n    // " + rows_str + "\n";
+        text += ulookup("c_sat_rows", rows.c) + ulookup("v_sat_rows", rows.v);
         text += "};\n";
         text += "template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>\n"
                 "__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {\n"
@@ -115,7 +158,7 @@ int main(int argc, char **argv) {
         text += "}  // namespace " + ns + "\n";
         const std::string k = "(const void *) " + ns + "::bp_fused_kernel<float, 8, " + std::to_string(L) + ", 0, ";
         entries += " \\\n    {{\"" + name + "\", " + std::to_string(L) + ", " + std::to_string(s.n_cpass) + ", " + std::to_string(s.n_apass) + ", " +
-                   std::to_string(s.n_vpass) + ", " + ns + "::sig_c_pass, " + ns + "::sig_v_pass, " + ns + "::sig_c_cnt_ge, " + ns + "::sig_v_cnt_ge}, {" + k +
+                   std::to_string(s.n_vpass) + ", " + ns + "::sig_c_pass, " + ns + "::sig_v_pass, " + ns + "::sig_c_cnt_ge, " + ns + "::sig_v_cnt_ge, \"" + rows_str + "\"}, {" + k +
                    "false, true, BP_NVP>, " + k + "true, true, BP_NVP>}},";
     }
     text += "\n#define ACG_BP_SPEC_ENTRIES" + entries + "\n";
