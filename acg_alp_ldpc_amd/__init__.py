@@ -9,7 +9,7 @@ from ._lib import (ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED, EVENT_NO_WORD, EV
 from .channel import gen_random_codewords, llr, llr_variance, transmit_frames  # noqa: F401
 from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
-from .decoder import BeliefPropagationDecoder, Decoder, MinSumDecoder, QPADMMDecoder  # noqa: F401
+from .decoder import BeliefPropagationDecoder, Decoder, MinSumDecoder, QPADMMDecoder, QuantConfig, QuantizedMinSumDecoder  # noqa: F401
 from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_exp_details, merge_exp_results,  # noqa: F401
                          run_experiment, run_experiment_codes, run_experiment_detail, run_experiment_grid,
                          run_experiment_inproc, run_experiment_sharded, shard_range)

@@ -25,6 +25,12 @@ class Params(C.Structure):
                 ("engine", C.c_int32), ("fast_setup", C.c_int32), ("schedule", C.c_int32)]
 
 
+class Quant(C.Structure):
+    """acg_ldpc_quant: the quantiser of the fixed-point layered min-sum engine (32 bytes)"""
+    _fields_ = [("llr_step", C.c_double), ("ch_bits", C.c_int32), ("msg_bits", C.c_int32), ("post_bits", C.c_int32),
+                ("scale_num", C.c_int32), ("scale_shift", C.c_int32), ("offset", C.c_int32)]
+
+
 class McCfg(C.Structure):
     _fields_ = [("frames", C.c_int64), ("first_frame", C.c_int64), ("snr", C.c_double), ("seed", C.c_uint64),
                 ("noise", C.c_int32), ("codewords", C.c_void_p), ("n_codewords", C.c_int64)]
@@ -72,6 +78,10 @@ SYMBOLS = {
     "acg_ldpc_code_generator": (C.c_int, [_vp, _vp]),
     "acg_ldpc_code_is_codeword": (C.c_int, [_vp, _vp]),
     "acg_ldpc_decoder_create": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(_vp)]),
+    "acg_ldpc_quant_default": (None, [C.POINTER(Quant)]),
+    "acg_ldpc_quant_check": (C.c_int, [C.POINTER(Quant)]),
+    "acg_ldpc_decoder_create_quantized": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(Quant), C.POINTER(_vp)]),
+    "acg_ldpc_debug_quantize": (C.c_int, [_vp, _i32, _i64, _f64, C.POINTER(Quant), _vp]),
     "acg_ldpc_decoder_destroy": (None, [_vp]),
     "acg_ldpc_decoder_name": (C.c_char_p, [_vp]),
     "acg_ldpc_decode_batch": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp]),

@@ -446,6 +446,112 @@ static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L, bool wide = f
     return 0;
 }
 
+// acg_ldpc_quant -> what the kernel reads
+QuantArgs acg::quant_args(const acg_ldpc_quant &q) {
+    QuantArgs a{};
+    a.inv_step = (float) (1.0 / q.llr_step);
+    a.cmax = (1 << (q.ch_bits - 1)) - 1;
+    a.rmax = (1 << (q.msg_bits - 1)) - 1;
+    a.pmax = (1 << (q.post_bits - 1)) - 1;
+    a.scale_num = q.scale_num;
+    a.scale_shift = q.scale_shift;
+    a.rnd = q.scale_shift > 0 ? 1 << (q.scale_shift - 1) : 0;
+    a.offset = q.offset;
+    return a;
+}
+
+// the rules of acg_ldpc_quant (include/acg_ldpc.h); host only
+static int quant_check(const acg_ldpc_quant *q) {
+    if (!q) {
+        set_error("null quantiser");
+        return 1;
+    }
+    const char *why = nullptr;
+    if (!(std::isfinite(q->llr_step) && q->llr_step > 0)) why = "llr_step must be finite and > 0";
+    else if (q->post_bits < 2 || q->post_bits > 16) why = "post_bits must be 2 ... 16";
+    else if (q->ch_bits < 2 || q->ch_bits > q->post_bits) why = "ch_bits must be 2 ... post_bits";
+    else if (q->msg_bits < 2 || q->msg_bits > 8 || q->msg_bits > q->post_bits) why = "msg_bits must be 2 ... 8 and <= post_bits";
+    else if (q->scale_shift < 0 || q->scale_shift > 8) why = "scale_shift must be 0 ... 8";
+    else if (q->scale_num < 1 || q->scale_num > (1 << q->scale_shift)) why = "scale_num must be 1 ... 2^scale_shift";
+    else if (q->offset < 0 || q->offset > (1 << (q->msg_bits - 1)) - 1) why = "offset must be 0 ... 2^(msg_bits-1) - 1";
+    if (why) {
+        set_error(std::string("invalid quantiser: ") + why);
+        return 3;
+    }
+    return 0;
+}
+
+// what acg_ldpc_decoder_create_quantized requires of the params (include/acg_ldpc.h); host only
+static int quant_params_check(const acg_ldpc_params &p) {
+    const char *why = nullptr;
+    if (p.algo != ACG_LDPC_BP_MINSUM) why = "algo must be ACG_LDPC_BP_MINSUM";
+    else if (p.schedule != ACG_LDPC_SCHEDULE_LAYERED) why = "schedule must be ACG_LDPC_SCHEDULE_LAYERED";
+    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (the number formats are the quantiser's)";
+    else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_FUSED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_FUSED (the state lives in LDS)";
+    else if (p.lanes_per_frame != 0 && p.lanes_per_frame != 64 && p.lanes_per_frame != 128 && p.lanes_per_frame != 256 && p.lanes_per_frame != 512 &&
+             p.lanes_per_frame != 1024)
+        why = "lanes_per_frame must be 0, 64, 128, 256, 512 or 1024";
+    if (why) {
+        set_error(std::string("quantized layered min-sum: ") + why);
+        return 3;
+    }
+    return 0;
+}
+
+// The fixed-point layered min-sum engine (bp_layered_q.hip): the sets and steps of decoder_setup_layered_block with the degree
+// cap 32, int16 posteriors and one byte per edge in LDS.  L = 0: the smallest of 64 ... 1024 that holds the largest set, else 1024.
+static int decoder_setup_layered_q(acg_ldpc_decoder *d) {
+    const Code &c = d->c;
+    if (!bp_layered_block_build(c, d->lblay, 32)) return 3;
+    const LayeredBlockLayout &ll = d->lblay;
+    int L = d->p.lanes_per_frame;
+    if (L == 0) {
+        L = 64;
+        while (L < 1024 && L < ll.width) L <<= 1;
+    }
+    LayerBlockTables &t = d->lbtab;
+    t.n = c.n;
+    t.nwords = (c.n + 31) / 32;
+    t.e = ll.e;
+    t.n_sets = ll.n_sets;
+    t.p_words = (((c.n + 1 + 7) & ~7) * 2) / 4;   // int16 cells, n + the neutral cell, padded to 16 bytes
+    t.r_words = (ll.e + 3) / 4;                   // one byte per edge
+    const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
+    const void *kp = bp_layered_q_kernel_ptr(L);
+    if (!kp) {
+        set_error("no quantized layered kernel instance for this lanes_per_frame");
+        return 3;
+    }
+    hipFuncAttributes fa{};
+    HIP_OK(hipFuncGetAttributes(&fa, kp));
+    if (lds + fa.sharedSizeBytes > 160 * 1024 || c.n >= (1 << 30)) {   // (sharedSizeBytes: the kernel's few control words)
+        set_error("quantized layered min-sum: a frame (posteriors + messages) does not fit in LDS");
+        return 3;
+    }
+    std::vector<int32_t> step, pos2(ll.pos.size());
+    bp_layered_block_steps(ll, L, step);
+    for (size_t i = 0; i < ll.pos.size(); i++) pos2[i] = 2 * ll.pos[i];
+    d->lb_step = upload(step, 8);
+    d->lb_pos = upload(pos2);
+    if (!d->lb_step.p || !d->lb_pos.p) return 10;
+    t.step = d->lb_step.as<const int32_t>();
+    t.pos = d->lb_pos.as<const int32_t>();
+    t.n_steps = (int) (step.size() / 8);
+    d->layered_block = true;   // (decode only: Monte-Carlo runs take the unfused route of the workgroup layered engines)
+    d->layered_q = true;
+    d->qargs = quant_args(d->quant);
+    d->L = L;
+    d->f64 = 0;
+    d->block = L;
+    d->frames_per_block = 1;
+    d->lds_block = lds;
+    if (int rc = bind_kernel(d, 0, kp)) return rc;
+    d->kernel[1] = nullptr;
+    d->grid_cap[1] = d->grid_cap[0];
+    d->tab.lds_bytes_per_frame = (int32_t) lds;
+    return 0;
+}
+
 // schedule = LAYERED: min-sum over conflict-free layers of checks with in-place posteriors (bp_layered.hip)
 static int decoder_setup_layered(acg_ldpc_decoder *d) {
     const Code &c = d->c;
@@ -787,7 +893,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
 }
 
 int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                      hipStream_t on_stream) {
+                                      hipStream_t on_stream, const acg_ldpc_quant *quant) {
     if (!code || !params || !out) {
         set_error("null argument");
         return 1;
@@ -795,6 +901,14 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
     if (params->max_iter < 0) {
         set_error("max_iter must be >= 0");
         return 1;
+    }
+    if (quant) {   // (host-only refusals first: they need no device)
+        if (int rc = quant_check(quant)) return rc;
+        if (int rc = quant_params_check(*params)) return rc;
+        if (code->c.max_cdeg > 32) {
+            set_error("quantized layered min-sum: check degree above 32 is not supported");
+            return 3;
+        }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -832,7 +946,11 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
                 evok = evok && hipEventCreate(&d->ring_ev0[k]) == hipSuccess && hipEventCreate(&d->ring_ev[k]) == hipSuccess;
             if (!evok) { set_error("hipEventCreate failed"); rc = 10; break; }
         }
-        if (params->algo == ACG_LDPC_QPADMM) {
+        if (quant) {
+            d->name = "QMS";
+            d->quant = *quant;
+            rc = decoder_setup_layered_q(d);
+        } else if (params->algo == ACG_LDPC_QPADMM) {
             d->name = "QP-ADMM";  // qp_admm.h:189
             std::string err;
             d->admm.reset(admm_device_create(d->c, d->p, d->cu_count, err));
@@ -854,6 +972,32 @@ extern "C" {
 
 int acg_ldpc_decoder_create(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out) {
     return guarded([&] { return acg_ldpc_decoder_create_impl(code, params, out); });
+}
+
+void acg_ldpc_quant_default(acg_ldpc_quant *q) {
+    if (!q) return;
+    q->llr_step = 0.5;
+    q->ch_bits = 6;
+    q->msg_bits = 6;
+    q->post_bits = 8;
+    q->scale_num = 1;
+    q->scale_shift = 0;
+    q->offset = 1;
+}
+
+int acg_ldpc_quant_check(const acg_ldpc_quant *q) {
+    return guarded([&] { return quant_check(q); });
+}
+
+int acg_ldpc_decoder_create_quantized(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
+                                      acg_ldpc_decoder **out) {
+    return guarded([&] {
+        if (!q) {
+            set_error("null argument");
+            return 1;
+        }
+        return acg_ldpc_decoder_create_impl(code, params, out, nullptr, q);
+    });
 }
 
 void acg_ldpc_decoder_destroy(acg_ldpc_decoder *d) {
@@ -920,6 +1064,13 @@ static std::string describe(const acg_ldpc_decoder *d) {
             }
             return t;
         }
+    } else if (d->layered_q) {
+        const acg_ldpc_quant &q = d->quant;
+        snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_q_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
+                               "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=int8 posteriors=int16 "
+                               "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d",
+                 algo, d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width, q.llr_step, q.ch_bits, q.msg_bits,
+                 q.post_bits, q.scale_num, q.scale_shift, q.offset);
     } else if (d->layered_block) {
         snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
                                "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=%s",

@@ -154,7 +154,8 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
             return 11;
         }
         const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
-        if (d->layered_wide) HIP_OK(bp_layered_wide_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
+        if (d->layered_q) HIP_OK(bp_layered_q_launch(d->kernel[0], d->lbtab, a, d->qargs, grid, d->block, d->lds_block, s));
+        else if (d->layered_wide) HIP_OK(bp_layered_wide_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
         else HIP_OK(bp_layered_block_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
     } else if (d->layered) {
         const int mc = a.mc ? 1 : 0;

@@ -160,6 +160,10 @@ struct acg_ldpc_decoder {
     // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory
     bool layered_block = false;
     bool layered_wide = false;  // (with layered_block) the kernel is bp_layered_wide_kernel: check degree up to 32, same tables
+    // (with layered_block) the kernel is bp_layered_q_kernel: fixed-point min-sum, handles of acg_ldpc_decoder_create_quantized only
+    bool layered_q = false;
+    acg_ldpc_quant quant{};
+    acg::QuantArgs qargs{};
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
@@ -218,9 +222,11 @@ namespace acg {
 struct DecoderDrop { void operator()(acg_ldpc_decoder *x) const { acg_ldpc_decoder_destroy(x); } };
 using DecoderPtr = std::unique_ptr<acg_ldpc_decoder, DecoderDrop>;
 
-// ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own) ----
+// ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own;
+// quant != null: the fixed-point layered min-sum engine of acg_ldpc_decoder_create_quantized) ----
 int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                 hipStream_t on_stream = nullptr);
+                                 hipStream_t on_stream = nullptr, const acg_ldpc_quant *quant = nullptr);
+QuantArgs quant_args(const acg_ldpc_quant &q);
 
 // ---- decode.hip ----
 double channel_sigma(double snr);

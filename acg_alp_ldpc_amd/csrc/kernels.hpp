@@ -133,6 +133,15 @@ struct LayerBlockTables {
     int32_t r_words;         // 32-bit words the e message cells occupy (e, or half of it rounded up for fp16 storage)
 };
 
+// Fixed-point layered min-sum (bp_layered_q.hip): acg_ldpc_quant as the kernel reads it.  The tables are LayerBlockTables with
+// two differences: pos holds byte offsets of 2-byte posterior cells, and p_words / r_words count the 32-bit words of the
+// int16 posteriors (+ neutral cell, padded) and of the one-byte message cells.
+struct QuantArgs {
+    float inv_step;   // (float) (1 / llr_step)
+    int32_t cmax, rmax, pmax;
+    int32_t scale_num, scale_shift, rnd, offset;   // rnd = 2^(scale_shift - 1), 0 for scale_shift = 0
+};
+
 // Streamed ("HBM") BP engine: plain CSR of the Tanner graph, read through scalar loads.
 struct StreamTables {
     const int32_t *row_ptr;   // [m+1] edges in check-major order (variables ascending)

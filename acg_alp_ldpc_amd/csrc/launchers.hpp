@@ -75,6 +75,13 @@ const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo);
 hipError_t bp_layered_wide_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
                                   hipStream_t s);
 
+// ---- bp_layered_q.hip (fixed-point layered min-sum, check degree up to 32; L = 64, 128, 256, 512, 1024) ----
+const void *bp_layered_q_kernel_ptr(int L);
+hipError_t bp_layered_q_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs &q, int grid, int block,
+                               size_t lds, hipStream_t s);
+// the kernel's quantiser on `count` symbols (a: y, y_is_f64 and the channel terms) -> count int16
+hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_t count, int16_t *out, hipStream_t s);
+
 // ---- bp_streamed.hip ----
 const void *bp_streamed_ptr(int algo, int f64);
 const void *bp_streamed_ring_ptr(int algo, bool nt);

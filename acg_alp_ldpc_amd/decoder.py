@@ -3,18 +3,20 @@
     BeliefPropagationDecoder(max_iter)                     algo/bp.h:208-222
     QPADMMDecoder(alpha, mu, max_iter=2000, eps_stop=1e-5) algo/qp_admm.h:180-194
     MinSumDecoder(max_iter, scale)                         build-added, not in the reference
+    QuantizedMinSumDecoder(max_iter, quant)                build-added, not in the reference: fixed-point layered min-sum
 
     decode(H, channel_word, snr) -> (codeword, ok)         same argument meaning as algo/algo.h:8:
         H: m x n 0/1 matrix (or a ParityCheckMatrix), channel_word: n raw channel symbols y
         (NOT LLRs), snr: Es/N0 in dB.  BP failure returns (empty array, False) like bp.h:198.
     decode_batch(H, Y, snr) -> (bits[F,n], ok[F], iters[F])
-    name() -> "BP" / "QP-ADMM" / "MS"
+    name() -> "BP" / "QP-ADMM" / "MS" / "QMS"
 
 Every call runs on the GPU through libacg_ldpc_hip.so; there is no CPU path.
 """
 import collections
 import contextlib
 import ctypes as C
+import dataclasses
 import threading
 
 import numpy as np
@@ -26,6 +28,7 @@ from .code import ParityCheckMatrix
 
 class Decoder:
     _algo = None
+    _name = None   # name() where the algorithm alone does not give it
 
     # The reference hands H to every decode() (algo/algo.h:8) and its optimize_H loop hands a NEW H per proposal to one
     # shared decoder (optimize_H.cpp:16-25,89-104): the analysed-graph cache is therefore bounded.  Least recently used
@@ -88,11 +91,15 @@ class Decoder:
         code = H if isinstance(H, ParityCheckMatrix) else ParityCheckMatrix(H)
         h = C.c_void_p()
         p = self._params()
-        check(lib().acg_ldpc_decoder_create(code._h, C.byref(p), C.byref(h)))
+        check(self._create(code, p, h))
         ent = (h, code)
         self._handles[k] = ent
         self._trim()
         return ent
+
+    def _create(self, code, p, h):
+        """the create call of the C ABI this class's handles come from -> its return code"""
+        return lib().acg_ldpc_decoder_create(code._h, C.byref(p), C.byref(h))
 
     def _trim(self):
         if len(self._handles) <= self.max_handles:
@@ -136,7 +143,7 @@ class Decoder:
 
     # -- reference API ----------------------------------------------------------------------
     def name(self):
-        return {_lib.ALGO_BP: "BP", _lib.ALGO_QPADMM: "QP-ADMM", _lib.ALGO_MINSUM: "MS"}[self._algo]
+        return self._name or {_lib.ALGO_BP: "BP", _lib.ALGO_QPADMM: "QP-ADMM", _lib.ALGO_MINSUM: "MS"}[self._algo]
 
     def decode(self, H, channel_word, snr):
         bits, ok, _ = self.decode_batch(H, np.asarray(channel_word, dtype=np.float64)[None, :], snr)
@@ -256,3 +263,48 @@ class QPADMMDecoder(Decoder):
         p = super()._params()
         p.alpha, p.mu, p.eps_stop = self.alpha, self.mu, self.eps_stop
         return p
+
+
+@dataclasses.dataclass(frozen=True)
+class QuantConfig:
+    """acg_ldpc_quant (include/acg_ldpc.h): the defaults are acg_ldpc_quant_default's — offset-1 min-sum, 6-bit channel values in
+    steps of 0.5 LLR, 6-bit messages, 8-bit posteriors."""
+    llr_step: float = 0.5
+    ch_bits: int = 6
+    msg_bits: int = 6
+    post_bits: int = 8
+    scale_num: int = 1
+    scale_shift: int = 0
+    offset: int = 1
+
+    def as_tuple(self):
+        return (float(self.llr_step), int(self.ch_bits), int(self.msg_bits), int(self.post_bits), int(self.scale_num),
+                int(self.scale_shift), int(self.offset))
+
+    def as_struct(self):
+        return _lib.Quant(*self.as_tuple())
+
+
+class QuantizedMinSumDecoder(Decoder):
+    """Build-added fixed-point layered min-sum (acg_ldpc_decoder_create_quantized; not in the reference): integer channel
+    values, messages and posteriors, one workgroup per frame, check degree up to 32.  Bit-true: tests/layered_q_ref.py restates it.
+    quant: a QuantConfig, a dict of its fields, or None for the defaults.  The schedule is layered and the algorithm min-sum;
+    lanes_per_frame 0, 64, 128, 256, 512 or 1024 = threads of the workgroup.  The library refuses anything else."""
+    _algo = _lib.ALGO_MINSUM
+    _name = "QMS"
+
+    def __init__(self, max_iter, quant=None, **kw):
+        kw.setdefault("schedule", _lib.SCHEDULE_LAYERED)
+        super().__init__(max_iter, **kw)
+        if quant is None:
+            quant = QuantConfig()
+        elif isinstance(quant, dict):
+            quant = QuantConfig(**quant)
+        self.quant = quant
+
+    def _key(self, H):
+        return super()._key(H) + ("quant",) + self.quant.as_tuple()
+
+    def _create(self, code, p, h):
+        q = self.quant.as_struct()
+        return lib().acg_ldpc_decoder_create_quantized(code._h, C.byref(p), C.byref(q), C.byref(h))

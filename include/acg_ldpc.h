@@ -165,8 +165,58 @@ int acg_ldpc_code_is_codeword(const acg_ldpc_code *code, const uint8_t *bits);
  * (main.cpp:28-40).  Fails (non-zero) when no HIP device is present. */
 int acg_ldpc_decoder_create(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out);
 void acg_ldpc_decoder_destroy(acg_ldpc_decoder *dec);
-/* replaces Decoder::name() (algo/algo.h:10): "BP" (bp.h:218), "QP-ADMM" (qp_admm.h:189), "MS" */
+/* replaces Decoder::name() (algo/algo.h:10): "BP" (bp.h:218), "QP-ADMM" (qp_admm.h:189), "MS"; "QMS" for a handle of
+ * acg_ldpc_decoder_create_quantized */
 const char *acg_ldpc_decoder_name(const acg_ldpc_decoder *dec);
+
+/* ---- fixed-point layered min-sum (build-added; not in the reference) ------------------------ */
+
+/* The quantiser of the integer layered min-sum engine (bp_layered_q_kernel): every value of the decoder is an integer, so a
+ * restatement (tests/layered_q_ref.py) matches word, flag and exit iteration of every frame.
+ *   channel     c = clamp(round-half-even(llr32 * (float) (1 / llr_step)), -Cmax, +Cmax), llr32 the fp32 channel LLR the float
+ *               layered engines form ((float) (2 y / sigma^2) for double symbols, (float) ((double) y * (2 / sigma^2)) for float
+ *               symbols), the product ONE fp32 multiply; NaN -> 0, +-inf -> +-Cmax.  Posterior P = c, every message R = 0.
+ *   one check   q_j = P_j - R_j; a_j = min(|q_j|, Rmax); m1 <= m2 the two smallest a_j (a check of ONE variable: m2 = Rmax);
+ *               mu_j = (a_j == m1) ? m2 : m1; mu'_j = max(((mu_j * scale_num + rnd) >> scale_shift) - offset, 0) with
+ *               rnd = 2^(scale_shift - 1) (0 for scale_shift = 0); R'_j = +-mu'_j, negative where the XOR of the signs (q < 0)
+ *               of the OTHER edges is 1; P'_j = clamp(q_j + R'_j, -Pmax, +Pmax).
+ *   decision    P < 0 decides 1; P = 0 decides 0.
+ * Schedule, stopping rule, latching, the final syndrome pass and the iteration count are those of the layered workgroup engines
+ * (ACG_LDPC_SCHEDULE_LAYERED above) over the sets acg_ldpc_debug_layers_wide reports. */
+typedef struct acg_ldpc_quant {      /* 32 bytes */
+    double  llr_step;     /* LLR per integer unit, finite, > 0 */
+    int32_t ch_bits;      /* channel value clipped to +-(2^(ch_bits-1) - 1)   = +-Cmax; 2 <= ch_bits <= post_bits */
+    int32_t msg_bits;     /* check->variable messages, +-(2^(msg_bits-1) - 1) = +-Rmax; 2 <= msg_bits <= 8, msg_bits <= post_bits */
+    int32_t post_bits;    /* posteriors, +-(2^(post_bits-1) - 1)              = +-Pmax; post_bits <= 16 */
+    int32_t scale_num;    /* normalisation scale_num / 2^scale_shift, rounded half up; 1 <= scale_num <= 2^scale_shift */
+    int32_t scale_shift;  /* 0 <= scale_shift <= 8 */
+    int32_t offset;       /* subtracted after scaling, floor at 0; 0 <= offset <= Rmax */
+} acg_ldpc_quant;
+/* llr_step 0.5, ch_bits 6, msg_bits 6, post_bits 8, scale 1 / 2^0, offset 1: offset-1 min-sum */
+void acg_ldpc_quant_default(acg_ldpc_quant *q);
+/* host only, no device needed: 0 if *q obeys every rule written next to the fields above, else non-zero with the rule in
+ * acg_ldpc_last_error */
+int acg_ldpc_quant_check(const acg_ldpc_quant *q);
+/* A decoder on the integer engine: one workgroup per frame, LDS = int16 posteriors + one byte per edge + the output word
+ * (acg_ldpc_decoder_layout reports the bytes).  The only way to it; acg_ldpc_decoder_create never selects it.  Required of
+ * *params, anything else is refused with a message and nothing is launched:
+ *   algo = ACG_LDPC_BP_MINSUM, schedule = ACG_LDPC_SCHEDULE_LAYERED, precision = ACG_LDPC_PREC_DEFAULT,
+ *   engine = ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_FUSED,
+ *   lanes_per_frame 0, 64, 128, 256, 512 or 1024 = threads of the workgroup that owns a frame (0: the smallest of the five that
+ *   holds the largest set of checks, else 1024).
+ * ms_scale is IGNORED: the normalisation is scale_num / 2^scale_shift and offset of *q.  max_iter, early_exit and device apply
+ * as everywhere.  Also refused: an invalid *q (acg_ldpc_quant_check), a check of more than 32 variables, a frame whose state
+ * does not fit in LDS.
+ * The handle is an ordinary decoder: acg_ldpc_decode_batch, _f32 and _dev take symbols + snr; acg_ldpc_mc_run and
+ * acg_ldpc_mc_run_detail go noise kernel -> decode -> classification kernel; acg_ldpc_mc_run_grid refuses it as it refuses every
+ * decoder that is not QP-ADMM; acg_ldpc_decoder_name returns "QMS"; acg_ldpc_decoder_describe names the kernel, the workgroup,
+ * sets and steps and the seven values of *q. */
+int acg_ldpc_decoder_create_quantized(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
+                                      acg_ldpc_decoder **out);
+/* diagnostics: the engine's quantiser, run on the device, on `count` host symbols (doubles if y_is_f64, else floats) at `snr`;
+ * out_host receives count int16 channel values */
+int acg_ldpc_debug_quantize(const void *y_host, int32_t y_is_f64, int64_t count, double snr, const acg_ldpc_quant *q,
+                            int16_t *out_host);
 
 /* replaces Decoder::decode(H, y, snr) (algo/algo.h:8) for `frames` frames at once.
  *   y      host, frames*n doubles, raw channel symbols (NOT LLRs; llr = 2y/sigma^2 is formed inside,

@@ -4,7 +4,8 @@
 //   class Decoder                          algo/algo.h:6-11
 //   class BeliefPropagationDecoder(int)    algo/bp.h:208-222      name() == "BP"
 //   class QPADMMDecoder(a, mu, it, eps)    algo/qp_admm.h:180-194 name() == "QP-ADMM"
-// so experiment.h / main.cpp style callers compile unchanged against these types.
+// so experiment.h / main.cpp style callers compile unchanged against these types.  Build-added, not in the
+// reference: MinSumDecoder ("MS") and QuantizedMinSumDecoder ("QMS", fixed-point layered min-sum).
 // Header-only; link with -lacg_ldpc_hip.  The analysed graph is cached on the CONTENT of H, because the reference passes H
 // to every call (SURVEY §8b "Inputs"); the cache is a small LRU (kMaxHandles), because the reference's optimize_H loop
 // hands a NEW H per proposal to one shared decoder (optimize_H.cpp:16-25,89-104).
@@ -138,6 +139,10 @@ public:
 protected:
     virtual void fill(acg_ldpc_params &p) const = 0;
     virtual std::pair<TCodeword, bool> finish(const std::vector<uint8_t> &bits, bool ok) const = 0;
+    // the create call of the C ABI this class's handles come from
+    virtual int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const {
+        return acg_ldpc_decoder_create(code, &p, out);
+    }
 
     static void check(int rc) {
         if (rc != 0) {  // the reference aborts through assert(); so does the adaptor, with the library's message
@@ -215,7 +220,7 @@ private:
         acg_ldpc_params p;
         acg_ldpc_params_default(&p);
         fill(p);
-        check(acg_ldpc_decoder_create(e.code, &p, &e.dec));
+        check(create(e.code, p, &e.dec));
         cache_.push_front(e);
         trim();
         return cache_.begin();
@@ -315,6 +320,39 @@ private:
     int _max_iter;
     double _scale;
     bool _layered;
+};
+
+// build-added; not in the reference.  Fixed-point layered min-sum (acg_ldpc_decoder_create_quantized): integer channel values,
+// messages and posteriors as *quant says; the default quantiser is offset-1 min-sum on a 6-bit channel.  name() == "QMS".
+class QuantizedMinSumDecoder : public HipDecoderBase {
+public:
+    static acg_ldpc_quant default_quant() {
+        acg_ldpc_quant q;
+        acg_ldpc_quant_default(&q);
+        return q;
+    }
+    explicit QuantizedMinSumDecoder(int max_iter, const acg_ldpc_quant &quant = default_quant(), int lanes_per_frame = 0)
+        : _max_iter(max_iter), _lanes(lanes_per_frame), _quant(quant) {}
+    std::string name() const override { return "QMS"; }
+
+protected:
+    void fill(acg_ldpc_params &p) const override {
+        p.algo = ACG_LDPC_BP_MINSUM;
+        p.max_iter = _max_iter;
+        p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
+        p.lanes_per_frame = _lanes;
+    }
+    int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
+        return acg_ldpc_decoder_create_quantized(code, &p, &_quant, out);
+    }
+    std::pair<TCodeword, bool> finish(const std::vector<uint8_t> &bits, bool ok) const override {
+        if (!ok) return {TCodeword(), false};
+        return {TCodeword(bits.begin(), bits.end()), true};
+    }
+
+private:
+    int _max_iter, _lanes;
+    acg_ldpc_quant _quant;
 };
 
 // Scores a batch of parity-check matrices of one m x n under one set of QP-ADMM parameters (acg_ldpc_mc_run_codes): the
