@@ -14,6 +14,7 @@ import pytest
 
 from awgn_ref import classify, sent_words
 from minsum_ref import Graph, flooding_minsum
+from spa_cases import irregular as _irregular, ragged as _ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -92,32 +93,6 @@ def mid(A):
     """(3,6)-regular 1500 x 3000: 256 threads per frame (pair); threshold about -1.9 dB, 1500 x 3000 needs a little more"""
     Hm = A.regular_ldpc(1500, 3000, 3, 6, seed=5)
     return Hm, A.ParityCheckMatrix(Hm)
-
-
-def _ragged():
-    """degree-1 and degree-2 checks, an empty row, degree-0 and degree-1 variables (the graph of test_bp_edge_cases)"""
-    H = np.zeros((5, 9), np.uint8)
-    H[0, [0, 1, 2, 3]] = 1
-    H[1, [2, 3, 4]] = 1
-    H[2, [5]] = 1
-    H[3, [0, 6]] = 1
-    return H
-
-
-def _irregular():
-    """variable degree 1..4, check degree 1..8 — one-variable checks included (their message is inf * scale), which
-    test_pair_f16_minsum_kernels removes"""
-    Hi = np.zeros((300, 600), np.uint8)
-    r = np.random.default_rng(8)
-    for v in range(600):
-        Hi[r.choice(300, size=1 + (v % 4), replace=False), v] = 1
-    for i in np.nonzero(Hi.sum(1) > 8)[0]:
-        Hi[i, np.nonzero(Hi[i])[0][8:]] = 0
-    for i, d in ((3, 1), (57, 1), (120, 1), (200, 2), (201, 2)):      # a few checks cut down to one / two variables
-        Hi[i, np.nonzero(Hi[i])[0][d:]] = 0
-    Hi = Hi[:, Hi.sum(0) >= 1]
-    assert set(Hi.sum(1)) >= {1, 2, 8} and set(Hi.sum(0)) == {1, 2, 3, 4}
-    return Hi
 
 
 # ------------------------------------------------------------------------------------------ fp32, wave-group kernel
