@@ -391,48 +391,53 @@ static int decoder_setup_streamed(acg_ldpc_decoder *d) {
     return 0;
 }
 
-// schedule = LAYERED with one workgroup of L = 256, 512 or 1024 threads per frame (bp_layered_block.hip): the layered engine for
-// codes whose frame is too large for a wavefront group.  Its only size limit is the LDS of a CU: posteriors + messages +
-// output word of ONE frame.
-// wide: the code has a check of degree 9 ... 32 — the same tables under bp_layered_wide_kernel (bp_layered_wide.hip); L = 0 then
-// stands for the smallest workgroup that takes the largest set in one pass, else 1024.
-static int decoder_setup_layered_block(acg_ldpc_decoder *d, int L, bool wide = false) {
+// One workgroup of L threads per frame (bp_layered_block.hip): the layered engines for codes whose frame is too large for a wavefront
+// group (block: check degree <= 8), for high-rate codes (wide: a check of degree 9 ... 32, the same tables) and for fixed-point
+// min-sum (q: acg_ldpc_decoder_create_quantized; check degree <= 32, int16 posteriors and one byte per edge).  The only size
+// limit is the LDS of a CU: posteriors + messages + output word of ONE frame.
+// L: 256, 512 or 1024 (q: also 64, 128); 0 stands for the smallest workgroup that takes the largest set in one pass, else 1024.
+static int decoder_setup_layered_wg(acg_ldpc_decoder *d, const acg_ldpc_decoder::LayeredWg kind, int L) {
+    using Wg = acg_ldpc_decoder::LayeredWg;
     const Code &c = d->c;
-    const bool f16 = d->p.precision == ACG_LDPC_PREC_F16;
-    if (!bp_layered_block_build(c, d->lblay, wide ? 32 : 8)) return 3;
+    const bool q = kind == Wg::q, f16 = d->p.precision == ACG_LDPC_PREC_F16;
+    if (!bp_layered_block_build(c, d->lblay, kind == Wg::block ? 8 : 32)) return 3;
     const LayeredBlockLayout &ll = d->lblay;
-    if (wide && L == 0) L = ll.width <= 256 ? 256 : (ll.width <= 512 ? 512 : 1024);
+    if (L == 0) {
+        L = q ? 64 : 256;
+        while (L < 1024 && L < ll.width) L <<= 1;
+    }
+    const int cell = q ? 2 : 4, msg = q ? 1 : (f16 ? 2 : 4);   // bytes of a posterior cell and of a message cell
     LayerBlockTables &t = d->lbtab;
     t.n = c.n;
     t.nwords = (c.n + 31) / 32;
     t.e = ll.e;
     t.n_sets = ll.n_sets;
-    t.p_words = (c.n + 1 + 3) & ~3;
-    t.r_words = f16 ? (ll.e + 1) / 2 : ll.e;
+    t.p_words = (int32_t) ((((size_t) c.n + 1 + 16 / cell - 1) & ~(size_t) (16 / cell - 1)) * cell / 4);   // n + the neutral cell, padded to 16 bytes
+    t.r_words = (int32_t) (((size_t) ll.e * msg + 3) / 4);
     const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
     const int algo = d->p.algo == ACG_LDPC_BP_MINSUM ? 1 : 0;
-    const void *kp = wide ? bp_layered_wide_kernel_ptr(L, f16, algo) : bp_layered_block_kernel_ptr(L, f16, algo);
+    const void *kp = q ? bp_layered_q_kernel_ptr(L) : (kind == Wg::wide ? bp_layered_wide_kernel_ptr(L, f16, algo) : bp_layered_block_kernel_ptr(L, f16, algo));
     if (!kp) {
-        set_error("no layered workgroup-per-frame kernel instance for this lanes_per_frame");
+        set_error(q ? "no quantized layered kernel instance for this lanes_per_frame" : "no layered workgroup-per-frame kernel instance for this lanes_per_frame");
         return 3;
     }
     hipFuncAttributes fa{};
     HIP_OK(hipFuncGetAttributes(&fa, kp));
-    if (lds + fa.sharedSizeBytes > 160 * 1024) {   // (sharedSizeBytes: the kernel's few control words)
-        set_error("layered schedule: a frame (posteriors + messages) does not fit in LDS");
+    if (lds + fa.sharedSizeBytes > 160 * 1024 || c.n >= (1 << 30)) {   // (sharedSizeBytes: the kernel's few control words)
+        set_error(std::string(q ? "quantized layered min-sum" : "layered schedule") + ": a frame (posteriors + messages) does not fit in LDS");
         return 3;
     }
-    std::vector<int32_t> step, pos4(ll.pos.size());
+    std::vector<int32_t> step, pos(ll.pos.size());
     bp_layered_block_steps(ll, L, step);
-    for (size_t i = 0; i < ll.pos.size(); i++) pos4[i] = 4 * ll.pos[i];
+    for (size_t i = 0; i < ll.pos.size(); i++) pos[i] = cell * ll.pos[i];
     d->lb_step = upload(step, 8);
-    d->lb_pos = upload(pos4);
+    d->lb_pos = upload(pos);
     if (!d->lb_step.p || !d->lb_pos.p) return 10;
     t.step = d->lb_step.as<const int32_t>();
     t.pos = d->lb_pos.as<const int32_t>();
     t.n_steps = (int) (step.size() / 8);
-    d->layered_block = true;
-    d->layered_wide = wide;
+    d->layered_wg = kind;
+    if (q) d->qargs = quant_args(d->quant);
     d->L = L;
     d->f64 = 0;
     d->block = L;
@@ -498,60 +503,6 @@ static int quant_params_check(const acg_ldpc_params &p) {
     return 0;
 }
 
-// The fixed-point layered min-sum engine (bp_layered_q.hip): the sets and steps of decoder_setup_layered_block with the degree
-// cap 32, int16 posteriors and one byte per edge in LDS.  L = 0: the smallest of 64 ... 1024 that holds the largest set, else 1024.
-static int decoder_setup_layered_q(acg_ldpc_decoder *d) {
-    const Code &c = d->c;
-    if (!bp_layered_block_build(c, d->lblay, 32)) return 3;
-    const LayeredBlockLayout &ll = d->lblay;
-    int L = d->p.lanes_per_frame;
-    if (L == 0) {
-        L = 64;
-        while (L < 1024 && L < ll.width) L <<= 1;
-    }
-    LayerBlockTables &t = d->lbtab;
-    t.n = c.n;
-    t.nwords = (c.n + 31) / 32;
-    t.e = ll.e;
-    t.n_sets = ll.n_sets;
-    t.p_words = (((c.n + 1 + 7) & ~7) * 2) / 4;   // int16 cells, n + the neutral cell, padded to 16 bytes
-    t.r_words = (ll.e + 3) / 4;                   // one byte per edge
-    const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
-    const void *kp = bp_layered_q_kernel_ptr(L);
-    if (!kp) {
-        set_error("no quantized layered kernel instance for this lanes_per_frame");
-        return 3;
-    }
-    hipFuncAttributes fa{};
-    HIP_OK(hipFuncGetAttributes(&fa, kp));
-    if (lds + fa.sharedSizeBytes > 160 * 1024 || c.n >= (1 << 30)) {   // (sharedSizeBytes: the kernel's few control words)
-        set_error("quantized layered min-sum: a frame (posteriors + messages) does not fit in LDS");
-        return 3;
-    }
-    std::vector<int32_t> step, pos2(ll.pos.size());
-    bp_layered_block_steps(ll, L, step);
-    for (size_t i = 0; i < ll.pos.size(); i++) pos2[i] = 2 * ll.pos[i];
-    d->lb_step = upload(step, 8);
-    d->lb_pos = upload(pos2);
-    if (!d->lb_step.p || !d->lb_pos.p) return 10;
-    t.step = d->lb_step.as<const int32_t>();
-    t.pos = d->lb_pos.as<const int32_t>();
-    t.n_steps = (int) (step.size() / 8);
-    d->layered_block = true;   // (decode only: Monte-Carlo runs take the unfused route of the workgroup layered engines)
-    d->layered_q = true;
-    d->qargs = quant_args(d->quant);
-    d->L = L;
-    d->f64 = 0;
-    d->block = L;
-    d->frames_per_block = 1;
-    d->lds_block = lds;
-    if (int rc = bind_kernel(d, 0, kp)) return rc;
-    d->kernel[1] = nullptr;
-    d->grid_cap[1] = d->grid_cap[0];
-    d->tab.lds_bytes_per_frame = (int32_t) lds;
-    return 0;
-}
-
 // schedule = LAYERED: min-sum over conflict-free layers of checks with in-place posteriors (bp_layered.hip)
 static int decoder_setup_layered(acg_ldpc_decoder *d) {
     const Code &c = d->c;
@@ -575,10 +526,10 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
             set_error("layered schedule: lanes_per_frame is chosen by the layering (pass 0), or 256, 512, 1024 for one workgroup per frame");
             return 3;
         }
-        return decoder_setup_layered_block(d, want_L, true);
+        return decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::wide, want_L);
     }
-    if (want_L == 256 || want_L == 512 || want_L == 1024) return decoder_setup_layered_block(d, want_L);
-    if (want_L == 0 && c.n >= 16000) return decoder_setup_layered_block(d, 1024);
+    if (want_L == 256 || want_L == 512 || want_L == 1024) return decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::block, want_L);
+    if (want_L == 0 && c.n >= 16000) return decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::block, 1024);
     if (!bp_layered_build(c, d->llay)) return 3;
     const LayeredLayout &ll = d->llay;
     if (d->p.lanes_per_frame != 0 && d->p.lanes_per_frame != ll.G) {
@@ -627,7 +578,7 @@ static int decoder_setup_layered(acg_ldpc_decoder *d) {
     if (per_wave * waves + t.tab_lds_bytes > 160 * 1024) {
         if (want_L == 0) {   // the workgroup-per-frame engine keeps no table in LDS and splits a frame over 16 wavefronts
             d->ltab = LayerTables{};
-            return decoder_setup_layered_block(d, 1024);
+            return decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::block, 1024);
         }
         set_error("layered schedule: a frame (posteriors + messages) does not fit in LDS");
         return 3;
@@ -949,7 +900,7 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
         if (quant) {
             d->name = "QMS";
             d->quant = *quant;
-            rc = decoder_setup_layered_q(d);
+            rc = decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::q, d->p.lanes_per_frame);
         } else if (params->algo == ACG_LDPC_QPADMM) {
             d->name = "QP-ADMM";  // qp_admm.h:189
             std::string err;
@@ -1064,17 +1015,17 @@ static std::string describe(const acg_ldpc_decoder *d) {
             }
             return t;
         }
-    } else if (d->layered_q) {
+    } else if (d->layered_wg == acg_ldpc_decoder::LayeredWg::q) {
         const acg_ldpc_quant &q = d->quant;
         snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_q_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
                                "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=int8 posteriors=int16 "
                                "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d",
                  algo, d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width, q.llr_step, q.ch_bits, q.msg_bits,
                  q.post_bits, q.scale_num, q.scale_shift, q.offset);
-    } else if (d->layered_block) {
+    } else if (d->layered_wg != acg_ldpc_decoder::LayeredWg::none) {
         snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
                                "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=%s",
-                 algo, d->layered_wide ? "bp_layered_wide_kernel" : "bp_layered_block_kernel", d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width,
+                 algo, d->layered_wg == acg_ldpc_decoder::LayeredWg::wide ? "bp_layered_wide_kernel" : "bp_layered_block_kernel", d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width,
                  d->p.precision == ACG_LDPC_PREC_F16 ? "fp16" : "fp32");
     } else {
         snprintf(b, sizeof b, "%s engine=fused kernel=%s lanes_per_frame=%d f64=%d block=%d frames_per_block=%d lds_block=%zu grid_cap=%d "

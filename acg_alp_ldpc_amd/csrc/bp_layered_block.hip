@@ -177,10 +177,14 @@ const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo) {
     return f16 ? layered_block_ptr_l<_Float16, 1>(L) : layered_block_ptr_l<float, 1>(L);
 }
 
-hipError_t bp_layered_block_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s) {
+// The launch of the three workgroup-per-frame layered kernels (this file's, bp_layered_wide.hip's and bp_layered_q.hip's); q: the
+// third argument of bp_layered_q_kernel, null for the float kernels
+hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs *q, int grid, int block, size_t lds,
+                                hipStream_t s) {
     LayerBlockTables tt = t;
     DecodeArgs aa = a;
-    void *args[2] = {&tt, &aa};
+    QuantArgs qq = q ? *q : QuantArgs{};
+    void *args[3] = {&tt, &aa, &qq};   // (hipLaunchKernel reads as many as the kernel has parameters)
     return hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, s);
 }
 

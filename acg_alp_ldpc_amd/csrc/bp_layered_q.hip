@@ -292,16 +292,6 @@ const void *bp_layered_q_kernel_ptr(int L) {
     }
 }
 
-// Decode only, as bp_layered_block_kernel: a Monte-Carlo run on such a handle goes AWGN kernel -> this kernel -> classification kernel.
-hipError_t bp_layered_q_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs &q, int grid, int block,
-                               size_t lds, hipStream_t s) {
-    LayerBlockTables tt = t;
-    DecodeArgs aa = a;
-    QuantArgs qq = q;
-    void *args[3] = {&tt, &aa, &qq};
-    return hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, s);
-}
-
 // acg_ldpc_debug_quantize: the device function the decode kernel calls, on a plain array of symbols
 __global__ void __launch_bounds__(256) quantize_debug_kernel(const DecodeArgs a, const QuantArgs qa, const int64_t count, int16_t *__restrict__ out) {
     for (int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t) gridDim.x * 256) out[i] = (int16_t) quantize_symbol(a, qa, (size_t) i);

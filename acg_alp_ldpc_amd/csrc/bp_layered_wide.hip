@@ -330,11 +330,4 @@ const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo) {
     return f16 ? layered_wide_ptr_l<_Float16, 1>(L) : layered_wide_ptr_l<float, 1>(L);
 }
 
-hipError_t bp_layered_wide_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s) {
-    LayerBlockTables tt = t;
-    DecodeArgs aa = a;
-    void *args[2] = {&tt, &aa};
-    return hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, s);
-}
-
 }  // namespace acg

@@ -148,15 +148,14 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
         } else {
             HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, (uint32_t *) d->sws.va, grid, W * 64, s));
         }
-    } else if (d->layered_block) {
+    } else if (d->layered_wg != acg_ldpc_decoder::LayeredWg::none) {
         if (a.mc) {
             set_error("internal: the workgroup-per-frame layered engine has no in-kernel generator");
             return 11;
         }
         const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
-        if (d->layered_q) HIP_OK(bp_layered_q_launch(d->kernel[0], d->lbtab, a, d->qargs, grid, d->block, d->lds_block, s));
-        else if (d->layered_wide) HIP_OK(bp_layered_wide_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
-        else HIP_OK(bp_layered_block_launch(d->kernel[0], d->lbtab, a, grid, d->block, d->lds_block, s));
+        const QuantArgs *q = d->layered_wg == acg_ldpc_decoder::LayeredWg::q ? &d->qargs : nullptr;
+        HIP_OK(bp_layered_wg_launch(d->kernel[0], d->lbtab, a, q, grid, d->block, d->lds_block, s));
     } else if (d->layered) {
         const int mc = a.mc ? 1 : 0;
         const int64_t blocks = (a.frames + d->frames_per_block - 1) / d->frames_per_block;

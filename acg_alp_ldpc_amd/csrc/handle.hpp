@@ -157,11 +157,11 @@ struct acg_ldpc_decoder {
     bool layered = false;
     acg::LayeredLayout llay;
     acg::LayerTables ltab{};
-    // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory
-    bool layered_block = false;
-    bool layered_wide = false;  // (with layered_block) the kernel is bp_layered_wide_kernel: check degree up to 32, same tables
-    // (with layered_block) the kernel is bp_layered_q_kernel: fixed-point min-sum, handles of acg_ldpc_decoder_create_quantized only
-    bool layered_q = false;
+    // layered BP, one workgroup per frame (bp_layered_block.hip): the step and position tables stay in device memory.  Which kernel:
+    // bp_layered_block_kernel (check degree <= 8), bp_layered_wide_kernel (<= 32, same tables) or bp_layered_q_kernel (fixed-point
+    // min-sum, handles of acg_ldpc_decoder_create_quantized only).  Decode only: Monte-Carlo runs take the unfused route.
+    enum class LayeredWg { none, block, wide, q };
+    LayeredWg layered_wg = LayeredWg::none;
     acg_ldpc_quant quant{};
     acg::QuantArgs qargs{};
     acg::LayeredBlockLayout lblay;

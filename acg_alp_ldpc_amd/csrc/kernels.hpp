@@ -116,26 +116,23 @@ struct LayerTables {
     int32_t lds_bytes_per_frame;
 };
 
-// Workgroup-per-frame layered BP (bp_layered_block.hip; LayeredBlockLayout in ldpc_internal.hpp).  Both tables live in device
-// memory; a workgroup's LDS holds the state of its frame and nothing else.  bp_layered_wide.hip (check degree up to 32) reads the
-// same tables: degree is then 1 ... 32, and that kernel fetches the position entries of a step 8 edges at a time.
+// Workgroup-per-frame layered BP (bp_layered_block.hip, bp_layered_wide.hip, bp_layered_q.hip; LayeredBlockLayout in
+// ldpc_internal.hpp).  Both tables live in device memory.  degree is 1 ... 8 for bp_layered_block_kernel, 1 ... 32 for the other two.
 struct LayerBlockTables {
     // [n_steps][8]: the (set, pass) pairs of one iteration in processing order =
     //   {degree, 1 = barrier behind the step (the last pass of a set; 0 behind the last set: the round's OR is its barrier),
     //    message cell of (edge 0, thread 0), position entry of (edge 0, thread 0), checks in the pass (<= L),
     //    checks in the whole set (the distance between the position entries of consecutive edges), 0, 0}
     const int32_t *step;
-    const int32_t *pos;      // [e] byte offset of the posterior cell of (set, edge j, slot) at set offset + j * cnt + slot
+    const int32_t *pos;      // [e] byte offset of the posterior cell (fp32; q: int16) of (set, edge j, slot) at set offset + j * cnt + slot
     int32_t n_steps, n_sets;
     int32_t n, nwords;
     int32_t e;               // message cells per frame = edges of the graph
-    int32_t p_words;         // posterior words per frame (n + the neutral cell, rounded up to a multiple of 4)
-    int32_t r_words;         // 32-bit words the e message cells occupy (e, or half of it rounded up for fp16 storage)
+    int32_t p_words;         // 32-bit words of the posterior cells: n + the neutral cell, padded to 16 bytes
+    int32_t r_words;         // 32-bit words of the e message cells (fp32, fp16; q: one byte), rounded up
 };
 
-// Fixed-point layered min-sum (bp_layered_q.hip): acg_ldpc_quant as the kernel reads it.  The tables are LayerBlockTables with
-// two differences: pos holds byte offsets of 2-byte posterior cells, and p_words / r_words count the 32-bit words of the
-// int16 posteriors (+ neutral cell, padded) and of the one-byte message cells.
+// Fixed-point layered min-sum (bp_layered_q.hip): acg_ldpc_quant as the kernel reads it
 struct QuantArgs {
     float inv_step;   // (float) (1 / llr_step)
     int32_t cmax, rmax, pmax;

@@ -65,20 +65,14 @@ const void *bp_pair_kernel_ptr(int L, bool regular);
 const void *bp_layered_kernel_ptr(int G, int waves, bool qc_arith, bool f16, int algo, bool mc);
 hipError_t bp_layered_launch(const void *kernel, const LayerTables &t, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s);
 
-// ---- bp_layered_block.hip ----
+// ---- the workgroup-per-frame layered kernels: bp_layered_block.hip (check degree <= 8; L = 256, 512, 1024), bp_layered_wide.hip
+// (<= 32, the same tables) and bp_layered_q.hip (fixed-point min-sum, <= 32; L = 64, 128, 256, 512, 1024) ----
 const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo);
-hipError_t bp_layered_block_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
-                                   hipStream_t s);
-
-// ---- bp_layered_wide.hip (check degree up to 32; the tables of bp_layered_block.hip) ----
 const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo);
-hipError_t bp_layered_wide_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
-                                  hipStream_t s);
-
-// ---- bp_layered_q.hip (fixed-point layered min-sum, check degree up to 32; L = 64, 128, 256, 512, 1024) ----
 const void *bp_layered_q_kernel_ptr(int L);
-hipError_t bp_layered_q_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs &q, int grid, int block,
-                               size_t lds, hipStream_t s);
+// q: the quantiser of bp_layered_q_kernel, null for the float kernels
+hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs *q, int grid, int block,
+                                size_t lds, hipStream_t s);
 // the kernel's quantiser on `count` symbols (a: y, y_is_f64 and the channel terms) -> count int16
 hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_t count, int16_t *out, hipStream_t s);
 
