@@ -82,6 +82,9 @@ SYMBOLS = {
     "acg_ldpc_quant_check": (C.c_int, [C.POINTER(Quant)]),
     "acg_ldpc_decoder_create_quantized": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(Quant), C.POINTER(_vp)]),
     "acg_ldpc_debug_quantize": (C.c_int, [_vp, _i32, _i64, _f64, C.POINTER(Quant), _vp]),
+    "acg_ldpc_quantize_dev": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp]),
+    "acg_ldpc_decode_batch_q_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_decode_batch_q": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "acg_ldpc_decoder_destroy": (None, [_vp]),
     "acg_ldpc_decoder_name": (C.c_char_p, [_vp]),
     "acg_ldpc_decode_batch": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp]),

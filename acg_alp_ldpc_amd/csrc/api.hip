@@ -106,15 +106,16 @@ static bool is_regular(const Code &c) {
     return regular;
 }
 
-// kernel[mc] = kp: raise its dynamic-LDS limit where the workgroup needs more than 64 KiB, and size the grid by its occupancy
-static int bind_kernel(acg_ldpc_decoder *d, int mc, const void *kp) {
+// kernel[mc] (or the pair handed in) = kp: raise its dynamic-LDS limit where the workgroup needs more than 64 KiB, and size the grid by its occupancy
+static int bind_kernel(acg_ldpc_decoder *d, const void *kp, const void *&kernel, int &grid_cap) {
     if (d->lds_block > 64 * 1024) HIP_OK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int) d->lds_block));
     int occ = 0;
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, d->block, d->lds_block));
-    d->kernel[mc] = kp;
-    d->grid_cap[mc] = std::max(occ, 1) * d->cu_count;
+    kernel = kp;
+    grid_cap = std::max(occ, 1) * d->cu_count;
     return 0;
 }
+static int bind_kernel(acg_ldpc_decoder *d, int mc, const void *kp) { return bind_kernel(d, kp, d->kernel[mc], d->grid_cap[mc]); }
 
 extern "C" {
 
@@ -416,7 +417,7 @@ static int decoder_setup_layered_wg(acg_ldpc_decoder *d, const acg_ldpc_decoder:
     t.r_words = (int32_t) (((size_t) ll.e * msg + 3) / 4);
     const size_t lds = ((size_t) t.p_words + (size_t) t.r_words + (size_t) t.nwords) * 4;
     const int algo = d->p.algo == ACG_LDPC_BP_MINSUM ? 1 : 0;
-    const void *kp = q ? bp_layered_q_kernel_ptr(L) : (kind == Wg::wide ? bp_layered_wide_kernel_ptr(L, f16, algo) : bp_layered_block_kernel_ptr(L, f16, algo));
+    const void *kp = q ? bp_layered_q_kernel_ptr(L, false) : (kind == Wg::wide ? bp_layered_wide_kernel_ptr(L, f16, algo) : bp_layered_block_kernel_ptr(L, f16, algo));
     if (!kp) {
         set_error(q ? "no quantized layered kernel instance for this lanes_per_frame" : "no layered workgroup-per-frame kernel instance for this lanes_per_frame");
         return 3;
@@ -447,6 +448,16 @@ static int decoder_setup_layered_wg(acg_ldpc_decoder *d, const acg_ldpc_decoder:
     if (int rc = bind_kernel(d, 0, kp)) return rc;
     d->kernel[1] = nullptr;
     d->grid_cap[1] = d->grid_cap[0];
+    if (q) {
+        // the integer entrance's instance of the same workgroup (acg_ldpc_decode_batch_q*): its own LDS limit and occupancy
+        const void *kio = bp_layered_q_kernel_ptr(L, true);
+        HIP_OK(hipFuncGetAttributes(&fa, kio));
+        if (lds + fa.sharedSizeBytes > 160 * 1024) {
+            set_error("quantized layered min-sum: a frame (posteriors + messages) does not fit in LDS");
+            return 3;
+        }
+        if (int rc = bind_kernel(d, kio, d->kernel_qio, d->grid_cap_qio)) return rc;
+    }
     d->tab.lds_bytes_per_frame = (int32_t) lds;
     return 0;
 }

@@ -177,8 +177,16 @@ __device__ __forceinline__ uint32_t q_layer_step(unsigned char *__restrict__ Pb,
 // Two workgroups of 1024 threads per CU are 8 wavefronts per SIMD: at most 96 scalar and 64 vector registers.  Without the bound
 // the compiler takes 106 scalar registers — 7 wavefronts per SIMD, ONE workgroup of 1024 per CU.  The smaller workgroups reach their
 // residency (three of 512 per CU: 6 wavefronts per SIMD) without it and keep the registers.
-template <int L>
-__global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 1024 ? 8 : 6))) bp_layered_q_kernel(const LayerBlockTables t, const DecodeArgs a, const QuantArgs qa) {
+//
+// IO: the integer entrance (acg_ldpc_decode_batch_q*).  A frame starts from qa.c_in — int16 channel values, clamped to +-cmax, no
+// quantiser — and, where qa.post_out is set, its int16 posteriors leave with its word.  The symbol entrance's instances (IO =
+// false) read neither pointer and compile to what they compiled to without them.  Left to itself the compiler gives the IO
+// instances 77-80 vector registers where their siblings take 68-71: 6 wavefronts per SIMD instead of 7.  For L <= 256 that is a
+// workgroup per SIMD fewer (24 / (L / 64) per CU instead of 28 / (L / 64)), so those are bound to 7 (72 registers, 4-5 of them in
+// scratch, reloaded once per FRAME: no scratch access inside a round); for L = 512 both figures are three workgroups per CU
+// and the instance keeps its registers.
+template <int L, bool IO>
+__global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 1024 ? 8 : (IO && L <= 256 ? 7 : 6)))) bp_layered_q_kernel(const LayerBlockTables t, const DecodeArgs a, const QuantArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long fr_lds;
     const int l = threadIdx.x;
@@ -218,7 +226,13 @@ __global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 102
         const int64_t frame = (int64_t) fr_lds;
         if (frame >= a.frames) break;
         // ---- start of a frame: P = quantised channel LLR, R = 0 -------------------------------------------------------------------
-        for (int v = l; v < t.n; v += L) P[v] = (short) quantize_symbol(a, qa, (size_t) frame * t.n + v);
+        if constexpr (IO) {
+            // (rows are n values apart: 2-byte aligned only, so one value per load)
+            const int16_t *const c = qa.c_in + (size_t) frame * t.n;
+            for (int v = l; v < t.n; v += L) P[v] = (short) min(max((int) c[v], -qa.cmax), qa.cmax);
+        } else {
+            for (int v = l; v < t.n; v += L) P[v] = (short) quantize_symbol(a, qa, (size_t) frame * t.n + v);
+        }
         for (int w = t.n + l; w < 2 * t.p_words; w += L) P[w] = 0;   // neutral cell: decides 0
         {
             uint32_t *Rw = reinterpret_cast<uint32_t *>(R);
@@ -258,6 +272,15 @@ __global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 102
                 } else {
                     for (int w = l; w < t.nwords; w += L) OB[w] = 0u;
                 }
+                if constexpr (IO) {
+                    // the posteriors of this round boundary: nobody has written P since the barrier of the round's OR, and the
+                    // barrier below stands between these reads and the next set
+                    if (qa.post_out) {
+                        int16_t *const po = qa.post_out + (size_t) frame * t.n;
+#pragma nounroll
+                        for (int v = l; v < t.n; v += L) po[v] = P[v];
+                    }
+                }
                 __syncthreads();   // (also: every posterior of the word is read before the next set rewrites it)
                 if (a.out_bits)
                     for (int w = l; w < t.nwords; w += L) a.out_bits[(size_t) frame * t.nwords + w] = OB[w];
@@ -281,16 +304,20 @@ __global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 102
     }
 }
 
-const void *bp_layered_q_kernel_ptr(int L) {
+template <bool IO>
+static const void *q_kernel_ptr_l(int L) {
     switch (L) {
-        case 64: return (const void *) bp_layered_q_kernel<64>;
-        case 128: return (const void *) bp_layered_q_kernel<128>;
-        case 256: return (const void *) bp_layered_q_kernel<256>;
-        case 512: return (const void *) bp_layered_q_kernel<512>;
-        case 1024: return (const void *) bp_layered_q_kernel<1024>;
+        case 64: return (const void *) bp_layered_q_kernel<64, IO>;
+        case 128: return (const void *) bp_layered_q_kernel<128, IO>;
+        case 256: return (const void *) bp_layered_q_kernel<256, IO>;
+        case 512: return (const void *) bp_layered_q_kernel<512, IO>;
+        case 1024: return (const void *) bp_layered_q_kernel<1024, IO>;
         default: return nullptr;
     }
 }
+
+// io: the instance of the integer entrance (channel values in, posteriors out)
+const void *bp_layered_q_kernel_ptr(int L, bool io) { return io ? q_kernel_ptr_l<true>(L) : q_kernel_ptr_l<false>(L); }
 
 // acg_ldpc_debug_quantize: the device function the decode kernel calls, on a plain array of symbols
 __global__ void __launch_bounds__(256) quantize_debug_kernel(const DecodeArgs a, const QuantArgs qa, const int64_t count, int16_t *__restrict__ out) {

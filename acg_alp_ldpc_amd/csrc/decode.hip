@@ -96,7 +96,11 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
 }
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
-int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
+int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio) {
+    if (qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qio)) {
+        set_error("internal: channel values handed to a decoder that is not quantized");
+        return 11;
+    }
     a.max_iter = d->p.max_iter;
     a.early_exit = d->p.early_exit;
     a.ms_scale = (float) d->p.ms_scale;
@@ -153,9 +157,18 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s) {
             set_error("internal: the workgroup-per-frame layered engine has no in-kernel generator");
             return 11;
         }
-        const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
-        const QuantArgs *q = d->layered_wg == acg_ldpc_decoder::LayeredWg::q ? &d->qargs : nullptr;
-        HIP_OK(bp_layered_wg_launch(d->kernel[0], d->lbtab, a, q, grid, d->block, d->lds_block, s));
+        if (qio) {
+            // the same launch with the integer entrance's instance and the two pointers behind the quantiser
+            QuantArgs q = d->qargs;
+            q.c_in = qio->c_in;
+            q.post_out = qio->post_out;
+            const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap_qio);
+            HIP_OK(bp_layered_wg_launch(d->kernel_qio, d->lbtab, a, &q, grid, d->block, d->lds_block, s));
+        } else {
+            const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
+            const QuantArgs *q = d->layered_wg == acg_ldpc_decoder::LayeredWg::q ? &d->qargs : nullptr;
+            HIP_OK(bp_layered_wg_launch(d->kernel[0], d->lbtab, a, q, grid, d->block, d->lds_block, s));
+        }
     } else if (d->layered) {
         const int mc = a.mc ? 1 : 0;
         const int64_t blocks = (a.frames + d->frames_per_block - 1) / d->frames_per_block;
@@ -271,7 +284,8 @@ int acg_ldpc_decode_batch_dev(acg_ldpc_decoder *d, const void *y_dev, int32_t y_
     return guarded([&] { return acg_ldpc_decode_batch_dev_impl(d, y_dev, y_is_f64, frames, snr, bits_dev, ok_dev, iters_dev, stream); });
 }
 
-static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes) {
+// y_bytes, out_bytes: per frame
+static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes, size_t out_bytes) {
     if (!d->pipe) {
         // built completely before it is published in the handle: a half-made pipe must never be seen by a later call
         std::unique_ptr<HostPipe> np(new HostPipe());
@@ -285,17 +299,17 @@ static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes) {
     // keep the buffers while they fit and are not grossly oversized for what is asked now (a 1M-frame batch followed by
     // single-frame decode() calls must not pin hundreds of MB for good)
     const size_t want = (size_t) chunk * y_bytes, have = (size_t) P.chunk * P.y_bytes;
-    if (chunk <= P.chunk && y_bytes <= P.y_bytes && (have <= ((size_t) 32 << 20) || have <= 16 * want)) return 0;
+    if (chunk <= P.chunk && y_bytes <= P.y_bytes && out_bytes <= P.out_bytes && (have <= ((size_t) 32 << 20) || have <= 16 * want)) return 0;
     P.release();
-    const int nwords = (d->c.n + 31) / 32;
     for (int b = 0; b < HostPipe::NBUF; b++) {
         if (int rc = P.pin_y[b].reserve((size_t) chunk * y_bytes)) return rc;
-        if (int rc = P.pin_out[b].reserve((size_t) chunk * (nwords * 4 + 5))) return rc;
+        if (int rc = P.pin_out[b].reserve((size_t) chunk * out_bytes + 16)) return rc;
         if (int rc = P.dev_y[b].reserve((size_t) chunk * y_bytes)) return rc;
-        if (int rc = P.dev_out[b].reserve((size_t) chunk * (nwords * 4 + 5))) return rc;
+        if (int rc = P.dev_out[b].reserve((size_t) chunk * out_bytes + 16)) return rc;
     }
     P.chunk = chunk;
     P.y_bytes = y_bytes;
+    P.out_bytes = out_bytes;
     return 0;
 }
 
@@ -330,14 +344,18 @@ static void unpack_bits(const uint32_t *words, int nwords, int n, int64_t frames
 // Host buffers in, host buffers out: chunks of the batch travel through two pinned staging sets.  Per chunk c (set c % 2):
 // host threads copy the symbols into pinned memory -> H2D, decode, D2H of words / flags / sweep counts on the set's
 // stream -> host threads expand the words into one byte per bit.  Chunk c + 1 is packed and chunk c - 1 unpacked while
-// the GPU works on chunk c.  elem = 8 (double symbols: exact LLRs, channel.h:14-16) or 4 (float symbols).
+// the GPU works on chunk c.  elem = 8 (double symbols: exact LLRs, channel.h:14-16) or 4 (float symbols); elem = 2: int16
+// channel values of a quantized handle (acg_ldpc_decode_batch_q; snr unused), whose int16 posteriors come back behind the
+// flags of the chunk where post is given.
 static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
-                             int32_t *iters) {
+                             int32_t *iters, int16_t *post = nullptr) {
     const int n = d->c.n, nwords = (n + 31) / 32;
     const size_t y_bytes = (size_t) n * elem;
+    const size_t row = (size_t) nwords * 4 + 5;   // words, sweep count and flag of a frame
+    auto post_off = [&](int64_t fc) { return ((size_t) fc * row + 15) & ~(size_t) 15; };
     // small batches (single frames: the reference's decode()) take one chunk; large ones <= 64k frames / 256 MiB per chunk
     const int64_t chunk = host_chunk_frames(frames, y_bytes);
-    if (int rc = ensure_pipe(d, chunk, y_bytes)) return rc;
+    if (int rc = ensure_pipe(d, chunk, y_bytes, row + (post ? (size_t) n * 2 : 0))) return rc;
     HostPipe &P = *d->pipe;
     const int64_t nchunks = (frames + chunk - 1) / chunk;
     const bool threads = frames >= 4096;  // tiny batches: the hand-off to the pool costs more than the copy
@@ -364,12 +382,13 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         hipStream_t s = P.stream[b];
         unsigned char *dev_out = P.dev_out[b].as<unsigned char>();
         HIP_OK(hipMemcpyAsync(P.dev_y[b].p, P.pin_y[b].p, (size_t) fc * y_bytes, hipMemcpyHostToDevice, s));
-        DecodeArgs a = decode_args(P.dev_y[b].p, (elem == 8) ? 1 : 0, fc, snr);
+        DecodeArgs a = decode_args(elem == 2 ? nullptr : P.dev_y[b].p, (elem == 8) ? 1 : 0, fc, snr);
+        const QuantIo io{P.dev_y[b].as<int16_t>(), post ? reinterpret_cast<int16_t *>(dev_out + post_off(fc)) : nullptr};
         a.out_bits = reinterpret_cast<uint32_t *>(dev_out);
         a.out_iters = reinterpret_cast<int32_t *>(dev_out + (size_t) fc * nwords * 4);
         a.out_ok = dev_out + (size_t) fc * (nwords * 4 + 4);
-        if (int rc = launch_decode(d, a, s)) return rc;
-        HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, (size_t) fc * (nwords * 4 + 5), hipMemcpyDeviceToHost, s));
+        if (int rc = launch_decode(d, a, s, elem == 2 ? &io : nullptr)) return rc;
+        HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, post ? post_off(fc) + (size_t) fc * n * 2 : (size_t) fc * row, hipMemcpyDeviceToHost, s));
         HIP_OK(hipEventRecord(P.done[b], s));
         return 0;
     };
@@ -381,13 +400,16 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         const uint32_t *pbits = reinterpret_cast<const uint32_t *>(out);
         std::memcpy(ok + f0, out + (size_t) fc * (nwords * 4 + 4), (size_t) fc);
         if (iters) std::memcpy(iters + f0, out + (size_t) fc * nwords * 4, (size_t) fc * 4);
+        const int16_t *ppost = reinterpret_cast<const int16_t *>(out + post_off(fc));
         if (!threads) {
             unpack_bits(pbits, nwords, n, fc, bits + (size_t) f0 * n);
+            if (post) std::memcpy(post + (size_t) f0 * n, ppost, (size_t) fc * n * 2);
             return 0;
         }
         pool->run_all([&](int part, int parts) {
             const int64_t lo = fc * part / parts, hi = fc * (part + 1) / parts;
             unpack_bits(pbits + (size_t) lo * nwords, nwords, n, hi - lo, bits + (size_t) (f0 + lo) * n);
+            if (post) std::memcpy(post + (size_t) (f0 + lo) * n, ppost + (size_t) lo * n, (size_t) (hi - lo) * n * 2);
         });
         return 0;
     };
@@ -431,6 +453,82 @@ int acg_ldpc_decode_batch(acg_ldpc_decoder *d, const double *y, int64_t frames, 
 int acg_ldpc_decode_batch_f32(acg_ldpc_decoder *d, const float *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
                               int32_t *iters) {
     return guarded([&] { return decode_batch_impl(d, y, 4, frames, snr, bits, ok, iters); });
+}
+
+// ---- the integer entrance of the fixed-point layered min-sum engine: channel values in, posteriors out ----
+
+// what the three entry points refuse before they look at their buffers
+static int quantized_handle(const acg_ldpc_decoder *d) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    if (d->layered_wg != acg_ldpc_decoder::LayeredWg::q) {
+        set_error("channel values need a decoder of acg_ldpc_decoder_create_quantized");
+        return 3;
+    }
+    return 0;
+}
+
+static int quantize_dev_impl(acg_ldpc_decoder *d, const void *y_dev, int32_t y_is_f64, int64_t count, double snr, int16_t *c_dev,
+                             void *stream) {
+    if (int rc = quantized_handle(d)) return rc;
+    if (count < 0 || (count > 0 && (!y_dev || !c_dev))) {
+        set_error("bad count / y / c");
+        return 1;
+    }
+    if (count == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    const DecodeArgs a = decode_args(y_dev, y_is_f64 ? 1 : 0, count, snr);
+    HIP_OK(quantize_debug_launch(a, d->qargs, count, c_dev, stream ? (hipStream_t) stream : d->stream));
+    return 0;
+}
+
+static int decode_batch_q_dev_impl(acg_ldpc_decoder *d, const int16_t *c_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                   int32_t *iters_dev, int16_t *post_dev, void *stream) {
+    if (int rc = quantized_handle(d)) return rc;
+    if (frames < 0 || (frames > 0 && !c_dev)) {
+        set_error("bad frames / c");
+        return 1;
+    }
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    DecodeArgs a = decode_args(nullptr, 0, frames, 0.0);   // (no symbols, no channel: the kernel reads neither)
+    a.out_bits = bits_dev;
+    a.out_ok = ok_dev;
+    a.out_iters = iters_dev;
+    const QuantIo io{c_dev, post_dev};
+    return launch_decode(d, a, stream ? (hipStream_t) stream : d->stream, &io);
+}
+
+static int decode_batch_q_impl(acg_ldpc_decoder *d, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
+                               int16_t *post) {
+    if (int rc = quantized_handle(d)) return rc;
+    if (frames < 0 || (frames > 0 && (!c || !bits || !ok))) {
+        set_error("null buffer");
+        return 1;
+    }
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    return decode_batch_host(d, c, 2, frames, 0.0, bits, ok, iters, post);
+}
+
+int acg_ldpc_quantize_dev(acg_ldpc_decoder *d, const void *y_dev, int32_t y_is_f64, int64_t count, double snr, int16_t *c_dev,
+                          void *stream) {
+    return guarded([&] { return quantize_dev_impl(d, y_dev, y_is_f64, count, snr, c_dev, stream); });
+}
+
+int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *d, const int16_t *c_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                int32_t *iters_dev, int16_t *post_dev, void *stream) {
+    return guarded([&] { return decode_batch_q_dev_impl(d, c_dev, frames, bits_dev, ok_dev, iters_dev, post_dev, stream); });
+}
+
+int acg_ldpc_decode_batch_q(acg_ldpc_decoder *d, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
+                            int16_t *post) {
+    return guarded([&] { return decode_batch_q_impl(d, c, frames, bits, ok, iters, post); });
 }
 
 int acg_ldpc_decoder_sync(acg_ldpc_decoder *d) {

@@ -50,8 +50,11 @@ struct HostPipe {
     static constexpr int NBUF = 2;
     int64_t chunk = 0;       // frames per chunk the buffers are sized for
     size_t y_bytes = 0;      // bytes per frame of the symbol buffers
+    size_t out_bytes = 0;    // bytes per frame of the output buffers (+ 16 per buffer for the alignment of the posteriors)
     PinnedBuf pin_y[NBUF], pin_out[NBUF];  // out: [frames][nwords] words | [frames] sweep counts | [frames] flags of the chunk in
-    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight: one region, so the results come back in ONE device-to-host copy
+    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight (| [frames][n] int16 posteriors from a 16-byte boundary, where
+                                           // acg_ldpc_decode_batch_q is asked for them): one region, so the results come back in
+                                           // ONE device-to-host copy
     hipStream_t stream[NBUF] = {};
     hipEvent_t done[NBUF] = {};
     void release() {
@@ -164,6 +167,8 @@ struct acg_ldpc_decoder {
     LayeredWg layered_wg = LayeredWg::none;
     acg_ldpc_quant quant{};
     acg::QuantArgs qargs{};
+    const void *kernel_qio = nullptr;   // q: the instance of the integer entrance (acg_ldpc_decode_batch_q*) and its resident
+    int grid_cap_qio = 0;               // workgroups; kernel[0] stays the symbol entrance's
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
@@ -231,7 +236,8 @@ QuantArgs quant_args(const acg_ldpc_quant &q);
 // ---- decode.hip ----
 double channel_sigma(double snr);
 void fill_channel(DecodeArgs &a, double snr);
-int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s);
+// qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for
+int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr);
 int ensure_staging(acg_ldpc_decoder *d, int64_t frames);
 void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a);
 DecodeArgs decode_args(const void *y, int y_is_f64, int64_t frames, double snr);

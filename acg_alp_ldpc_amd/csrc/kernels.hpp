@@ -137,6 +137,15 @@ struct QuantArgs {
     float inv_step;   // (float) (1 / llr_step)
     int32_t cmax, rmax, pmax;
     int32_t scale_num, scale_shift, rnd, offset;   // rnd = 2^(scale_shift - 1), 0 for scale_shift = 0
+    // the integer entrance (acg_ldpc_decode_batch_q*), read by the IO instances only.  (Last in the block, and in the one block
+    // that only this kernel reads: no other argument moves.)
+    const int16_t *c_in;   // frames * n channel values, clamped to +-cmax by the kernel
+    int16_t *post_out;     // frames * n posteriors, written with the frame's word; null = off
+};
+// the two pointers as launch_decode takes them
+struct QuantIo {
+    const int16_t *c_in;
+    int16_t *post_out;
 };
 
 // Streamed ("HBM") BP engine: plain CSR of the Tanner graph, read through scalar loads.

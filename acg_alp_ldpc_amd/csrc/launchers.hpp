@@ -69,7 +69,8 @@ hipError_t bp_layered_launch(const void *kernel, const LayerTables &t, const Dec
 // (<= 32, the same tables) and bp_layered_q.hip (fixed-point min-sum, <= 32; L = 64, 128, 256, 512, 1024) ----
 const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo);
 const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo);
-const void *bp_layered_q_kernel_ptr(int L);
+// io: the instance of the integer entrance (QuantArgs::c_in in, QuantArgs::post_out out) instead of the symbol entrance's
+const void *bp_layered_q_kernel_ptr(int L, bool io);
 // q: the quantiser of bp_layered_q_kernel, null for the float kernels
 hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs *q, int grid, int block,
                                 size_t lds, hipStream_t s);

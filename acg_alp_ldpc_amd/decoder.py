@@ -308,3 +308,57 @@ class QuantizedMinSumDecoder(Decoder):
     def _create(self, code, p, h):
         q = self.quant.as_struct()
         return lib().acg_ldpc_decoder_create_quantized(code._h, C.byref(p), C.byref(q), C.byref(h))
+
+    # -- the integer entrance: channel values in, posteriors out (acg_ldpc_decode_batch_q*) ---------
+    def quantize(self, H, Y, snr):
+        """host symbols (float64, or float32 travelling as float32) -> int16 channel values of the same shape: this decoder's
+        quantiser as the symbol entrance applies it (acg_ldpc_debug_quantize).  H is not read: the quantiser knows no code."""
+        f32 = isinstance(Y, np.ndarray) and Y.dtype == np.float32
+        Y = np.ascontiguousarray(Y, dtype=np.float32 if f32 else np.float64)
+        out = np.empty(Y.shape, dtype=np.int16)
+        q = self.quant.as_struct()
+        check(lib().acg_ldpc_debug_quantize(Y.ctypes.data, 0 if f32 else 1, Y.size, float(snr), C.byref(q), out.ctypes.data))
+        return out
+
+    def decode_llr_batch(self, H, C, posteriors=True, out=None):
+        """C: frames x n INTEGER channel values (any integer dtype; every value must fit int16; the decoder clamps them to
+        +-Cmax).  A punctured position is 0, a shortened one +Cmax (known 0) or -Cmax (known 1).  A floating-point array is
+        refused: LLRs are quantised by the caller, or by quantize().
+        out = (bits, ok, iters[, post]) reuses caller arrays.  -> (bits[F,n], ok[F], iters[F][, post[F,n] int16])"""
+        a = np.asarray(C)
+        if a.dtype.kind not in "iu":
+            raise TypeError("decode_llr_batch takes integer channel values, not %s: quantise first (quantize())" % a.dtype)
+        if a.dtype != np.int16:
+            if a.size and (a.min() < -32768 or a.max() > 32767):
+                raise ValueError("channel values must fit int16")
+            a = a.astype(np.int16)
+        a = np.ascontiguousarray(a)
+        with self._lease(H) as (h, code):
+            if a.ndim != 2 or a.shape[1] != code.n:
+                raise ValueError("C must be frames x n")
+            F = a.shape[0]
+            if out is not None:
+                bits, ok, iters = out[:3]
+                post = out[3] if posteriors else None
+                assert bits.shape == (F, code.n) and bits.dtype == np.uint8 and bits.flags.c_contiguous
+                assert ok.shape == (F,) and ok.dtype == np.uint8 and iters.shape == (F,) and iters.dtype == np.int32
+                assert post is None or (post.shape == (F, code.n) and post.dtype == np.int16 and post.flags.c_contiguous)
+            else:
+                bits = np.empty((F, code.n), dtype=np.uint8)
+                ok = np.empty(F, dtype=np.uint8)
+                iters = np.empty(F, dtype=np.int32)
+                post = np.empty((F, code.n), dtype=np.int16) if posteriors else None
+            check(lib().acg_ldpc_decode_batch_q(h, a.ctypes.data, F, bits.ctypes.data, ok.ctypes.data, iters.ctypes.data,
+                                                post.ctypes.data if post is not None else None))
+        return (bits, ok, iters, post) if posteriors else (bits, ok, iters)
+
+    def decode_llr_batch_dev(self, H, c_ptr, frames, bits_ptr, ok_ptr, iters_ptr=None, post_ptr=None, stream=None):
+        """device pointers (ints): frames*n int16 channel values in; packed words, flags, iterations and, where post_ptr is
+        given, frames*n int16 posteriors out; asynchronous on `stream` (None = the decoder's own stream)"""
+        with self._lease(H) as (h, _):
+            check(lib().acg_ldpc_decode_batch_q_dev(h, c_ptr, int(frames), bits_ptr, ok_ptr, iters_ptr, post_ptr, stream))
+
+    def quantize_dev(self, H, y_ptr, y_is_f64, count, snr, c_ptr, stream=None):
+        """device pointers (ints): `count` symbols -> `count` int16 channel values; asynchronous on `stream`"""
+        with self._lease(H) as (h, _):
+            check(lib().acg_ldpc_quantize_dev(h, y_ptr, 1 if y_is_f64 else 0, int(count), float(snr), c_ptr, stream))

@@ -218,6 +218,35 @@ int acg_ldpc_decoder_create_quantized(const acg_ldpc_code *code, const acg_ldpc_
 int acg_ldpc_debug_quantize(const void *y_host, int32_t y_is_f64, int64_t count, double snr, const acg_ldpc_quant *q,
                             int16_t *out_host);
 
+/* The integer entrance of the engine: channel values in, posteriors out.  For bit-true work against another implementation of
+ * the rules above, for channel values from one's own demapper or quantiser, and for channels that symbols + snr cannot express.
+ *   channel value in   a frame is n int16_t values c_v; the decoder starts from P_v = clamp(c_v, -Cmax, +Cmax) (so -32768
+ *                      becomes -Cmax) and every message from 0: exactly the state the symbol entrance reaches when its
+ *                      quantiser yields the same P.  llr_step plays no part and there is no snr.
+ *                      A punctured position is c = 0; a shortened one c = +Cmax (known 0) or -Cmax (known 1).  Nothing special
+ *                      is done for them: they are channel values like any other.
+ *   posterior out      a frame's posterior is n int16_t values P_v, |P_v| <= Pmax, read at the moment the frame's word, flag
+ *                      and iteration are written: for a frame that latches, the posteriors of the round boundary at which its
+ *                      word is formed — with early_exit = 0 the frame is swept on, the posterior written is still the latched
+ *                      one; for a frame that fails, the posteriors after max_iter iterations (its word is zeros as everywhere);
+ *                      for max_iter = 0 the clamped channel value.  So (post < 0) is the word of every frame with ok = 1.
+ * All three take a handle of acg_ldpc_decoder_create_quantized only.  Each returns non-zero, leaves a message in
+ * acg_ldpc_last_error and launches nothing for a null handle, a handle of acg_ldpc_decoder_create, frames (count) < 0, or
+ * frames (count) > 0 with a null input (the host call: also null bits or ok).  frames == 0 is a no-op that returns 0. */
+
+/* the handle's quantiser on the device: count symbols -> count channel values (what acg_ldpc_debug_quantize computes,
+ * asynchronous on `stream`; NULL = the handle's own stream) */
+int acg_ldpc_quantize_dev(acg_ldpc_decoder *dec, const void *y_dev, int32_t y_is_f64, int64_t count, double snr, int16_t *c_dev,
+                          void *stream);
+/* acg_ldpc_decode_batch_dev with channel values in and, if post_dev != NULL, frames*n int16 posteriors out: the same launch
+ * path, so the work-counter ring, the event pair and the stream rules at the top of this header hold for it */
+int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *dec, const int16_t *c_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                int32_t *iters_dev, int16_t *post_dev, void *stream);
+/* host buffers, through the pipelined two-set staging path of acg_ldpc_decode_batch (2 bytes in per value; 2 more out per value
+ * when post is given); post may be NULL */
+int acg_ldpc_decode_batch_q(acg_ldpc_decoder *dec, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
+                            int16_t *post);
+
 /* replaces Decoder::decode(H, y, snr) (algo/algo.h:8) for `frames` frames at once.
  *   y      host, frames*n doubles, raw channel symbols (NOT LLRs; llr = 2y/sigma^2 is formed inside,
  *          channel.h:12-16, bp.h:66, qp_admm.h:27)

@@ -151,6 +151,13 @@ protected:
         }
     }
 
+    // f(handle for H), the handle pinned for the duration of the call as decode() pins its own
+    template <class F>
+    void with_handle(const TMatrix &H, F &&f) {
+        Lease l(this, H);
+        f(l.dec());
+    }
+
 private:
     struct Entry {
         int m = 0, n = 0;
@@ -334,6 +341,44 @@ public:
     explicit QuantizedMinSumDecoder(int max_iter, const acg_ldpc_quant &quant = default_quant(), int lanes_per_frame = 0)
         : _max_iter(max_iter), _lanes(lanes_per_frame), _quant(quant) {}
     std::string name() const override { return "QMS"; }
+
+    // ---- the integer entrance (acg_ldpc.h: acg_ldpc_decode_batch_q*): channel values in, posteriors out ----
+    // Y: symbols -> int16 channel values, this decoder's quantiser as the symbol entrance applies it (acg_ldpc_debug_quantize)
+    std::vector<int16_t> quantize(const std::vector<double> &Y, double snr) const {
+        std::vector<int16_t> c(Y.size());
+        check(acg_ldpc_debug_quantize(Y.data(), 1, (int64_t) Y.size(), snr, &_quant, c.data()));
+        return c;
+    }
+    struct LlrResult {
+        std::vector<uint8_t> bits, ok;   // frames*n bytes (zeros for a failed frame), frames flags
+        std::vector<int32_t> iters;      // frames
+        std::vector<int16_t> post;       // frames*n posteriors; empty when not asked for
+    };
+    // C: frames*n channel values (clamped to +-Cmax by the decoder; punctured = 0, shortened = +-Cmax)
+    LlrResult decode_llr_batch(const TMatrix &H, const std::vector<int16_t> &C, bool posteriors = true) {
+        const size_t n = H[0].size(), frames = C.size() / n;
+        LlrResult r;
+        r.bits.resize(frames * n);
+        r.ok.resize(frames);
+        r.iters.resize(frames);
+        if (posteriors) r.post.resize(frames * n);
+        with_handle(H, [&](acg_ldpc_decoder *d) {
+            check(acg_ldpc_decode_batch_q(d, C.data(), (int64_t) frames, r.bits.data(), r.ok.data(), r.iters.data(),
+                                          posteriors ? r.post.data() : nullptr));
+        });
+        return r;
+    }
+    // device buffers, asynchronous on `stream` (null: the handle's own)
+    void decode_llr_batch_dev(const TMatrix &H, const int16_t *c_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                              int32_t *iters_dev = nullptr, int16_t *post_dev = nullptr, void *stream = nullptr) {
+        with_handle(H, [&](acg_ldpc_decoder *d) {
+            check(acg_ldpc_decode_batch_q_dev(d, c_dev, frames, bits_dev, ok_dev, iters_dev, post_dev, stream));
+        });
+    }
+    void quantize_dev(const TMatrix &H, const void *y_dev, bool y_is_f64, int64_t count, double snr, int16_t *c_dev,
+                      void *stream = nullptr) {
+        with_handle(H, [&](acg_ldpc_decoder *d) { check(acg_ldpc_quantize_dev(d, y_dev, y_is_f64 ? 1 : 0, count, snr, c_dev, stream)); });
+    }
 
 protected:
     void fill(acg_ldpc_params &p) const override {
