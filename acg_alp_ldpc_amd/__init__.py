@@ -11,8 +11,8 @@ from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
 from .decoder import BeliefPropagationDecoder, Decoder, MinSumDecoder, QPADMMDecoder, QuantConfig, QuantizedMinSumDecoder  # noqa: F401
 from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_exp_details, merge_exp_results,  # noqa: F401
-                         run_experiment, run_experiment_codes, run_experiment_detail, run_experiment_grid,
-                         run_experiment_inproc, run_experiment_sharded, shard_range)
+                         quant_structs, run_experiment, run_experiment_codes, run_experiment_detail, run_experiment_grid,
+                         run_experiment_inproc, run_experiment_quants, run_experiment_sharded, shard_range)
 
 
 def read_pcm(path):

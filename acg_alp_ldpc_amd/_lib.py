@@ -99,6 +99,7 @@ SYMBOLS = {
     "acg_ldpc_mc_run_detail": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McDetail), _vp, _vp, _i64]),
     "acg_ldpc_mc_detail_merge": (None, [C.POINTER(McDetail), C.POINTER(McDetail)]),
     "acg_ldpc_mc_run_grid": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _vp, _i32, _vp]),
+    "acg_ldpc_mc_run_quants": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _i32, _vp]),
     "acg_ldpc_evaluator_create": (C.c_int, [C.POINTER(Params), C.POINTER(_vp)]),
     "acg_ldpc_evaluator_destroy": (None, [_vp]),
     "acg_ldpc_mc_run_codes": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),

@@ -457,6 +457,14 @@ static int decoder_setup_layered_wg(acg_ldpc_decoder *d, const acg_ldpc_decoder:
             return 3;
         }
         if (int rc = bind_kernel(d, kio, d->kernel_qio, d->grid_cap_qio)) return rc;
+        // and the grid form of the symbol entrance (acg_ldpc_mc_run_quants)
+        const void *kgrid = bp_layered_q_grid_kernel_ptr(L);
+        HIP_OK(hipFuncGetAttributes(&fa, kgrid));
+        if (lds + fa.sharedSizeBytes > 160 * 1024) {
+            set_error("quantized layered min-sum: a frame (posteriors + messages) does not fit in LDS");
+            return 3;
+        }
+        if (int rc = bind_kernel(d, kgrid, d->kernel_qgrid, d->grid_cap_qgrid)) return rc;
     }
     d->tab.lds_bytes_per_frame = (int32_t) lds;
     return 0;
@@ -1030,7 +1038,7 @@ static std::string describe(const acg_ldpc_decoder *d) {
         const acg_ldpc_quant &q = d->quant;
         snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_q_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "
                                "grid_cap=%d sets=%d steps=%d largest_set=%d schedule=layered messages=int8 posteriors=int16 "
-                               "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d",
+                               "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d mc_quants=single-launch",
                  algo, d->L, d->block, d->lds_block, d->grid_cap[0], d->lbtab.n_sets, d->lbtab.n_steps, d->lblay.width, q.llr_step, q.ch_bits, q.msg_bits,
                  q.post_bits, q.scale_num, q.scale_shift, q.offset);
     } else if (d->layered_wg != acg_ldpc_decoder::LayeredWg::none) {

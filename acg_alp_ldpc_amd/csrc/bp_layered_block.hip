@@ -178,13 +178,14 @@ const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo) {
 }
 
 // The launch of the three workgroup-per-frame layered kernels (this file's, bp_layered_wide.hip's and bp_layered_q.hip's); q: the
-// third argument of bp_layered_q_kernel, null for the float kernels
+// third argument of bp_layered_q_kernel, null for the float kernels; g: the fourth of bp_layered_q_grid_kernel
 hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs *q, int grid, int block, size_t lds,
-                                hipStream_t s) {
+                                hipStream_t s, const QuantGridArgs *g) {
     LayerBlockTables tt = t;
     DecodeArgs aa = a;
     QuantArgs qq = q ? *q : QuantArgs{};
-    void *args[3] = {&tt, &aa, &qq};   // (hipLaunchKernel reads as many as the kernel has parameters)
+    QuantGridArgs gg = g ? *g : QuantGridArgs{};
+    void *args[4] = {&tt, &aa, &qq, &gg};   // (hipLaunchKernel reads as many as the kernel has parameters)
     return hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, s);
 }
 

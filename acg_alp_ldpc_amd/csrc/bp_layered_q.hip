@@ -185,8 +185,20 @@ __device__ __forceinline__ uint32_t q_layer_step(unsigned char *__restrict__ Pb,
 // workgroup per SIMD fewer (24 / (L / 64) per CU instead of 28 / (L / 64)), so those are bound to 7 (72 registers, 4-5 of them in
 // scratch, reloaded once per FRAME: no scratch access inside a round); for L = 512 both figures are three workgroups per CU
 // and the instance keeps its registers.
-template <int L, bool IO>
-__global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 1024 ? 8 : (IO && L <= 256 ? 7 : 6)))) bp_layered_q_kernel(const LayerBlockTables t, const DecodeArgs a, const QuantArgs qa) {
+//
+// Grid: the third form (acg_ldpc_mc_run_quants) — frames of DIFFERENT quantisers in one launch.  Grid is empty for the two
+// forms above, whose argument list is the three blocks, or the one type QuantGridArgs: a fourth argument block that only this
+// form has.  The work counter deals virtual frames vf in [0, points * g.fc): point vf / g.fc decodes frame vf % g.fc of the
+// shared symbol buffer a.y with the eight quantiser words at g.tab + 8 * point, and word, flag and iteration go to index vf.
+// The point index is formed from the first lane's copy of vf (a launch covers fewer than 2^30 virtual frames), so the table is
+// read by scalar loads and the frame's quantiser lies in scalar registers as the kernel argument of the other forms does:
+// everything below sees a QuantArgs and is the same code.  One division per frame.  Under the symbol entrance's bounds it has
+// that one's residency: 67-70 vector registers (7 wavefronts per SIMD) for L <= 512, 64 and 8 for L = 1024.  (Bound to 7 as the
+// IO instances are, L <= 256 drops from 106 to 94 scalar registers and spills 50-52 of them instead of 38-40: 1 % slower.)
+template <int L, bool IO, typename... Grid>
+__global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 1024 ? 8 : (IO && L <= 256 ? 7 : 6)))) bp_layered_q_kernel(const LayerBlockTables t, const DecodeArgs a, const QuantArgs qa_arg, const Grid... grid) {
+    constexpr bool GRID = sizeof...(Grid) != 0;
+    static_assert(!GRID || (sizeof...(Grid) == 1 && !IO), "the grid form: one QuantGridArgs behind the symbol entrance's arguments");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ unsigned long long fr_lds;
     const int l = threadIdx.x;
@@ -225,13 +237,31 @@ __global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(L >= 102
         __syncthreads();
         const int64_t frame = (int64_t) fr_lds;
         if (frame >= a.frames) break;
+        // ---- the frame's quantiser and its row of a.y: the argument and `frame`, or the point's table row and frame % fc -------------
+        QuantArgs qg;
+        size_t sym_frame = (size_t) frame;
+        if constexpr (GRID) {
+            const QuantGridArgs &g = (grid, ...);
+            const uint32_t vf = (uint32_t) __builtin_amdgcn_readfirstlane((int) frame);
+            const uint32_t point = vf / g.fc;
+            const int32_t *const row = g.tab + (size_t) point * 8;
+            qg.inv_step = __builtin_bit_cast(float, qsload(row, 0));
+            qg.cmax = qsload(row, 1), qg.rmax = qsload(row, 2), qg.pmax = qsload(row, 3);
+            qg.scale_num = qsload(row, 4), qg.scale_shift = qsload(row, 5), qg.rnd = qsload(row, 6), qg.offset = qsload(row, 7);
+            qg.c_in = nullptr, qg.post_out = nullptr;
+            sym_frame = (size_t) (vf - point * g.fc);
+        }
+        const QuantArgs &qa = [&]() -> const QuantArgs & {
+            if constexpr (GRID) return qg;
+            else return qa_arg;
+        }();
         // ---- start of a frame: P = quantised channel LLR, R = 0 -------------------------------------------------------------------
         if constexpr (IO) {
             // (rows are n values apart: 2-byte aligned only, so one value per load)
             const int16_t *const c = qa.c_in + (size_t) frame * t.n;
             for (int v = l; v < t.n; v += L) P[v] = (short) min(max((int) c[v], -qa.cmax), qa.cmax);
         } else {
-            for (int v = l; v < t.n; v += L) P[v] = (short) quantize_symbol(a, qa, (size_t) frame * t.n + v);
+            for (int v = l; v < t.n; v += L) P[v] = (short) quantize_symbol(a, qa, sym_frame * t.n + v);
         }
         for (int w = t.n + l; w < 2 * t.p_words; w += L) P[w] = 0;   // neutral cell: decides 0
         {
@@ -318,6 +348,18 @@ static const void *q_kernel_ptr_l(int L) {
 
 // io: the instance of the integer entrance (channel values in, posteriors out)
 const void *bp_layered_q_kernel_ptr(int L, bool io) { return io ? q_kernel_ptr_l<true>(L) : q_kernel_ptr_l<false>(L); }
+
+// the grid form (acg_ldpc_mc_run_quants): a quantiser per virtual frame from QuantGridArgs::tab
+const void *bp_layered_q_grid_kernel_ptr(int L) {
+    switch (L) {
+        case 64: return (const void *) bp_layered_q_kernel<64, false, QuantGridArgs>;
+        case 128: return (const void *) bp_layered_q_kernel<128, false, QuantGridArgs>;
+        case 256: return (const void *) bp_layered_q_kernel<256, false, QuantGridArgs>;
+        case 512: return (const void *) bp_layered_q_kernel<512, false, QuantGridArgs>;
+        case 1024: return (const void *) bp_layered_q_kernel<1024, false, QuantGridArgs>;
+        default: return nullptr;
+    }
+}
 
 // acg_ldpc_debug_quantize: the device function the decode kernel calls, on a plain array of symbols
 __global__ void __launch_bounds__(256) quantize_debug_kernel(const DecodeArgs a, const QuantArgs qa, const int64_t count, int16_t *__restrict__ out) {

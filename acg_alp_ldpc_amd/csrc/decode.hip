@@ -96,9 +96,13 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
 }
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
-int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio) {
+int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid) {
     if (qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qio)) {
         set_error("internal: channel values handed to a decoder that is not quantized");
+        return 11;
+    }
+    if (qgrid && (qio || d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qgrid || !qgrid->tab || qgrid->fc == 0 || a.frames >= ((int64_t) 1 << 30))) {
+        set_error("internal: a quantiser grid handed to a launch that cannot take it");
         return 11;
     }
     a.max_iter = d->p.max_iter;
@@ -164,6 +168,10 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
             q.post_out = qio->post_out;
             const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap_qio);
             HIP_OK(bp_layered_wg_launch(d->kernel_qio, d->lbtab, a, &q, grid, d->block, d->lds_block, s));
+        } else if (qgrid) {
+            // the same launch with the grid form's instance: the quantiser block travels but is not read
+            const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap_qgrid);
+            HIP_OK(bp_layered_wg_launch(d->kernel_qgrid, d->lbtab, a, &d->qargs, grid, d->block, d->lds_block, s, qgrid));
         } else {
             const int grid = (int) std::min<int64_t>(a.frames, d->grid_cap[0]);
             const QuantArgs *q = d->layered_wg == acg_ldpc_decoder::LayeredWg::q ? &d->qargs : nullptr;
@@ -241,11 +249,12 @@ DecodeArgs acg::decode_args(const void *y, int y_is_f64, int64_t frames, double 
 }
 
 // One decode chunk on the handle's stream: symbols already on the device in, outputs in the staging buffers (which the
-// caller reserved).  Caller holds d->mu, so c.slot is this launch's own event pair.
-int acg::decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c) {
+// caller reserved).  qgrid: `frames` virtual frames of a quantiser grid over the qgrid->fc frames at y (launch_decode).
+// Caller holds d->mu, so c.slot is this launch's own event pair.
+int acg::decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const QuantGridArgs *qgrid) {
     c.a = decode_args(y, y_is_f64, frames, snr);
     stage_outputs(d, c.a);
-    const int rc = launch_decode(d, c.a, d->stream);
+    const int rc = launch_decode(d, c.a, d->stream, nullptr, qgrid);
     c.slot = d->last_slot;
     return rc;
 }

@@ -169,6 +169,8 @@ struct acg_ldpc_decoder {
     acg::QuantArgs qargs{};
     const void *kernel_qio = nullptr;   // q: the instance of the integer entrance (acg_ldpc_decode_batch_q*) and its resident
     int grid_cap_qio = 0;               // workgroups; kernel[0] stays the symbol entrance's
+    const void *kernel_qgrid = nullptr; // q: the grid form of the symbol entrance (acg_ldpc_mc_run_quants: a quantiser per virtual
+    int grid_cap_qgrid = 0;             // frame) and its resident workgroups
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
@@ -200,7 +202,8 @@ struct acg_ldpc_decoder {
     // chunk with its pinned copy, the chunk-relative frames selected as events, their records and XOR rows
     acg::DeviceBuf det_counters, det_kind, det_sel, det_events, det_words;
     acg::PinnedBuf det_kind_h, det_sel_h, det_counters_h;
-    // parameter grid (acg_ldpc_mc_run_grid): counters[point][MC_NCOUNTERS] and the per-point tables of the chunk in flight
+    // parameter grid (acg_ldpc_mc_run_grid; quantiser grid, acg_ldpc_mc_run_quants): counters[point][MC_NCOUNTERS] and the
+    // per-point tables of the chunk in flight (q: 32 bytes per point, the head of its QuantArgs)
     acg::DeviceBuf grid_counters, grid_tab;
     // Per-launch work counters: every launch takes the next slot of a small ring of device words (the dynamic frame /
     // tile hand-out of the kernels), so launches of one handle that overlap on different streams never share one.
@@ -237,7 +240,8 @@ QuantArgs quant_args(const acg_ldpc_quant &q);
 double channel_sigma(double snr);
 void fill_channel(DecodeArgs &a, double snr);
 // qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for
-int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr);
+// qgrid != null: the grid form of a quantized handle — a.frames virtual frames, a quantiser per point instead of the handle's
+int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr, const QuantGridArgs *qgrid = nullptr);
 int ensure_staging(acg_ldpc_decoder *d, int64_t frames);
 void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a);
 DecodeArgs decode_args(const void *y, int y_is_f64, int64_t frames, double snr);
@@ -245,7 +249,7 @@ struct Chunk {  // one decode on the handle's stream: its arguments and its even
     DecodeArgs a;
     int slot;
 };
-int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c);
+int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const QuantGridArgs *qgrid = nullptr);
 float chunk_ms(const acg_ldpc_decoder *d, const Chunk &c);
 
 }  // namespace acg

@@ -142,6 +142,12 @@ struct QuantArgs {
     const int16_t *c_in;   // frames * n channel values, clamped to +-cmax by the kernel
     int16_t *post_out;     // frames * n posteriors, written with the frame's word; null = off
 };
+// The grid form of the kernel (bp_layered_q_grid_kernel, acg_ldpc_mc_run_quants): an argument block of its own behind
+// QuantArgs, so no argument of the other instances moves.
+struct QuantGridArgs {
+    const int32_t *tab;   // [points][8]: the first 32 bytes of each point's QuantArgs (inv_step ... offset)
+    uint32_t fc;          // frames per point: virtual frame vf = point * fc + frame
+};
 // the two pointers as launch_decode takes them
 struct QuantIo {
     const int16_t *c_in;

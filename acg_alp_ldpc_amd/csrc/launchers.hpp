@@ -71,9 +71,11 @@ const void *bp_layered_block_kernel_ptr(int L, bool f16, int algo);
 const void *bp_layered_wide_kernel_ptr(int L, bool f16, int algo);
 // io: the instance of the integer entrance (QuantArgs::c_in in, QuantArgs::post_out out) instead of the symbol entrance's
 const void *bp_layered_q_kernel_ptr(int L, bool io);
-// q: the quantiser of bp_layered_q_kernel, null for the float kernels
+// the grid form of the symbol entrance: a quantiser per virtual frame (QuantGridArgs, acg_ldpc_mc_run_quants)
+const void *bp_layered_q_grid_kernel_ptr(int L);
+// q: the quantiser of bp_layered_q_kernel, null for the float kernels; g: the fourth argument of bp_layered_q_grid_kernel
 hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, const DecodeArgs &a, const QuantArgs *q, int grid, int block,
-                                size_t lds, hipStream_t s);
+                                size_t lds, hipStream_t s, const QuantGridArgs *g = nullptr);
 // the kernel's quantiser on `count` symbols (a: y, y_is_f64 and the channel terms) -> count int16
 hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_t count, int16_t *out, hipStream_t s);
 

@@ -1,7 +1,9 @@
 // C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo.  acg_ldpc_mc_run, the detail run, the QP-ADMM
-// parameter grid, the evaluator of a batch of codes, and the generators (device AWGN, host codewords and transmit).
+// parameter grid, the quantiser grid of the fixed-point engine, the evaluator of a batch of codes, and the generators (device
+// AWGN, host codewords and transmit).
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -579,6 +581,96 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
 int acg_ldpc_mc_run_grid(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu, int32_t n_points,
                          acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_grid_impl(d, cfg, alpha, mu, n_points, res); });
+}
+
+// ---------------------------------------------------------------- Monte-Carlo over a grid of quantisers
+// The fixed-point layered min-sum engine's counterpart of the parameter grid above: the chunk loop of its single-launch path
+// (frames in blocks of fb, points in chunks of npc, npc * fb <= the budget virtual frames per launch; the noise of a block drawn
+// once), with bp_layered_q_kernel's grid form reading point k's quantiser from row k of a 32-byte-per-point device table.  The
+// table of the whole call is written once; a chunk's launch points at its first row.  No guard points: every quantiser is
+// checked before anything is launched.  The arguments are checked before the handle is read.
+static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
+                                       acg_ldpc_mc_result *res) {
+    if (!d || !cfg || !quants || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    if (n_points < 1) {
+        set_error("acg_ldpc_mc_run_quants: n_points must be >= 1");
+        return 1;
+    }
+    if (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qgrid) {
+        set_error("acg_ldpc_mc_run_quants needs a decoder of acg_ldpc_decoder_create_quantized");
+        return 3;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    for (int32_t k = 0; k < n_points; k++)
+        if (int rc = acg_ldpc_quant_check(&quants[k])) {
+            set_error("acg_ldpc_mc_run_quants: quants[" + std::to_string(k) + "]: " + last_error());
+            return rc;
+        }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::memset(res, 0, sizeof(*res) * (size_t) n_points);
+    if (cfg->frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    int rc = 0;
+    if ((rc = ensure_codewords(d, cfg))) return rc;
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+    const SentWords cw = sent_words(d, cfg);
+    const int64_t budget = std::min<int64_t>(mc_grid_budget(), ((int64_t) 1 << 30) - 1);   // (the kernel's 32-bit virtual frame)
+    const int64_t fb = std::min<int64_t>(cfg->frames, budget);
+    const int64_t npc = std::max<int64_t>(1, std::min<int64_t>(budget / fb, n_points));
+    // the symbols of one block of frames serve every point; the per-frame outputs are those of npc * fb virtual frames
+    if ((rc = ensure_staging(d, fb))) return rc;
+    if ((rc = d->st_bits.reserve((size_t) (npc * fb) * nwords * sizeof(uint32_t))) || (rc = d->st_ok.reserve((size_t) (npc * fb))) ||
+        (rc = d->st_iters.reserve((size_t) (npc * fb) * sizeof(int32_t))))
+        return rc;
+    const size_t counter_bytes = (size_t) n_points * MC_NCOUNTERS * sizeof(unsigned long long);
+    if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
+    unsigned long long *counters = d->grid_counters.as<unsigned long long>();
+    HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
+    constexpr size_t ROW = 8 * sizeof(int32_t);   // inv_step ... offset: QuantArgs without the two pointers of the integer entrance
+    static_assert(offsetof(QuantArgs, c_in) == ROW, "the quantiser table holds the head of QuantArgs");
+    std::vector<unsigned char> tab_h((size_t) n_points * ROW);
+    for (int32_t k = 0; k < n_points; k++) {
+        const QuantArgs qa = quant_args(quants[k]);
+        std::memcpy(&tab_h[(size_t) k * ROW], &qa, ROW);
+    }
+    if ((rc = d->grid_tab.reserve(tab_h.size()))) return rc;
+    // (the stream is idle: every call on this handle ends with a synchronisation, so the table may be rewritten)
+    HIP_OK(hipMemcpy(d->grid_tab.p, tab_h.data(), tab_h.size(), hipMemcpyHostToDevice));
+    std::vector<double> yh;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
+        const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
+        if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
+        for (int64_t c0 = 0; c0 < n_points; c0 += npc) {
+            const int64_t np = std::min<int64_t>(npc, n_points - c0);
+            const QuantGridArgs g{d->grid_tab.as<const int32_t>() + (size_t) c0 * 8, (uint32_t) fc};
+            Chunk c;
+            if ((rc = decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c, &g))) return rc;
+            HIP_OK(classify_grid_launch(d->st_y.p, host, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
+                                        counters + (size_t) c0 * MC_NCOUNTERS, nullptr, nullptr, d->c.m, d->stream));
+            HIP_OK(hipStreamSynchronize(d->stream));
+            const float ms = chunk_ms(d, c);
+            for (int64_t j = 0; j < np; j++) res[c0 + j].kernel_ms += (double) ms / (double) np;
+        }
+        HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
+    }
+    std::vector<unsigned long long> h((size_t) n_points * MC_NCOUNTERS);
+    HIP_OK(hipMemcpy(h.data(), counters, counter_bytes, hipMemcpyDeviceToHost));
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int32_t k = 0; k < n_points; k++) {
+        counters_to_result(&h[(size_t) k * MC_NCOUNTERS], &res[k]);
+        res[k].time_sec = wall;
+    }
+    return 0;
+}
+
+int acg_ldpc_mc_run_quants(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
+                           acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_quants_impl(d, cfg, quants, n_points, res); });
 }
 
 }  // extern "C"

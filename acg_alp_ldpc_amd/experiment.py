@@ -245,6 +245,60 @@ def run_experiment_grid(decoder, codewords, H, snr, alphas, mus, frames=None, fi
                              kernel_ms=r.kernel_ms) for r in res[:a.size]]
 
 
+def quant_structs(quants):
+    """a sequence of QuantConfig, 7-tuples (llr_step, ch_bits, msg_bits, post_bits, scale_num, scale_shift, offset) or dicts of
+    QuantConfig's fields (the others at their defaults) -> a ctypes array of _lib.Quant, at least one entry long"""
+    from .decoder import QuantConfig
+    out = (_lib.Quant * max(1, len(quants)))()
+    for k, q in enumerate(quants):
+        if isinstance(q, dict):
+            q = QuantConfig(**q)
+        elif not isinstance(q, QuantConfig):
+            q = tuple(q)
+            if len(q) != 7:
+                raise _lib.LdpcError("run_experiment_quants: quants[%d] has %d values, a quantiser has 7" % (k, len(q)))
+            q = QuantConfig(*q)
+        out[k] = q.as_struct()
+    return out
+
+
+def run_experiment_quants(decoder, codewords, H, snr, quants, frames=None, first_frame=0, noise="host", seed=1):
+    """The format search of the fixed-point layered min-sum engine in one call on one handle (acg_ldpc_mc_run_quants): point k
+    decodes the same frames as every other point with quants[k] in place of the decoder's own quantiser.
+
+    decoder: a QuantizedMinSumDecoder; its max_iter, early_exit and lanes_per_frame apply.  quants: QuantConfig, 7-tuples or
+    dicts (quant_structs).  Returns one ExperimentResult per point, equal in the seven counters to run_experiment on
+    QuantizedMinSumDecoder(..., quant=quants[k]); time_sec is the wall time of the whole call and kernel_ms the point's share
+    of device time.  An invalid quantiser anywhere in the list is refused (LdpcError naming its index).  Other arguments as
+    run_experiment."""
+    from .decoder import QuantizedMinSumDecoder
+    if not isinstance(decoder, QuantizedMinSumDecoder):
+        raise _lib.LdpcError("run_experiment_quants needs a QuantizedMinSumDecoder (acg_ldpc_decoder_create_quantized)")
+    quants = list(quants)
+    qs = quant_structs(quants)
+    with decoder._lease(H) as (h, code):
+        cfg = McCfg()
+        cw = None
+        if codewords is not None:
+            cw = np.ascontiguousarray(codewords, dtype=np.uint8)
+            assert cw.ndim == 2 and cw.shape[1] == code.n
+            cfg.codewords = cw.ctypes.data
+            cfg.n_codewords = cw.shape[0]
+        if frames is None:
+            if cw is None:
+                raise ValueError("frames required without codewords")
+            frames = cw.shape[0]
+        cfg.frames = int(frames)
+        cfg.first_frame = int(first_frame)
+        cfg.snr = float(snr)
+        cfg.seed = int(seed)
+        cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
+        res = (McResult * max(1, len(quants)))()
+        check(lib().acg_ldpc_mc_run_quants(h, C.byref(cfg), qs, len(quants), res))
+    return [ExperimentResult(**{f: getattr(r, f) for f in ExperimentResult.FIELDS}, time_sec=r.time_sec,
+                             kernel_ms=r.kernel_ms) for r in res[:len(quants)]]
+
+
 class CodesEvaluator:
     """acg_ldpc_evaluator: scores batches of parity-check matrices of one m x n under one set of QP-ADMM parameters
     (the scoring of optimize_H.cpp:16-25 for many proposals at once).  params_or_decoder: a QPADMMDecoder (its alpha, mu,

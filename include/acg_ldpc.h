@@ -210,7 +210,9 @@ int acg_ldpc_quant_check(const acg_ldpc_quant *q);
  * The handle is an ordinary decoder: acg_ldpc_decode_batch, _f32 and _dev take symbols + snr; acg_ldpc_mc_run and
  * acg_ldpc_mc_run_detail go noise kernel -> decode -> classification kernel; acg_ldpc_mc_run_grid refuses it as it refuses every
  * decoder that is not QP-ADMM; acg_ldpc_decoder_name returns "QMS"; acg_ldpc_decoder_describe names the kernel, the workgroup,
- * sets and steps and the seven values of *q. */
+ * sets and steps and the seven values of *q.
+ * What a number format costs: acg_ldpc_mc_run_quants (declared with the Monte-Carlo calls below) runs acg_ldpc_mc_run for a
+ * whole list of quantisers on ONE such handle, frames of different quantisers sharing a launch. */
 int acg_ldpc_decoder_create_quantized(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
                                       acg_ldpc_decoder **out);
 /* diagnostics: the engine's quantiser, run on the device, on `count` host symbols (doubles if y_is_f64, else floats) at `snr`;
@@ -399,6 +401,29 @@ void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b
  * null pointers. */
 int acg_ldpc_mc_run_grid(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
                          int32_t n_points, acg_ldpc_mc_result *res);
+
+/* The format search of the fixed-point layered min-sum engine: acg_ldpc_mc_run for n_points quantisers quants[k] on ONE handle
+ * of acg_ldpc_decoder_create_quantized.  dec's own quantiser is ignored in this call; its max_iter, early_exit,
+ * lanes_per_frame and device apply.  Every point simulates the same global frames [first_frame, first_frame + frames) with
+ * the same codewords and the same noise (both noise modes), generated once per block of frames.  res[k] (n_points entries)
+ * holds, in its seven integer counters, what acg_ldpc_mc_run returns for *cfg on a handle created with quants[k] and the same
+ * acg_ldpc_params;
+ *   time_sec   of EVERY entry is the wall time of the whole call (not a per-point time: do not add them up);
+ *   kernel_ms  of an entry is the point's share of device time: the device time of the launch (chunk of points) it ran
+ *              in divided by the number of points in that chunk.
+ * Duplicate points are allowed and return equal counters.  Sharding by first_frame / frames and acg_ldpc_mc_merge per point
+ * work as for acg_ldpc_mc_run.  frames == 0 is a no-op that zeroes res and returns 0; max_iter = 0 takes the same path (every
+ * frame fails with 0 iterations).
+ * Single launch (acg_ldpc_decoder_describe of every quantized handle says mc_quants=single-launch): a launch of the kernel's
+ * grid form decodes a chunk of points x frames, the quantiser of a frame read from a device table of 32 bytes per point;
+ * the chunk is sized so that its per-frame outputs are those of a 65536-frame decode.  No handle is created or destroyed and
+ * nothing is allocated per point.
+ * Errors (non-zero, message in acg_ldpc_last_error, nothing launched, res untouched), in this order: null dec, cfg, quants
+ * or res; n_points < 1 (both before the handle is looked at); a handle that is not of acg_ldpc_decoder_create_quantized; a
+ * bad cfg as for acg_ldpc_mc_run; ANY quants[k] that acg_ldpc_quant_check rejects — the message names k and the rule.  There
+ * is no guard point: an invalid format is a caller error. */
+int acg_ldpc_mc_run_quants(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
+                           acg_ldpc_mc_result *res);
 
 /* replaces the scoring of optimize_H.cpp:16-25 for a BATCH of parity-check matrices: acg_ldpc_mc_run for n_codes codes of one
  * m x n under one set of QP-ADMM parameters.  An evaluator owns one stream, one work-counter ring, one set of staging and
