@@ -42,6 +42,12 @@ class McResult(C.Structure):
                 ("time_sec", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class CascadeResult(C.Structure):
+    """acg_ldpc_cascade_result: 2 x McResult + 4 x int64 + 1 double = 184 bytes"""
+    _fields_ = [("total", McResult), ("first", McResult), ("second_frames", C.c_int64), ("second_correct", C.c_int64),
+                ("second_pseudo", C.c_int64), ("second_sum_iters", C.c_int64), ("second_kernel_ms", C.c_double)]
+
+
 class McDetail(C.Structure):
     _fields_ = [("base", McResult), ("word_frames", C.c_int64), ("bit_errors", C.c_int64),
                 ("noncodeword_frames", C.c_int64), ("sum_syndrome_weight", C.c_int64), ("n_events", C.c_int64),
@@ -94,6 +100,18 @@ SYMBOLS = {
     "acg_ldpc_decoder_last_kernel_ms": (C.c_float, [_vp]),
     "acg_ldpc_decoder_layout": (None, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "acg_ldpc_decoder_describe": (_i32, [_vp, C.c_char_p, _i32]),
+    "acg_ldpc_cascade_create": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(Quant), C.POINTER(Params), C.POINTER(Quant),
+                                          C.POINTER(_vp)]),
+    "acg_ldpc_cascade_destroy": (None, [_vp]),
+    "acg_ldpc_cascade_stage": (_vp, [_vp, _i32]),
+    "acg_ldpc_cascade_name": (C.c_char_p, [_vp]),
+    "acg_ldpc_cascade_describe": (_i32, [_vp, C.c_char_p, _i32]),
+    "acg_ldpc_cascade_decode_batch_dev": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_cascade_decode_batch": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_cascade_decode_batch_f32": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_cascade_last_call": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "acg_ldpc_cascade_mc_run": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(CascadeResult)]),
+    "acg_ldpc_cascade_merge": (None, [C.POINTER(CascadeResult), C.POINTER(CascadeResult)]),
     "acg_ldpc_mc_run": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McResult)]),
     "acg_ldpc_mc_merge": (None, [C.POINTER(McResult), C.POINTER(McResult)]),
     "acg_ldpc_mc_run_detail": (C.c_int, [_vp, C.POINTER(McCfg), C.POINTER(McDetail), _vp, _vp, _i64]),

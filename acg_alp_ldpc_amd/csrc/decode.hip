@@ -265,6 +265,14 @@ float acg::chunk_ms(const acg_ldpc_decoder *d, const Chunk &c) {
     return hipEventElapsedTime(&ms, d->ring_ev0[c.slot], d->ring_ev[c.slot]) == hipSuccess ? ms : 0;
 }
 
+// frames per chunk of the pipelined host path: bounded by BYTES (256 MiB of symbols per staging buffer), not by a frame
+// count — 65536 frames of the 10 000-symbol code in doubles would pin 2 x 5.2 GB of host memory and as much HBM per handle
+int64_t acg::host_chunk_frames(int64_t frames, size_t y_bytes) {
+    const int64_t by_bytes = (int64_t) (((size_t) 256 << 20) / std::max<size_t>(y_bytes, 1));
+    const int64_t cap = std::max<int64_t>(1024, std::min<int64_t>(1 << 16, by_bytes));
+    return std::min<int64_t>(frames, cap);
+}
+
 extern "C" {
 
 double acg_ldpc_llr_variance(double snr) { return std::pow(10, -(snr / 10)) / 2; }  // llr_variance, channel.h:12
@@ -320,14 +328,6 @@ static int ensure_pipe(acg_ldpc_decoder *d, int64_t chunk, size_t y_bytes, size_
     P.y_bytes = y_bytes;
     P.out_bytes = out_bytes;
     return 0;
-}
-
-// frames per chunk of the pipelined host path: bounded by BYTES (256 MiB of symbols per staging buffer), not by a frame
-// count — 65536 frames of the 10 000-symbol code in doubles would pin 2 x 5.2 GB of host memory and as much HBM per handle
-static int64_t host_chunk_frames(int64_t frames, size_t y_bytes) {
-    const int64_t by_bytes = (int64_t) (((size_t) 256 << 20) / std::max<size_t>(y_bytes, 1));
-    const int64_t cap = std::max<int64_t>(1024, std::min<int64_t>(1 << 16, by_bytes));
-    return std::min<int64_t>(frames, cap);
 }
 
 // packed words -> one byte per bit, 8 bits at a time through a 256-entry table

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -230,6 +231,40 @@ namespace acg {
 struct DecoderDrop { void operator()(acg_ldpc_decoder *x) const { acg_ldpc_decoder_destroy(x); } };
 using DecoderPtr = std::unique_ptr<acg_ldpc_decoder, DecoderDrop>;
 
+}  // namespace acg
+
+// Two decoders for one code on one device and the buffers of the hand-over between them (cascade.hip; the Monte-Carlo run in
+// mc.hip).  A call holds mu, then stage[0]->mu, then stage[1]->mu.
+struct acg_ldpc_cascade {
+    acg::DecoderPtr stage[2];
+    std::mutex mu;
+    std::string name;  // "<first>+<second>"
+    int device = 0;
+    // the chunk in flight: the failed frames' indices and their count (with its pinned copy), their symbols, and the second
+    // decoder's outputs for them; sized by ensure() for the largest chunk so far, released by release()
+    int64_t cap_frames = 0;
+    size_t cap_row = 0;  // bytes of a symbol row the compact buffer was sized for
+    acg::DeviceBuf idx, count, c_y, c_bits, c_ok, c_iters;
+    acg::PinnedBuf count_h;
+    // recorded behind every chunk that handed frames on: the next chunk waits for it on ITS stream before it reuses the buffers
+    hipEvent_t tail_ev = nullptr;
+    bool tail_used = false;
+    // of the most recent decode call (acg_ldpc_cascade_last_call): the second stage's launch of the last chunk may still run,
+    // so its event slot is kept instead of its time
+    int64_t last_chunk = 0;  // frames per chunk that call used
+    int64_t last_second = 0;
+    float last_ms[2] = {0, 0};
+    int pending_slot = -1;
+    // Monte-Carlo run: symbols and outputs of a chunk; counters rows `first`, `total`, then the second stage's sweeps
+    acg::DeviceBuf mc_y, mc_bits, mc_ok, mc_iters, mc_counters;
+    void release() {
+        idx.reset(), count.reset(), c_y.reset(), c_bits.reset(), c_ok.reset(), c_iters.reset(), count_h.reset();
+        cap_frames = 0, cap_row = 0;
+    }
+};
+
+namespace acg {
+
 // ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own;
 // quant != null: the fixed-point layered min-sum engine of acg_ldpc_decoder_create_quantized) ----
 int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
@@ -251,5 +286,27 @@ struct Chunk {  // one decode on the handle's stream: its arguments and its even
 };
 int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const QuantGridArgs *qgrid = nullptr);
 float chunk_ms(const acg_ldpc_decoder *d, const Chunk &c);
+// frames per chunk of the pipelined host path for symbol rows of y_bytes: at most 65536 frames / 256 MiB of symbols
+int64_t host_chunk_frames(int64_t frames, size_t y_bytes);
+
+// ---- cascade.hip ----
+// frames per chunk of a cascade call over `frames` frames of symbol rows of row_bytes (host_chunk_frames; ACG_CASCADE_CHUNK lowers it)
+int64_t cascade_chunk_frames(int64_t frames, size_t row_bytes);
+// the Monte-Carlo run's two looks into a chunk, both on the chunk's stream: first_done when stage 0's outputs stand in the
+// caller's buffers (before the select), second_done(K) when stage 1's stand in the compact ones (before the scatter)
+struct CascadeHooks {
+    std::function<int()> first_done;
+    std::function<int(int64_t)> second_done;
+};
+// One chunk of fc <= the frames ensure()d: stage 0 -> select -> wait for K -> gather, stage 1, scatter (asynchronous behind the
+// wait); K and the launches' times are added to c->last_second / c->last_ms.  Caller holds the three mutexes, has set the
+// device and called cascade_begin and cascade_ensure for fc.
+int cascade_ensure(acg_ldpc_cascade *c, int64_t frames, size_t row_bytes);
+// a new call in chunks of `chunk` frames: what acg_ldpc_cascade_last_call reports starts from zero
+void cascade_begin(acg_ldpc_cascade *c, int64_t chunk);
+// waits for the second stage's launch of the last chunk, which a call leaves running, and books its time in c->last_ms[1]
+int cascade_settle(acg_ldpc_cascade *c);
+int cascade_chunk_dev(acg_ldpc_cascade *c, const void *y, int y_is_f64, int64_t fc, double snr, uint32_t *bits, uint8_t *ok, int32_t *iters,
+                      uint8_t *stage, hipStream_t s, const CascadeHooks *hooks = nullptr);
 
 }  // namespace acg

@@ -58,6 +58,17 @@ hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bit
                                 int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
                                 hipStream_t s);
 
+// ---- cascade_kernels.hip: the glue of a two-stage decode, per chunk of frames (an int32 count: at most 65536) ----
+// idx[0 .. *count) = the frames with ok == 0, ascending; stage (may be null) = 1 for every frame.  idx: `frames` entries
+hipError_t cascade_select_launch(const uint8_t *ok, int32_t frames, int32_t *idx, int32_t *count, uint8_t *stage, hipStream_t s);
+// row k of out = row idx[k] of y, rows of n symbols of elem = 4 or 8 bytes
+hipError_t cascade_gather_launch(const void *y, int elem, int32_t n, const int32_t *idx, int32_t K, void *out, hipStream_t s);
+// rows idx[k] of bits / ok / iters (may be null) / stage (may be null, = 2) from row k of the compact outputs
+hipError_t cascade_scatter_launch(const uint32_t *cbits, const uint8_t *cok, const int32_t *citers, const int32_t *idx, int32_t K,
+                                  int32_t nwords, uint32_t *bits, uint8_t *ok, int32_t *iters, uint8_t *stage, hipStream_t s);
+// *sum += iters[0 .. K)
+hipError_t cascade_sum_iters_launch(const int32_t *iters, int32_t K, unsigned long long *sum, hipStream_t s);
+
 // ---- bp_block.hip, bp_pair.hip, bp_layered.hip ----
 const void *bp_block_kernel_ptr(int algo, int f64, int L, bool mc, bool idxlds, bool idxreg, bool regular);
 const void *bp_block_kernel_ptr_dbg(int f64);

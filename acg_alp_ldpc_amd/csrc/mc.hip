@@ -1,6 +1,6 @@
 // C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo.  acg_ldpc_mc_run, the detail run, the QP-ADMM
-// parameter grid, the quantiser grid of the fixed-point engine, the evaluator of a batch of codes, and the generators (device
-// AWGN, host codewords and transmit).
+// parameter grid, the quantiser grid of the fixed-point engine, the run through a cascade (cascade.hip), the evaluator of a batch
+// of codes, and the generators (device AWGN, host codewords and transmit).
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -671,6 +671,108 @@ static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cf
 int acg_ldpc_mc_run_quants(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
                            acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_quants_impl(d, cfg, quants, n_points, res); });
+}
+
+// ---------------------------------------------------------------- Monte-Carlo through a cascade
+// The unfused route, chunk by chunk, a Monte-Carlo chunk being one chunk of the cascade's device path (cascade_chunk_dev): noise
+// (AWGN kernel, or transmit_host and a copy) -> stage 0 -> classification into row `first` -> select / gather / stage 1 / scatter
+// -> classification of the merged outputs into row `total`.  The frames of stage 1 had ok = 0 after stage 0 and so count as
+// neither correct nor pseudo in `first`: second_correct and second_pseudo are the differences of the two rows.  The sweeps of
+// stage 1 are summed from its compact outputs (cascade_sum_iters_launch) into the word behind the two rows.
+static int cascade_mc_run_impl(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, acg_ldpc_cascade_result *res) {
+    if (!c || !cfg || !res) {
+        set_error("null argument");
+        return 1;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    std::memset(res, 0, sizeof(*res));
+    const auto t0 = std::chrono::steady_clock::now();
+    acg_ldpc_decoder *d0 = c->stage[0].get(), *d1 = c->stage[1].get();
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::lock_guard<std::recursive_mutex> lk0(d0->mu);
+    std::lock_guard<std::recursive_mutex> lk1(d1->mu);
+    const int n = d0->c.n, nwords = (n + 31) / 32;
+    const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+    const size_t row = (size_t) n * (host ? sizeof(double) : sizeof(float));
+    const int64_t chunk = cascade_chunk_frames(cfg->frames, row);
+    cascade_begin(c, chunk);
+    if (cfg->frames == 0) return 0;
+    HIP_OK(hipSetDevice(c->device));
+    int rc = 0;
+    if ((rc = ensure_codewords(d0, cfg))) return rc;
+    if ((rc = cascade_ensure(c, chunk, row))) return rc;
+    const size_t fcap = (size_t) chunk;
+    if ((rc = c->mc_y.reserve(fcap * row)) || (rc = c->mc_bits.reserve(fcap * nwords * sizeof(uint32_t))) || (rc = c->mc_ok.reserve(fcap)) ||
+        (rc = c->mc_iters.reserve(fcap * sizeof(int32_t))))
+        return rc;
+    constexpr size_t NC = 2 * MC_NCOUNTERS + 1;
+    if ((rc = c->mc_counters.reserve(NC * sizeof(unsigned long long)))) return rc;
+    unsigned long long *counters = c->mc_counters.as<unsigned long long>();
+    hipStream_t s = d0->stream;
+    HIP_OK(hipMemsetAsync(counters, 0, NC * sizeof(unsigned long long), s));
+    // QP-ADMM's flag is not IsCodeword (qp_admm.h:177): its frames are classified with the CSR walk.  Row `first` as
+    // acg_ldpc_mc_run classifies for stage 0; row `total` with the walk where either stage needs it (a word BP returned with
+    // ok = 1 passes it by definition)
+    const int32_t *row0 = nullptr, *col0 = nullptr, *row1 = nullptr, *col1 = nullptr;
+    if (d0->admm) (void) admm_device_unfused_mc(d0->admm.get(), &row0, &col0);
+    if (d1->admm) (void) admm_device_unfused_mc(d1->admm.get(), &row1, &col1);
+    const int32_t *rowt = row0 ? row0 : row1, *colt = row0 ? col0 : col1;
+    const SentWords cw = sent_words(d0, cfg);
+    uint32_t *bits = c->mc_bits.as<uint32_t>();
+    uint8_t *ok = c->mc_ok.as<uint8_t>();
+    int32_t *iters = c->mc_iters.as<int32_t>();
+    std::vector<double> yh;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+        if (host) {
+            yh.resize((size_t) fc * n);
+            transmit_host(cfg->codewords, cfg->n_codewords, n, first, fc, cfg->snr, yh.data());
+            HIP_OK(hipMemcpyAsync(c->mc_y.p, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        } else {
+            HIP_OK(awgn_launch(c->mc_y.as<float>(), fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), s));
+        }
+        CascadeHooks hooks;
+        hooks.first_done = [&] {
+            HIP_OK(classify_grid_launch(c->mc_y.p, host, bits, ok, iters, fc, 1, n, nwords, first, cw.dev, cw.n, counters, row0, col0, d0->c.m, s));
+            return 0;
+        };
+        hooks.second_done = [&](int64_t K) {
+            HIP_OK(cascade_sum_iters_launch(c->c_iters.as<int32_t>(), (int32_t) K, counters + 2 * MC_NCOUNTERS, s));
+            return 0;
+        };
+        if ((rc = cascade_chunk_dev(c, c->mc_y.p, host, fc, cfg->snr, bits, ok, iters, nullptr, s, &hooks))) return rc;
+        HIP_OK(classify_grid_launch(c->mc_y.p, host, bits, ok, iters, fc, 1, n, nwords, first, cw.dev, cw.n, counters + MC_NCOUNTERS, rowt, colt,
+                                    d0->c.m, s));
+        HIP_OK(hipStreamSynchronize(s));   // (the chunk's buffers and yh are rewritten by the next one)
+        if ((rc = cascade_settle(c))) return rc;
+    }
+    unsigned long long h[NC];
+    HIP_OK(hipMemcpy(h, counters, sizeof(h), hipMemcpyDeviceToHost));
+    counters_to_result(h, &res->first);
+    counters_to_result(h + MC_NCOUNTERS, &res->total);
+    res->second_frames = c->last_second;
+    res->second_correct = res->total.correct - res->first.correct;
+    res->second_pseudo = res->total.pseudo - res->first.pseudo;
+    res->second_sum_iters = (int64_t) h[2 * MC_NCOUNTERS];
+    res->first.kernel_ms = c->last_ms[0];
+    res->second_kernel_ms = c->last_ms[1];
+    res->total.kernel_ms = (double) c->last_ms[0] + (double) c->last_ms[1];
+    res->total.time_sec = res->first.time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+int acg_ldpc_cascade_mc_run(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, acg_ldpc_cascade_result *res) {
+    return guarded([&] { return cascade_mc_run_impl(c, cfg, res); });
+}
+
+void acg_ldpc_cascade_merge(acg_ldpc_cascade_result *a, const acg_ldpc_cascade_result *b) {
+    acg_ldpc_mc_merge(&a->total, &b->total);
+    acg_ldpc_mc_merge(&a->first, &b->first);
+    a->second_frames += b->second_frames;
+    a->second_correct += b->second_correct;
+    a->second_pseudo += b->second_pseudo;
+    a->second_sum_iters += b->second_sum_iters;
+    a->second_kernel_ms += b->second_kernel_ms;
 }
 
 }  // extern "C"

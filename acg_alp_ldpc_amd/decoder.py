@@ -26,46 +26,32 @@ from ._lib import Params, check, lib
 from .code import ParityCheckMatrix
 
 
-class Decoder:
-    _algo = None
-    _name = None   # name() where the algorithm alone does not give it
+class _HandleCache:
+    """The analysed-graph cache of a decoder object: device handles keyed on H, least recently used first, a handle in use
+    never evicted.  A subclass says where its handles come from (_create) and how they go (_destroy)."""
 
     # The reference hands H to every decode() (algo/algo.h:8) and its optimize_H loop hands a NEW H per proposal to one
     # shared decoder (optimize_H.cpp:16-25,89-104): the analysed-graph cache is therefore bounded.  Least recently used
     # handles beyond MAX_HANDLES are destroyed (device memory, streams and events go with them).
     MAX_HANDLES = 8
 
-    def __init__(self, max_iter, early_exit=True, precision=_lib.PREC_DEFAULT, device=-1, lanes_per_frame=0,
-                 engine=_lib.ENGINE_AUTO, schedule=_lib.SCHEDULE_FLOODING, fast_setup=False, max_handles=None):
-        self.max_iter = int(max_iter)
-        self.early_exit = bool(early_exit)
-        self.precision = precision
-        self.device = device
-        self.lanes_per_frame = lanes_per_frame
-        self.engine = engine
-        self.schedule = schedule
-        self.fast_setup = bool(fast_setup)
+    def __init__(self, max_handles=None):
         self.max_handles = int(max_handles) if max_handles else self.MAX_HANDLES
         self._handles = collections.OrderedDict()  # analysed-graph cache keyed on H (SURVEY §8b "Inputs"), LRU order
         self._pins = collections.Counter()         # calls in flight per key: a handle in use is never evicted
         self._lock = threading.RLock()             # (ctypes calls release the GIL: one decoder object may be used from threads)
 
-    # -- parameters -------------------------------------------------------------------------
-    def _params(self):
-        p = Params()
-        lib().acg_ldpc_params_default(C.byref(p))
-        p.algo = self._algo
-        p.max_iter = self.max_iter
-        p.early_exit = 1 if self.early_exit else 0
-        p.precision = self.precision
-        p.device = self.device
-        p.lanes_per_frame = self.lanes_per_frame
-        p.engine = self.engine
-        p.schedule = self.schedule
-        p.fast_setup = 1 if self.fast_setup else 0
-        return p
+    def _create(self, code, p, h):
+        """the create call of the C ABI this class's handles come from (p: what _params() returned) -> its return code"""
+        raise NotImplementedError
 
-    # -- handle cache -----------------------------------------------------------------------
+    def _destroy(self, h):
+        """the destroy call for a handle of _create"""
+        raise NotImplementedError
+
+    def _params(self):
+        raise NotImplementedError
+
     def _key(self, H):
         """ParityCheckMatrix objects are keyed on identity (they are immutable); dense arrays on their CONTENT: shape + the
         packed bits themselves (5.6 KB for 160 x 280), compared for equality by the dict — a hash alone could collide and
@@ -97,10 +83,6 @@ class Decoder:
         self._trim()
         return ent
 
-    def _create(self, code, p, h):
-        """the create call of the C ABI this class's handles come from -> its return code"""
-        return lib().acg_ldpc_decoder_create(code._h, C.byref(p), C.byref(h))
-
     def _trim(self):
         if len(self._handles) <= self.max_handles:
             return
@@ -109,7 +91,7 @@ class Decoder:
                 break
             if self._pins[k] == 0 and k != next(reversed(self._handles)):
                 old, _ = self._handles.pop(k)
-                lib().acg_ldpc_decoder_destroy(old)   # synchronises the handle's stream first
+                self._destroy(old)   # synchronises the handle's stream first
 
     @contextlib.contextmanager
     def _lease(self, H):
@@ -131,7 +113,7 @@ class Decoder:
     def close(self):
         with self._lock:
             for h, _ in self._handles.values():
-                lib().acg_ldpc_decoder_destroy(h)
+                self._destroy(h)
             self._handles = collections.OrderedDict()
             self._pins.clear()
 
@@ -140,6 +122,44 @@ class Decoder:
             self.close()
         except Exception:
             pass
+
+
+class Decoder(_HandleCache):
+    _algo = None
+    _name = None   # name() where the algorithm alone does not give it
+
+    def __init__(self, max_iter, early_exit=True, precision=_lib.PREC_DEFAULT, device=-1, lanes_per_frame=0,
+                 engine=_lib.ENGINE_AUTO, schedule=_lib.SCHEDULE_FLOODING, fast_setup=False, max_handles=None):
+        super().__init__(max_handles)
+        self.max_iter = int(max_iter)
+        self.early_exit = bool(early_exit)
+        self.precision = precision
+        self.device = device
+        self.lanes_per_frame = lanes_per_frame
+        self.engine = engine
+        self.schedule = schedule
+        self.fast_setup = bool(fast_setup)
+
+    # -- parameters -------------------------------------------------------------------------
+    def _params(self):
+        p = Params()
+        lib().acg_ldpc_params_default(C.byref(p))
+        p.algo = self._algo
+        p.max_iter = self.max_iter
+        p.early_exit = 1 if self.early_exit else 0
+        p.precision = self.precision
+        p.device = self.device
+        p.lanes_per_frame = self.lanes_per_frame
+        p.engine = self.engine
+        p.schedule = self.schedule
+        p.fast_setup = 1 if self.fast_setup else 0
+        return p
+
+    def _create(self, code, p, h):
+        return lib().acg_ldpc_decoder_create(code._h, C.byref(p), C.byref(h))
+
+    def _destroy(self, h):
+        lib().acg_ldpc_decoder_destroy(h)
 
     # -- reference API ----------------------------------------------------------------------
     def name(self):
@@ -362,3 +382,97 @@ class QuantizedMinSumDecoder(Decoder):
         """device pointers (ints): `count` symbols -> `count` int16 channel values; asynchronous on `stream`"""
         with self._lease(H) as (h, _):
             check(lib().acg_ldpc_quantize_dev(h, y_ptr, 1 if y_is_f64 else 0, int(count), float(snr), c_ptr, stream))
+
+
+class CascadeDecoder(_HandleCache):
+    """Two-stage decoding (acg_ldpc_cascade_*): `first` decodes every frame, `second` only the frames `first` fails (ok = 0),
+    from the same symbols; the hand-over stays on the device.  first, second: Decoder objects as PARAMETER CARRIERS — their
+    _params() and, for a QuantizedMinSumDecoder, their quantiser.  Their own handles are not borrowed: a cascade handle owns
+    its two decoders, and this object caches cascade handles per H with the discipline of every Decoder.
+
+        decode(H, channel_word, snr) -> (codeword, ok)
+        decode_batch(H, Y, snr) -> (bits[F,n], ok[F], iters[F], stage[F])    stage: 1 or 2, the stage that produced the row
+        name() -> "<first>+<second>", e.g. "MS+BP"
+    """
+
+    def __init__(self, first, second, max_handles=None):
+        for d in (first, second):
+            if not isinstance(d, Decoder):
+                raise TypeError("CascadeDecoder takes two Decoder objects, not %s" % type(d).__name__)
+        super().__init__(max_handles)
+        self.first, self.second = first, second
+
+    def _params(self):
+        return self.first._params(), self.second._params()
+
+    @staticmethod
+    def _quant(d):
+        return C.byref(d.quant.as_struct()) if isinstance(d, QuantizedMinSumDecoder) else None
+
+    def _key(self, H):
+        return super()._key(H) + tuple(("quant",) + d.quant.as_tuple() if isinstance(d, QuantizedMinSumDecoder) else ()
+                                       for d in (self.first, self.second))
+
+    def _create(self, code, p, h):
+        return lib().acg_ldpc_cascade_create(code._h, C.byref(p[0]), self._quant(self.first), C.byref(p[1]),
+                                             self._quant(self.second), C.byref(h))
+
+    def _destroy(self, h):
+        lib().acg_ldpc_cascade_destroy(h)
+
+    def name(self):
+        return self.first.name() + "+" + self.second.name()
+
+    def stage_handle(self, H, stage):
+        """the borrowed decoder handle of stage 0 / 1 of the cascade handle for H (acg_ldpc_cascade_stage): valid while that
+        cascade handle lives; never destroy it"""
+        h, _ = self.handle(H)
+        s = lib().acg_ldpc_cascade_stage(h, int(stage))
+        if not s:
+            raise _lib.LdpcError(lib().acg_ldpc_last_error().decode())
+        return C.c_void_p(s)
+
+    def decode(self, H, channel_word, snr):
+        bits, ok, _, stage = self.decode_batch(H, np.asarray(channel_word, dtype=np.float64)[None, :], snr)
+        last = self.first if stage[0] == 1 else self.second
+        if not ok[0] and last._algo != _lib.ALGO_QPADMM:
+            return np.zeros(0, dtype=np.uint8), False  # {TCodeword(), false}, bp.h:198
+        return bits[0], bool(ok[0])
+
+    def decode_batch(self, H, Y, snr):
+        """Y: frames x n channel symbols, float64 or float32 (travels as float32), as Decoder.decode_batch"""
+        f32 = isinstance(Y, np.ndarray) and Y.dtype == np.float32
+        Y = np.ascontiguousarray(Y, dtype=np.float32 if f32 else np.float64)
+        with self._lease(H) as (h, code):
+            if Y.ndim != 2 or Y.shape[1] != code.n:
+                raise ValueError("Y must be frames x n")
+            F = Y.shape[0]
+            bits = np.empty((F, code.n), dtype=np.uint8)
+            ok = np.empty(F, dtype=np.uint8)
+            iters = np.empty(F, dtype=np.int32)
+            stage = np.empty(F, dtype=np.uint8)
+            fn = lib().acg_ldpc_cascade_decode_batch_f32 if f32 else lib().acg_ldpc_cascade_decode_batch
+            check(fn(h, Y.ctypes.data, F, float(snr), bits.ctypes.data, ok.ctypes.data, iters.ctypes.data, stage.ctypes.data))
+        return bits, ok, iters, stage
+
+    def decode_batch_dev(self, H, y_ptr, y_is_f64, frames, snr, bits_ptr, ok_ptr, iters_ptr=None, stage_ptr=None, stream=None):
+        """device pointers (ints); one host wait per chunk of 65536 frames, the tail asynchronous on `stream` (None = the
+        first decoder's own stream)"""
+        with self._lease(H) as (h, _):
+            check(lib().acg_ldpc_cascade_decode_batch_dev(h, y_ptr, 1 if y_is_f64 else 0, int(frames), float(snr), bits_ptr,
+                                                          ok_ptr, iters_ptr, stage_ptr, stream))
+
+    def describe(self, H):
+        """both stages' describe lines, the chunk and the last call's second-stage frames"""
+        h, _ = self.handle(H)
+        buf = C.create_string_buffer(4096)
+        lib().acg_ldpc_cascade_describe(h, buf, 4096)
+        return buf.value.decode()
+
+    def last_call(self, H):
+        """(frames handed to the second stage, device ms of the first decoder's launches, of the second's) of the most recent
+        call on the handle for H; waits for the second stage's last launch"""
+        h, _ = self.handle(H)
+        k, a, b = C.c_int64(), C.c_float(), C.c_float()
+        check(lib().acg_ldpc_cascade_last_call(h, C.byref(k), C.byref(a), C.byref(b)))
+        return k.value, a.value, b.value

@@ -102,6 +102,47 @@ def run_experiment(decoder, codewords, H, snr, frames=None, first_frame=0, noise
                             kernel_ms=res.kernel_ms)
 
 
+CASCADE_EXTRAS = ("second_frames", "second_correct", "second_pseudo", "second_sum_iters", "second_kernel_ms")
+
+
+def run_experiment_cascade(cascade, codewords, H, snr, frames=None, first_frame=0, noise="host", seed=1):
+    """acg_ldpc_cascade_mc_run: run_experiment through a CascadeDecoder.  Returns (total, first, extras): the ExperimentResult
+    of the returned outputs, the ExperimentResult of the first decoder alone on the same frames (its seven counters are
+    run_experiment's on that decoder), and a dict of the second stage's figures (CASCADE_EXTRAS): the frames handed to it, how
+    many of them it decoded correctly / to a pseudo-codeword, its sweeps and its device time.  Arguments as run_experiment."""
+    with cascade._lease(H) as (h, code):
+        cfg = McCfg()
+        cw = None
+        if codewords is not None:
+            cw = np.ascontiguousarray(codewords, dtype=np.uint8)
+            assert cw.ndim == 2 and cw.shape[1] == code.n
+            cfg.codewords = cw.ctypes.data
+            cfg.n_codewords = cw.shape[0]
+        if frames is None:
+            if cw is None:
+                raise ValueError("frames required without codewords")
+            frames = cw.shape[0]
+        cfg.frames = int(frames)
+        cfg.first_frame = int(first_frame)
+        cfg.snr = float(snr)
+        cfg.seed = int(seed)
+        cfg.noise = _lib.NOISE_HOST_MT19937 if noise == "host" else _lib.NOISE_DEVICE_PHILOX
+        res = _lib.CascadeResult()
+        check(lib().acg_ldpc_cascade_mc_run(h, C.byref(cfg), C.byref(res)))
+    total, first = (ExperimentResult(**{f: getattr(r, f) for f in ExperimentResult.FIELDS}, time_sec=r.time_sec,
+                                     kernel_ms=r.kernel_ms) for r in (res.total, res.first))
+    return total, first, {f: getattr(res, f) for f in CASCADE_EXTRAS}
+
+
+def merge_cascade_results(a, b):
+    """acg_ldpc_cascade_merge for shards, on the triples run_experiment_cascade returns: everything adds.  a is updated and returned."""
+    merge_exp_results(a[0], b[0])
+    merge_exp_results(a[1], b[1])
+    for f in CASCADE_EXTRAS:
+        a[2][f] += b[2][f]
+    return a
+
+
 # acg_ldpc_mc_event as a numpy record (32 bytes)
 EVENT_DTYPE = np.dtype([("frame", "<i8"), ("kind", "<i4"), ("iters", "<i4"), ("raw_errors", "<i4"), ("bit_errors", "<i4"),
                         ("syndrome_weight", "<i4"), ("reserved", "<i4")])

@@ -291,6 +291,61 @@ void acg_ldpc_decoder_layout(const acg_ldpc_decoder *dec, int32_t *lds_bytes_per
  * timed leg).  Writes at most cap bytes incl. the terminating 0; returns the size the full text needs. */
 int32_t acg_ldpc_decoder_describe(const acg_ldpc_decoder *dec, char *buf, int32_t cap);
 
+/* ---- two-stage decoding: a second decoder for the frames the first fails (build-added) ------ */
+
+/* A cascade owns TWO decoders for one code on one device: a cheap one that sees every frame and a strong one that sees only
+ * the frames the cheap one gives up on.  Semantics, per frame.  Let (w1, ok1, it1) be what stage 0 returns for the frame.
+ *   ok1 = 1   the cascade returns (w1, 1, it1) and stage = 1;
+ *   ok1 = 0   it returns (w2, ok2, it2) and stage = 2: what stage 1 returns for the same symbols at the same snr.
+ * iters is the count of the stage that produced the result (a second-stage frame spent max_iter of the first on top of it);
+ * the flag is that stage's flag (QP-ADMM reports 1 for every frame it touches).  A frame's result depends on the frame only,
+ * not on the batch it is in, so the cascade equals the two handles run by hand: stage 0 on everything, stage 1 on the compacted
+ * failed rows, the results put back.  Any two decoders are accepted, quantized handles included (symbol entrance).  A first
+ * stage that never fails (QP-ADMM without its guard) leaves the second idle; max_iter = 0 or a guard decoder as first stage
+ * sends every frame on.  Neither is an error.
+ * Device path, per chunk of at most 65536 frames / 256 MiB of symbols (the bound of acg_ldpc_decode_batch's staging) on the
+ * caller's stream: stage 0 into the caller's outputs -> cascade_select_kernel (the ascending list of the frames with ok = 0 and
+ * their number K) -> K comes to the host in one small copy followed by a wait on the stream: THE ONE HOST WAIT PER CHUNK -> if
+ * K > 0: cascade_gather_kernel (their symbol rows into a compact batch), stage 1 over K frames through the ordinary launch path
+ * (work-counter ring, event pair and stream rules at the top of this header), cascade_scatter_kernel (words, flag, iterations,
+ * stage = 2 back to their rows).  The tail of the last chunk is asynchronous, as acg_ldpc_decode_batch_dev is: outputs are
+ * complete once the stream is idle.  The hand-over buffers belong to the cascade, so two calls on different streams are ordered
+ * on the device, not concurrent.  A call holds the cascade's mutex, then stage 0's, then stage 1's. */
+typedef struct acg_ldpc_cascade acg_ldpc_cascade;
+/* q_first / q_second: NULL = that stage comes from acg_ldpc_decoder_create, else from acg_ldpc_decoder_create_quantized with that
+ * quantiser.  Refused (non-zero, message in acg_ldpc_last_error): null code, params or out; params that resolve to different
+ * devices (-1 = the current device); whatever the two create calls refuse, with their message prefixed "first: " / "second: ". */
+int acg_ldpc_cascade_create(const acg_ldpc_code *code, const acg_ldpc_params *first, const acg_ldpc_quant *q_first,
+                            const acg_ldpc_params *second, const acg_ldpc_quant *q_second, acg_ldpc_cascade **out);
+void acg_ldpc_cascade_destroy(acg_ldpc_cascade *c);
+/* the two decoders, borrowed (stage 0 / 1; anything else: NULL): ordinary handles for describe, layout, or a decode of their
+ * own; never destroy them */
+acg_ldpc_decoder *acg_ldpc_cascade_stage(acg_ldpc_cascade *c, int32_t stage);
+/* "<first>+<second>" of acg_ldpc_decoder_name, e.g. "MS+BP", "BP+QP-ADMM" */
+const char *acg_ldpc_cascade_name(const acg_ldpc_cascade *c);
+/* "cascade <name> | first: <describe line> | second: <describe line> | chunk=<frames per chunk> last_second_frames=<K>", the
+ * last two of the most recent call; buf / cap / return value as acg_ldpc_decoder_describe */
+int32_t acg_ldpc_cascade_describe(const acg_ldpc_cascade *c, char *buf, int32_t cap);
+
+/* buffers as acg_ldpc_decode_batch_dev; stage_dev: device, frames bytes, written 1 or 2 for every frame (may be NULL, and so may
+ * iters_dev); stream: NULL = stage 0's own stream.  frames == 0 is a no-op that returns 0.  Refused with a message, nothing
+ * launched: a null cascade, frames < 0, a null y_dev with frames > 0, null bits_dev or ok_dev.  A K outside 0 ... chunk read back
+ * from the device fails the call without a further launch. */
+int acg_ldpc_cascade_decode_batch_dev(acg_ldpc_cascade *c, const void *y_dev, int32_t y_is_f64, int64_t frames, double snr,
+                                      uint32_t *bits_dev, uint8_t *ok_dev, int32_t *iters_dev, uint8_t *stage_dev, void *stream);
+/* host buffers as acg_ldpc_decode_batch (iters and stage may be NULL): a composition of the host paths of the two handles —
+ * stage 0's pipelined decode over all frames, a host gather of the failed rows, stage 1's decode over them, a host scatter;
+ * nothing new runs on the device.  Same results and refusals as the device entry. */
+int acg_ldpc_cascade_decode_batch(acg_ldpc_cascade *c, const double *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
+                                  int32_t *iters, uint8_t *stage);
+int acg_ldpc_cascade_decode_batch_f32(acg_ldpc_cascade *c, const float *y, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
+                                      int32_t *iters, uint8_t *stage);
+/* of the most recent decode or Monte-Carlo call on this cascade: frames handed to the second stage, device ms of the first /
+ * second decoder's launches summed over the chunks (host entries: of the last launch of each).  Waits for the second stage's
+ * last launch, which the device entry leaves running; call it before the stage handles are launched on again.  Any pointer may
+ * be NULL. */
+int acg_ldpc_cascade_last_call(acg_ldpc_cascade *c, int64_t *second_frames, float *first_ms, float *second_ms);
+
 /* ---- Monte-Carlo loop (experiment.h) --------------------------------------------------- */
 
 typedef struct acg_ldpc_mc_cfg {
@@ -318,6 +373,25 @@ typedef struct acg_ldpc_mc_result {
 int acg_ldpc_mc_run(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res);
 /* merge_exp_results (experiment.h:70-78): a += b (used to combine per-GPU shards on the host) */
 void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b);
+
+/* acg_ldpc_mc_run through a cascade (two-stage decoding, above): both noise modes, codewords and first_frame as there, the
+ * counters the same for any chunking and sharding.  Every frame goes noise (AWGN kernel, or the host generator and a copy) ->
+ * the cascade's device path, chunk by chunk, with the classification kernel run on stage 0's outputs before the scatter (first)
+ * and on the merged outputs (total).  A first decoder with a fused Monte-Carlo kernel does not use it here: the second stage
+ * needs the symbols. */
+typedef struct acg_ldpc_cascade_result {
+    acg_ldpc_mc_result total;   /* the returned outputs classified as acg_ldpc_mc_run classifies; kernel_ms = both stages */
+    acg_ldpc_mc_result first;   /* seven counters = acg_ldpc_mc_run(stage 0, cfg); kernel_ms of its launches */
+    int64_t second_frames;      /* frames handed to stage 1 (ok = 0 after stage 0).  = first.total - first.correct - first.pseudo
+                                   whenever stage 0's flag is the zero syndrome: every BP engine, and a QP-ADMM guard decoder */
+    int64_t second_correct, second_pseudo, second_sum_iters;  /* of those frames: total.correct = first.correct + second_correct,
+                                                                 total.pseudo = first.pseudo + second_pseudo */
+    double  second_kernel_ms;
+} acg_ldpc_cascade_result;
+/* Errors (non-zero, message, nothing launched): null c, cfg or res; a bad cfg as for acg_ldpc_mc_run. */
+int acg_ldpc_cascade_mc_run(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, acg_ldpc_cascade_result *res);
+/* shards: everything adds */
+void acg_ldpc_cascade_merge(acg_ldpc_cascade_result *a, const acg_ldpc_cascade_result *b);
 
 /* ---- Monte-Carlo detail run: bit errors and a log of the frames that are not correct ------- */
 

@@ -11,6 +11,11 @@
 //            [--events-out FILE --events-cap N]   log the N lowest frames that are not correct, one line per event
 //                         (a frame index replays the frame: device noise is keyed on it)
 //            Without these three the driver runs acg_ldpc_mc_run and its output is what it always was.
+//            [--cascade A,B]   A, B of bp | admm | minsum, the decoders the flags above configure: also evaluate the two-stage
+//                         decoder "A then B on the frames A fails" (acg_ldpc_cascade_mc_run) on one device — one more block on
+//                         stdout and one more row per SNR in report.csv, Method = the cascade's name (e.g. MS+BP), behind
+//                         the rows of the single decoders; stderr adds the share of frames the second stage saw.  The
+//                         detail files do not cover it.  Without the flag nothing changes.
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -35,6 +40,17 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "acg_eval: --events-out FILE and --events-cap N (N > 0) go together\n");
         return 2;
     }
+    std::string cascade_first, cascade_second;
+    if (a.has("--cascade")) {
+        const std::string spec = a.get("--cascade", "");
+        const size_t comma = spec.find(',');
+        auto known = [](const std::string &w) { return w == "bp" || w == "admm" || w == "minsum"; };
+        if (comma != std::string::npos) cascade_first = spec.substr(0, comma), cascade_second = spec.substr(comma + 1);
+        if (!known(cascade_first) || !known(cascade_second)) {
+            std::fprintf(stderr, "acg_eval: --cascade A,B with A and B of bp, admm, minsum\n");
+            return 2;
+        }
+    }
     acg_ldpc_code *code = nullptr;
     if (acg_ldpc_code_load_txt(hpath, &code)) drv::die("read_pcm");
     int m, n, E;
@@ -50,34 +66,50 @@ int main(int argc, char **argv) {
     const int gpus = (int) a.integer("--gpus", 1);
     const int ndev = (int) a.integer("--device-count", 1 << 30);  // tests: fold N handles onto fewer devices
     std::vector<drv::MultiGpu> decs;
+    // the three decoders the flags configure, by the names --cascade uses
+    auto params_of = [&](const std::string &which, acg_ldpc_params &p) {
+        acg_ldpc_params_default(&p);
+        if (which == "bp") {
+            p.algo = ACG_LDPC_BP_SUMPRODUCT;
+            p.max_iter = (int) a.integer("--bp-iters", 100);  // main.cpp:29
+        } else if (which == "admm") {
+            p.algo = ACG_LDPC_QPADMM;
+            p.alpha = a.num("--alpha", 1.2);  // main.cpp:31
+            p.mu = a.num("--mu", 0.55);
+            p.max_iter = (int) a.integer("--admm-iters", 10000);
+            p.eps_stop = a.num("--eps", 1e-5);
+        } else if (which == "minsum") {  // build-added variant (north_star); not one of main.cpp's decoders
+            p.algo = ACG_LDPC_BP_MINSUM;
+            p.max_iter = (int) a.integer("--minsum-iters", 50);
+            p.ms_scale = a.num("--ms-scale", 0.75);
+            if (a.has("--layered")) p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
+            if (a.has("--ms-f16")) p.precision = ACG_LDPC_PREC_F16;
+        } else
+            return false;
+        return true;
+    };
     acg_ldpc_params p;
     if (!a.has("--no-bp")) {
-        acg_ldpc_params_default(&p);
-        p.algo = ACG_LDPC_BP_SUMPRODUCT;
-        p.max_iter = (int) a.integer("--bp-iters", 100);  // main.cpp:29
+        params_of("bp", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
     if (!a.has("--no-admm")) {
-        acg_ldpc_params_default(&p);
-        p.algo = ACG_LDPC_QPADMM;
-        p.alpha = a.num("--alpha", 1.2);  // main.cpp:31
-        p.mu = a.num("--mu", 0.55);
-        p.max_iter = (int) a.integer("--admm-iters", 10000);
-        p.eps_stop = a.num("--eps", 1e-5);
+        params_of("admm", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
-
-    if (a.has("--minsum-iters")) {  // build-added variant (north_star); not one of main.cpp's decoders
-        acg_ldpc_params_default(&p);
-        p.algo = ACG_LDPC_BP_MINSUM;
-        p.max_iter = (int) a.integer("--minsum-iters", 50);
-        p.ms_scale = a.num("--ms-scale", 0.75);
-        if (a.has("--layered")) p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
-        if (a.has("--ms-f16")) p.precision = ACG_LDPC_PREC_F16;
+    if (a.has("--minsum-iters")) {
+        params_of("minsum", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
+    }
+    acg_ldpc_cascade *cascade = nullptr;
+    if (a.has("--cascade")) {
+        acg_ldpc_params p1, p2;
+        params_of(cascade_first, p1);
+        params_of(cascade_second, p2);
+        if (acg_ldpc_cascade_create(code, &p1, nullptr, &p2, nullptr, &cascade)) drv::die("acg_ldpc_cascade_create");
     }
 
     std::cout.precision(5);
@@ -118,6 +150,32 @@ int main(int argc, char **argv) {
                   << r.mean_hamming_wrong() << std::endl;
         }
         std::cerr << std::string(30, '_') << std::endl;
+    }
+    if (cascade) {
+        std::cout << "Algo: " << acg_ldpc_cascade_name(cascade) << std::endl;
+        for (double snr : snrs) {
+            acg_ldpc_mc_cfg cfg;
+            std::memset(&cfg, 0, sizeof cfg);
+            cfg.frames = tests;
+            cfg.snr = snr;
+            cfg.seed = (uint64_t) a.integer("--seed", 1);
+            cfg.noise = noise;
+            cfg.codewords = cws.empty() ? nullptr : cws.data();
+            cfg.n_codewords = cws.empty() ? 0 : (int64_t) (cws.size() / (size_t) n);
+            acg_ldpc_cascade_result cr;
+            if (acg_ldpc_cascade_mc_run(cascade, &cfg, &cr)) drv::die("acg_ldpc_cascade_mc_run");
+            drv::McOut r, r1;
+            r.r = cr.total;
+            r1.r = cr.first;
+            std::cout << "\tSNR: " << snr << ", FER: " << r.fer() << ", (time=" << r.avg_time() << "s)" << std::endl;
+            std::cerr << "\t\tAverage hamming distance: " << r.mean_hamming() << std::endl;
+            std::cerr << "\t\tFirst stage alone: FER " << r1.fer() << "; second stage: " << cr.second_frames << " of " << cr.total.total
+                      << " frames, " << cr.second_correct << " decoded correctly" << std::endl;
+            fdata << acg_ldpc_cascade_name(cascade) << "," << snr << "," << std::sqrt(acg_ldpc_llr_variance(snr)) << "," << r.fer() << ","
+                  << r.avg_time() << "," << r.mean_hamming() << "," << r.mean_hamming_ok() << "," << r.mean_hamming_wrong() << std::endl;
+        }
+        std::cerr << std::string(30, '_') << std::endl;
+        acg_ldpc_cascade_destroy(cascade);
     }
     for (auto &d : decs) d.destroy();
     acg_ldpc_code_destroy(code);
