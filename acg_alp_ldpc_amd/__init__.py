@@ -9,7 +9,7 @@ from ._lib import (ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED, EVENT_NO_WORD, EV
 from .channel import gen_random_codewords, llr, llr_variance, transmit_frames  # noqa: F401
 from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
-from .decoder import (BeliefPropagationDecoder, CascadeDecoder, Decoder, MinSumDecoder, QPADMMDecoder, QuantConfig,  # noqa: F401
+from .decoder import (BeliefPropagationDecoder, CascadeDecoder, Decoder, MinSumDecoder, OSDDecoder, QPADMMDecoder, QuantConfig,  # noqa: F401
                       QuantizedMinSumDecoder)
 from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_cascade_results, merge_exp_details,  # noqa: F401
                          merge_exp_results, quant_structs, run_experiment, run_experiment_cascade, run_experiment_codes,

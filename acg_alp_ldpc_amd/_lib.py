@@ -60,7 +60,7 @@ class McEvent(C.Structure):
                 ("bit_errors", C.c_int32), ("syndrome_weight", C.c_int32), ("reserved", C.c_int32)]
 
 
-ALGO_BP, ALGO_MINSUM, ALGO_QPADMM = 0, 1, 2
+ALGO_BP, ALGO_MINSUM, ALGO_QPADMM, ALGO_OSD = 0, 1, 2, 3
 EVENT_PSEUDO, EVENT_NO_WORD, EVENT_NONCODEWORD = 1, 2, 3
 PREC_DEFAULT, PREC_F64, PREC_F32, PREC_F16 = 0, 1, 2, 3
 NOISE_DEVICE_PHILOX, NOISE_HOST_MT19937 = 0, 1
@@ -91,6 +91,9 @@ SYMBOLS = {
     "acg_ldpc_quantize_dev": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp]),
     "acg_ldpc_decode_batch_q_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "acg_ldpc_decode_batch_q": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_osd_decode_batch_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_osd_decode_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "acg_ldpc_debug_osd_soft": (C.c_int, [_vp, _i32, _i64, _vp]),
     "acg_ldpc_decoder_destroy": (None, [_vp]),
     "acg_ldpc_decoder_name": (C.c_char_p, [_vp]),
     "acg_ldpc_decode_batch": (C.c_int, [_vp, _vp, _i64, _f64, _vp, _vp, _vp]),

@@ -470,6 +470,70 @@ static int decoder_setup_layered_wg(acg_ldpc_decoder *d, const acg_ldpc_decoder:
     return 0;
 }
 
+// what algo = ACG_LDPC_OSD requires of the params (include/acg_ldpc.h, "OSD"); host only
+static int osd_params_check(const acg_ldpc_params &p, const Code &c) {
+    const char *why = nullptr;
+    if (p.max_iter != 0 && p.max_iter != 1) why = "max_iter is the order and must be 0 or 1";
+    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (every value is an integer)";
+    else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_FUSED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_FUSED (the state lives in LDS)";
+    else if (p.schedule != ACG_LDPC_SCHEDULE_FLOODING) why = "schedule must be ACG_LDPC_SCHEDULE_FLOODING (there is no schedule)";
+    else if (p.lanes_per_frame != 0 && p.lanes_per_frame != 64 && p.lanes_per_frame != 128 && p.lanes_per_frame != 256)
+        why = "lanes_per_frame must be 0, 64, 128 or 256";
+    else if (c.n > 65535) why = "n must be <= 65535 (the sort key holds the variable in 16 bits)";
+    if (why) {
+        set_error(std::string("OSD: ") + why);
+        return 3;
+    }
+    return 0;
+}
+
+// algo = ACG_LDPC_OSD: one workgroup per frame, the frame's working matrix in LDS (osd.hip)
+static int decoder_setup_osd(acg_ldpc_decoder *d) {
+    const Code &c = d->c;
+    int L = d->p.lanes_per_frame;
+    if (L == 0) {
+        L = 64;
+        while (L < 256 && 2 * L < c.n) L <<= 1;
+    }
+    OsdArgs &o = d->oargs;
+    o.n = c.n;
+    o.m = c.m;
+    o.nwords = (c.n + 31) / 32;
+    o.wm = (c.m + 31) / 32;
+    o.stride = o.wm | 1;
+    o.order = d->p.max_iter;
+    o.s_in = nullptr;
+    const size_t lds = osd_lds_bytes(c.n, c.m);
+    const void *kp = osd_kernel_ptr(L);
+    if (!kp) {
+        set_error("OSD: no kernel instance for this lanes_per_frame");
+        return 3;
+    }
+    hipFuncAttributes fa{};
+    HIP_OK(hipFuncGetAttributes(&fa, kp));
+    if (lds + fa.sharedSizeBytes > 160 * 1024) {
+        set_error("OSD: a frame (working matrix of " + std::to_string(c.n) + " columns x " + std::to_string(o.wm) + " words, keys, pivots, word = " +
+                  std::to_string(lds) + " bytes) does not fit in LDS");
+        return 3;
+    }
+    std::vector<uint32_t> cols;
+    o.rank = code_osd_table(c, o.stride, cols);
+    d->osd_cols = upload(cols);
+    if (!d->osd_cols.p) return 10;
+    o.cols = d->osd_cols.as<const uint32_t>();
+    d->osd = true;
+    d->L = L;
+    d->f64 = 0;
+    d->block = L;
+    d->frames_per_block = 1;
+    d->lds_block = lds;
+    if (int rc = bind_kernel(d, 0, kp)) return rc;
+    d->kernel[1] = nullptr;
+    d->grid_cap[1] = d->grid_cap[0];
+    d->tab.lds_bytes_per_frame = (int32_t) lds;
+    return 0;
+}
+
 // acg_ldpc_quant -> what the kernel reads
 QuantArgs acg::quant_args(const acg_ldpc_quant &q) {
     QuantArgs a{};
@@ -880,6 +944,14 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
             return 3;
         }
     }
+    if (!quant && params->algo == ACG_LDPC_OSD) {
+        if (int rc = osd_params_check(*params, code->c)) return rc;
+        if (osd_lds_bytes(code->c.n, code->c.m) > 160 * 1024) {
+            set_error("OSD: a frame (working matrix of " + std::to_string(code->c.n) + " columns x " + std::to_string((code->c.m + 31) / 32) +
+                      " words, keys, pivots, word) does not fit in LDS");
+            return 3;
+        }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available: libacg_ldpc_hip has no CPU fallback");
@@ -928,6 +1000,9 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
         } else if (params->algo == ACG_LDPC_BP_SUMPRODUCT || params->algo == ACG_LDPC_BP_MINSUM) {
             d->name = params->algo == ACG_LDPC_BP_SUMPRODUCT ? "BP" : "MS";  // bp.h:218
             rc = decoder_setup_bp(d);
+        } else if (params->algo == ACG_LDPC_OSD) {
+            d->name = "OSD";
+            rc = decoder_setup_osd(d);
         } else {
             set_error("unknown algo");
             rc = 1;
@@ -1008,7 +1083,11 @@ static std::string describe(const acg_ldpc_decoder *d) {
     const char *algo = d->p.algo == ACG_LDPC_QPADMM ? "qpadmm" : (d->p.algo == ACG_LDPC_BP_MINSUM ? "minsum" : "sum-product");
     int slabs = 0, f32 = 0;
     int64_t slab = 0;
-    if (d->admm && admm_device_streamed(d->admm.get(), &slabs, &slab, &f32)) {
+    if (d->osd) {
+        snprintf(b, sizeof b, "osd engine=fused kernel=osd_kernel lanes_per_frame=%d block=%d frames_per_block=1 order=%d rank=%d lds_block=%zu "
+                               "grid_cap=%d workgroups_per_cu=%d",
+                 d->L, d->block, d->oargs.order, d->oargs.rank, d->lds_block, d->grid_cap[0], d->grid_cap[0] / std::max(d->cu_count, 1));
+    } else if (d->admm && admm_device_streamed(d->admm.get(), &slabs, &slab, &f32)) {
         snprintf(b, sizeof b, "%s engine=streamed kernel=admm_streamed_kernel<%s> f64=%d slab_bytes=%lld slabs=%d workspace_bytes=%lld "
                                "workspace=hipMalloc mc_grid=per-point",
                  algo, f32 ? "float" : "double", f32 ? 0 : 1, (long long) slab, slabs, (long long) slab * slabs);

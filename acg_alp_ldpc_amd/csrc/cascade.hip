@@ -1,5 +1,6 @@
 // C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 5: two-stage decoding.  A cascade owns two decoder handles for one
-// code; a frame the first gives up on (ok = 0) is decoded again by the second, from the same symbols.  The engines are the
+// code; a frame the first gives up on (ok = 0) is decoded again by the second, from the same symbols — or, where the first is
+// a quantized handle and the second OSD, from the first's posteriors (post_handover).  The engines are the
 // handles' own (launch_decode): what is new is the hand-over, which stays on the device — select, gather, scatter
 // (cascade_kernels.hip) — with one host wait per chunk, for the number of failed frames.  The Monte-Carlo run is in mc.hip.
 #include <algorithm>
@@ -32,6 +33,11 @@ int acg::cascade_ensure(acg_ldpc_cascade *c, int64_t frames, size_t row_bytes) {
     if (int rc = c->c_bits.reserve(f * nwords * sizeof(uint32_t))) return rc;
     if (int rc = c->c_ok.reserve(f)) return rc;
     if (int rc = c->c_iters.reserve(f * sizeof(int32_t))) return rc;
+    if (c->post_handover) {
+        const size_t vals = f * (size_t) c->stage[0]->c.n * sizeof(int16_t);
+        if (int rc = c->q_c.reserve(vals)) return rc;
+        if (int rc = c->q_post.reserve(vals)) return rc;
+    }
     c->cap_frames = (int64_t) f;
     c->cap_row = row;
     return 0;
@@ -68,7 +74,16 @@ int acg::cascade_chunk_dev(acg_ldpc_cascade *c, const void *y, int y_is_f64, int
     a.out_bits = bits;
     a.out_ok = ok;
     a.out_iters = iters;
-    if (int rc = launch_decode(d0, a, s)) return rc;
+    if (c->post_handover) {
+        // stage 0 through its quantiser and its integer entrance — equal to its symbol entrance (include/acg_ldpc.h) — so that
+        // its posteriors stand in q_post
+        HIP_OK(quantize_debug_launch(decode_args(y, y_is_f64, fc * n, snr), d0->qargs, fc * n, c->q_c.as<int16_t>(), s));
+        a.y = nullptr;
+        const QuantIo io{c->q_c.as<int16_t>(), c->q_post.as<int16_t>()};
+        if (int rc = launch_decode(d0, a, s, &io)) return rc;
+    } else if (int rc = launch_decode(d0, a, s)) {
+        return rc;
+    }
     const int slot0 = d0->last_slot;
     if (hooks && hooks->first_done)
         if (int rc = hooks->first_done()) return rc;
@@ -88,12 +103,15 @@ int acg::cascade_chunk_dev(acg_ldpc_cascade *c, const void *y, int y_is_f64, int
     c->last_second += K;
     if (K == 0) return 0;
     // 3. gather, stage 1 over the compact batch, scatter
-    HIP_OK(cascade_gather_launch(y, y_is_f64 ? 8 : 4, n, idx, (int32_t) K, c->c_y.p, s));
-    DecodeArgs b = decode_args(c->c_y.p, y_is_f64, K, snr);
+    // (posterior hand-over: the failed frames' int16 posterior rows instead of their symbol rows, into OSD's integer entrance)
+    if (c->post_handover) HIP_OK(cascade_gather_launch(c->q_post.p, 2, n, idx, (int32_t) K, c->c_y.p, s));
+    else HIP_OK(cascade_gather_launch(y, y_is_f64 ? 8 : 4, n, idx, (int32_t) K, c->c_y.p, s));
+    DecodeArgs b = decode_args(c->post_handover ? nullptr : c->c_y.p, y_is_f64, K, snr);
     b.out_bits = c->c_bits.as<uint32_t>();
     b.out_ok = c->c_ok.as<uint8_t>();
     b.out_iters = c->c_iters.as<int32_t>();
-    if (int rc = launch_decode(d1, b, s)) return rc;
+    const QuantIo io1{c->c_y.as<int16_t>(), nullptr};
+    if (int rc = launch_decode(d1, b, s, c->post_handover ? &io1 : nullptr)) return rc;
     c->pending_slot = d1->last_slot;
     if (hooks && hooks->second_done)
         if (int rc = hooks->second_done(K)) return rc;
@@ -140,6 +158,7 @@ static int cascade_create_impl(const acg_ldpc_code *code, const acg_ldpc_params 
         }
         c->stage[k].reset(d);
     }
+    c->post_handover = q[0] && !q[1] && c->stage[1]->osd;
     c->device = c->stage[0]->device;
     c->name = c->stage[0]->name + "+" + c->stage[1]->name;
     HIP_OK(hipSetDevice(c->device));
@@ -212,6 +231,37 @@ static int cascade_decode_host_impl(acg_ldpc_cascade *c, const void *y, int elem
     std::lock_guard<std::recursive_mutex> lk0(d0->mu);
     std::lock_guard<std::recursive_mutex> lk1(d1->mu);
     const size_t n = (size_t) d0->c.n, row = n * elem;
+    if (c->post_handover) {
+        // the posteriors exist on the device only: the chunks of the device path, symbols copied in and outputs copied out
+        const int nwords = (int) (n + 31) / 32;
+        const int64_t chunk = cascade_chunk_frames(frames, row);
+        cascade_begin(c, chunk);
+        if (frames == 0) return 0;
+        HIP_OK(hipSetDevice(c->device));
+        if (int rc = cascade_ensure(c, chunk, row)) return rc;
+        DeviceBuf dy, dbits, dok, dit, dst;
+        if (int rc = dy.reserve((size_t) chunk * row)) return rc;
+        if (int rc = dbits.reserve((size_t) chunk * nwords * sizeof(uint32_t))) return rc;
+        if (int rc = dok.reserve((size_t) chunk)) return rc;
+        if (int rc = dit.reserve((size_t) chunk * sizeof(int32_t))) return rc;
+        if (int rc = dst.reserve((size_t) chunk)) return rc;
+        std::vector<uint32_t> hbits((size_t) chunk * nwords);
+        hipStream_t s = d0->stream;
+        for (int64_t f0 = 0; f0 < frames; f0 += chunk) {
+            const int64_t fc = std::min(chunk, frames - f0);
+            HIP_OK(hipMemcpyAsync(dy.p, (const unsigned char *) y + (size_t) f0 * row, (size_t) fc * row, hipMemcpyHostToDevice, s));
+            if (int rc = cascade_chunk_dev(c, dy.p, elem == 8 ? 1 : 0, fc, snr, dbits.as<uint32_t>(), dok.as<uint8_t>(), dit.as<int32_t>(), dst.as<uint8_t>(), s))
+                return rc;
+            HIP_OK(hipStreamSynchronize(s));
+            HIP_OK(hipMemcpy(hbits.data(), dbits.p, (size_t) fc * nwords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(ok + f0, dok.p, (size_t) fc, hipMemcpyDeviceToHost));
+            if (iters) HIP_OK(hipMemcpy(iters + f0, dit.p, (size_t) fc * sizeof(int32_t), hipMemcpyDeviceToHost));
+            if (stage) HIP_OK(hipMemcpy(stage + f0, dst.p, (size_t) fc, hipMemcpyDeviceToHost));
+            for (int64_t f = 0; f < fc; f++)
+                for (size_t v = 0; v < n; v++) bits[(size_t) (f0 + f) * n + v] = (hbits[(size_t) f * nwords + (v >> 5)] >> (v & 31)) & 1u;
+        }
+        return cascade_settle(c);
+    }
     cascade_begin(c, host_chunk_frames(std::max<int64_t>(frames, 1), row));
     if (frames == 0) return 0;
     auto decode = [&](acg_ldpc_decoder *d, const void *sym, int64_t f, uint8_t *b, uint8_t *o, int32_t *it) {
@@ -282,7 +332,7 @@ int32_t acg_ldpc_cascade_describe(const acg_ldpc_cascade *c, char *buf, int32_t 
         }
         // (the two figures of the last call are read without the mutex: describe is a diagnostic, as the decoder's is)
         t += " | chunk=" + std::to_string(c->last_chunk ? c->last_chunk : cascade_chunk_frames(1 << 16, (size_t) c->stage[0]->c.n * 4)) +
-             " last_second_frames=" + std::to_string(c->last_second);
+             " last_second_frames=" + std::to_string(c->last_second) + (c->post_handover ? " handover=posteriors" : " handover=symbols");
         return (int) copy_text(t, buf, cap);
     });
 }

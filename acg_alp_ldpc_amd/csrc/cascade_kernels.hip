@@ -93,6 +93,8 @@ hipError_t cascade_gather_launch(const void *y, int elem, int32_t n, const int32
     // else one element per access (the element's own alignment is all an odd n leaves)
     if (((uintptr_t) y | (uintptr_t) out | row) % 16 == 0)
         hipLaunchKernelGGL(cascade_gather_kernel<uint4>, dim3(grid), dim3(256), 0, s, (const uint4 *) y, (uint4 *) out, idx, K, (int32_t) (row / 16));
+    else if (elem == 2)
+        hipLaunchKernelGGL(cascade_gather_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, (const uint16_t *) y, (uint16_t *) out, idx, K, n);
     else if (elem == 8)
         hipLaunchKernelGGL(cascade_gather_kernel<uint64_t>, dim3(grid), dim3(256), 0, s, (const uint64_t *) y, (uint64_t *) out, idx, K, n);
     else

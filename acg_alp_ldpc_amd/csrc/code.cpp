@@ -182,6 +182,34 @@ bool code_generator(const Code &c, uint8_t *G) {
 }
 
 // ---------------------------------------------------------------- BP LDS layout
+int code_osd_table(const Code &c, int stride, std::vector<uint32_t> &cols) {
+    cols.assign((size_t) c.n * stride, 0u);
+    for (int r = 0; r < c.m; r++)
+        for (int e = c.row_ptr[r]; e < c.row_ptr[r + 1]; e++) cols[(size_t) c.edge_var[e] * stride + (r >> 5)] |= 1u << (r & 31);
+    // the rank: eliminate on a copy, column by column (which columns come first does not change it)
+    std::vector<uint32_t> w = cols;
+    const int wm = (c.m + 31) / 32;
+    std::vector<uint32_t> used((size_t) wm, 0u);
+    int rank = 0;
+    for (int v = 0; v < c.n && rank < c.m; v++) {
+        const uint32_t *col = &w[(size_t) v * stride];
+        int p = -1;
+        for (int k = 0; k < wm && p < 0; k++) {
+            const uint32_t x = col[k] & ~used[k];
+            if (x) p = 32 * k + __builtin_ctz(x);
+        }
+        if (p < 0) continue;
+        used[p >> 5] |= 1u << (p & 31);
+        rank++;
+        for (int j = v + 1; j < c.n; j++) {
+            uint32_t *cj = &w[(size_t) j * stride];
+            if (cj[p >> 5] >> (p & 31) & 1u)
+                for (int k = 0; k < wm; k++) cj[k] ^= k == (p >> 5) ? col[k] & ~(1u << (p & 31)) : col[k];
+        }
+    }
+    return rank;
+}
+
 bool bp_layout_build(const Code &c, int L, BpLayout &o, int max_apass) {
     o = BpLayout();
     o.L = L;

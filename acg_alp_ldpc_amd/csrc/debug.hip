@@ -251,6 +251,32 @@ int acg_ldpc_debug_quantize(const void *y_host, int32_t y_is_f64, int64_t count,
     return guarded([&] { return acg_ldpc_debug_quantize_impl(y_host, y_is_f64, count, snr, q, out_host); });
 }
 
+static int acg_ldpc_debug_osd_soft_impl(const void *y_host, int32_t y_is_f64, int64_t count, int16_t *out_host) {
+    if (!y_host || !out_host || count < 0) {
+        set_error("bad argument");
+        return 1;
+    }
+    if (count == 0) return 0;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device available: libacg_ldpc_hip has no CPU fallback");
+        return 20;
+    }
+    const size_t es = y_is_f64 ? 8 : 4;
+    DeviceBuf dy, dout;
+    if (int rc = dy.reserve(es * (size_t) count)) return rc;
+    if (int rc = dout.reserve(sizeof(int16_t) * (size_t) count)) return rc;
+    HIP_OK(hipMemcpy(dy.p, y_host, es * (size_t) count, hipMemcpyHostToDevice));
+    HIP_OK(osd_soft_debug_launch(dy.p, y_is_f64 ? 1 : 0, count, dout.as<int16_t>(), nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out_host, dout.p, sizeof(int16_t) * (size_t) count, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int acg_ldpc_debug_osd_soft(const void *y_host, int32_t y_is_f64, int64_t count, int16_t *out_host) {
+    return guarded([&] { return acg_ldpc_debug_osd_soft_impl(y_host, y_is_f64, count, out_host); });
+}
+
 static int acg_ldpc_debug_phi_sat_impl(const void *x_host, void *out_host, int32_t n) {
     DeviceBuf dx, dout;
     if (int rc = dx.reserve(4 * (size_t) n)) return rc;

@@ -97,7 +97,7 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
 int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid) {
-    if (qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qio)) {
+    if (qio && d->osd ? qio->post_out != nullptr : qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qio)) {
         set_error("internal: channel values handed to a decoder that is not quantized");
         return 11;
     }
@@ -156,6 +156,14 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
         } else {
             HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, (uint32_t *) d->sws.va, grid, W * 64, s));
         }
+    } else if (d->osd) {
+        if (a.mc) {
+            set_error("internal: the OSD engine has no in-kernel generator");
+            return 11;
+        }
+        OsdArgs o = d->oargs;
+        o.s_in = qio ? qio->c_in : nullptr;
+        HIP_OK(osd_launch(d->kernel[0], o, a, (int) std::min<int64_t>(a.frames, d->grid_cap[0]), d->block, d->lds_block, s));
     } else if (d->layered_wg != acg_ldpc_decoder::LayeredWg::none) {
         if (a.mc) {
             set_error("internal: the workgroup-per-frame layered engine has no in-kernel generator");
@@ -355,7 +363,7 @@ static void unpack_bits(const uint32_t *words, int nwords, int n, int64_t frames
 // stream -> host threads expand the words into one byte per bit.  Chunk c + 1 is packed and chunk c - 1 unpacked while
 // the GPU works on chunk c.  elem = 8 (double symbols: exact LLRs, channel.h:14-16) or 4 (float symbols); elem = 2: int16
 // channel values of a quantized handle (acg_ldpc_decode_batch_q; snr unused), whose int16 posteriors come back behind the
-// flags of the chunk where post is given.
+// flags of the chunk where post is given, or int16 soft values of an OSD handle (acg_ldpc_osd_decode_batch).
 static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
                              int32_t *iters, int16_t *post = nullptr) {
     const int n = d->c.n, nwords = (n + 31) / 32;
@@ -538,6 +546,59 @@ int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *d, const int16_t *c_dev, int64
 int acg_ldpc_decode_batch_q(acg_ldpc_decoder *d, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
                             int16_t *post) {
     return guarded([&] { return decode_batch_q_impl(d, c, frames, bits, ok, iters, post); });
+}
+
+// ---- the integer entrance of the OSD engine: soft values in ----
+
+static int osd_handle(const acg_ldpc_decoder *d) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    if (!d->osd) {
+        set_error("soft values need a decoder with algo = ACG_LDPC_OSD");
+        return 3;
+    }
+    return 0;
+}
+
+static int osd_decode_batch_dev_impl(acg_ldpc_decoder *d, const int16_t *s_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                     int32_t *iters_dev, void *stream) {
+    if (int rc = osd_handle(d)) return rc;
+    if (frames < 0 || (frames > 0 && !s_dev)) {
+        set_error("bad frames / s");
+        return 1;
+    }
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    DecodeArgs a = decode_args(nullptr, 0, frames, 0.0);   // (no symbols, no channel: the kernel reads neither)
+    a.out_bits = bits_dev;
+    a.out_ok = ok_dev;
+    a.out_iters = iters_dev;
+    const QuantIo io{s_dev, nullptr};
+    return launch_decode(d, a, stream ? (hipStream_t) stream : d->stream, &io);
+}
+
+static int osd_decode_batch_impl(acg_ldpc_decoder *d, const int16_t *s, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters) {
+    if (int rc = osd_handle(d)) return rc;
+    if (frames < 0 || (frames > 0 && (!s || !bits || !ok))) {
+        set_error("null buffer");
+        return 1;
+    }
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    return decode_batch_host(d, s, 2, frames, 0.0, bits, ok, iters);
+}
+
+int acg_ldpc_osd_decode_batch_dev(acg_ldpc_decoder *d, const int16_t *s_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                  int32_t *iters_dev, void *stream) {
+    return guarded([&] { return osd_decode_batch_dev_impl(d, s_dev, frames, bits_dev, ok_dev, iters_dev, stream); });
+}
+
+int acg_ldpc_osd_decode_batch(acg_ldpc_decoder *d, const int16_t *s, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters) {
+    return guarded([&] { return osd_decode_batch_impl(d, s, frames, bits, ok, iters); });
 }
 
 int acg_ldpc_decoder_sync(acg_ldpc_decoder *d) {

@@ -175,6 +175,11 @@ struct acg_ldpc_decoder {
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
+    // ordered-statistics decoding (osd.hip; algo = ACG_LDPC_OSD): the packed column table, and what the kernel reads.  One kernel
+    // for both entrances (OsdArgs::s_in set per launch); decode only: Monte-Carlo runs take the unfused route.
+    bool osd = false;
+    acg::OsdArgs oargs{};
+    acg::DeviceBuf osd_cols;
     // streamed BP engine
     bool streamed = false;
     acg::StreamTables stab{};
@@ -245,6 +250,10 @@ struct acg_ldpc_cascade {
     int64_t cap_frames = 0;
     size_t cap_row = 0;  // bytes of a symbol row the compact buffer was sized for
     acg::DeviceBuf idx, count, c_y, c_bits, c_ok, c_iters;
+    // posterior hand-over (stage 0 quantized, stage 1 OSD): the chunk's channel values and posteriors; c_y holds the failed
+    // frames' posterior rows
+    bool post_handover = false;
+    acg::DeviceBuf q_c, q_post;
     acg::PinnedBuf count_h;
     // recorded behind every chunk that handed frames on: the next chunk waits for it on ITS stream before it reuses the buffers
     hipEvent_t tail_ev = nullptr;
@@ -258,7 +267,7 @@ struct acg_ldpc_cascade {
     // Monte-Carlo run: symbols and outputs of a chunk; counters rows `first`, `total`, then the second stage's sweeps
     acg::DeviceBuf mc_y, mc_bits, mc_ok, mc_iters, mc_counters;
     void release() {
-        idx.reset(), count.reset(), c_y.reset(), c_bits.reset(), c_ok.reset(), c_iters.reset(), count_h.reset();
+        idx.reset(), count.reset(), c_y.reset(), c_bits.reset(), c_ok.reset(), c_iters.reset(), count_h.reset(), q_c.reset(), q_post.reset();
         cap_frames = 0, cap_row = 0;
     }
 };
@@ -274,7 +283,8 @@ QuantArgs quant_args(const acg_ldpc_quant &q);
 // ---- decode.hip ----
 double channel_sigma(double snr);
 void fill_channel(DecodeArgs &a, double snr);
-// qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for
+// qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for; of an
+// OSD handle — soft values instead of a.y (post_out null)
 // qgrid != null: the grid form of a quantized handle — a.frames virtual frames, a quantiser per point instead of the handle's
 int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr, const QuantGridArgs *qgrid = nullptr);
 int ensure_staging(acg_ldpc_decoder *d, int64_t frames);

@@ -154,6 +154,16 @@ struct QuantIo {
     int16_t *post_out;
 };
 
+// Ordered-statistics decoding (osd.hip): what the kernel reads next to DecodeArgs
+struct OsdArgs {
+    const uint32_t *cols;   // [n][stride] H column-major, bit r % 32 of word r / 32 of column v = H[r][v]
+    const int16_t *s_in;    // frames * n soft values (the integer entrance); null: the symbol entrance quantises a.y
+    int32_t n, m, nwords;
+    int32_t wm, stride;     // words of a column = ceil(m / 32), and their distance = wm made odd
+    int32_t rank;           // rank of H over GF(2): the pivots of a frame
+    int32_t order;          // 0 or 1
+};
+
 // Streamed ("HBM") BP engine: plain CSR of the Tanner graph, read through scalar loads.
 struct StreamTables {
     const int32_t *row_ptr;   // [m+1] edges in check-major order (variables ascending)

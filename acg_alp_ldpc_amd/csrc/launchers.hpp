@@ -61,7 +61,7 @@ hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bit
 // ---- cascade_kernels.hip: the glue of a two-stage decode, per chunk of frames (an int32 count: at most 65536) ----
 // idx[0 .. *count) = the frames with ok == 0, ascending; stage (may be null) = 1 for every frame.  idx: `frames` entries
 hipError_t cascade_select_launch(const uint8_t *ok, int32_t frames, int32_t *idx, int32_t *count, uint8_t *stage, hipStream_t s);
-// row k of out = row idx[k] of y, rows of n symbols of elem = 4 or 8 bytes
+// row k of out = row idx[k] of y, rows of n symbols of elem = 4 or 8 bytes (2: the int16 posteriors of a quantized stage)
 hipError_t cascade_gather_launch(const void *y, int elem, int32_t n, const int32_t *idx, int32_t K, void *out, hipStream_t s);
 // rows idx[k] of bits / ok / iters (may be null) / stage (may be null, = 2) from row k of the compact outputs
 hipError_t cascade_scatter_launch(const uint32_t *cbits, const uint8_t *cok, const int32_t *citers, const int32_t *idx, int32_t K,
@@ -89,6 +89,13 @@ hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, c
                                 size_t lds, hipStream_t s, const QuantGridArgs *g = nullptr);
 // the kernel's quantiser on `count` symbols (a: y, y_is_f64 and the channel terms) -> count int16
 hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_t count, int16_t *out, hipStream_t s);
+
+// ---- osd.hip: ordered-statistics decoding, one workgroup of L = 64, 128 or 256 threads per frame ----
+const void *osd_kernel_ptr(int L);
+size_t osd_lds_bytes(int n, int m);   // dynamic LDS of a workgroup
+hipError_t osd_launch(const void *kernel, const OsdArgs &o, const DecodeArgs &a, int grid, int block, size_t lds, hipStream_t s);
+// the symbol entrance's quantiser on `count` symbols -> count int16
+hipError_t osd_soft_debug_launch(const void *y, int y_is_f64, int64_t count, int16_t *out, hipStream_t s);
 
 // ---- bp_streamed.hip ----
 const void *bp_streamed_ptr(int algo, int f64);

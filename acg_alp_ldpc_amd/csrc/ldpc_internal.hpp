@@ -90,6 +90,8 @@ bool code_read_txt(const char *path, std::vector<uint8_t> &H, int &m, int &n);
 bool code_write_txt(const Code &c, const char *path);
 bool code_generator(const Code &c, uint8_t *G);
 bool code_is_codeword(const Code &c, const uint8_t *bits);
+// Ordered-statistics decoding (osd.hip): H column-major in words of 32 rows, column v at cols[v * stride], and its GF(2) rank
+int code_osd_table(const Code &c, int stride, std::vector<uint32_t> &cols);
 bool bp_layout_build(const Code &c, int L, BpLayout &out, int max_apass = 0);
 int bp_default_lanes(const Code &c, bool f64);
 bool bp_layout_absorb(const Code &c, int L, BpLayout &lay);

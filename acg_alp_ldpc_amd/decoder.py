@@ -4,12 +4,13 @@
     QPADMMDecoder(alpha, mu, max_iter=2000, eps_stop=1e-5) algo/qp_admm.h:180-194
     MinSumDecoder(max_iter, scale)                         build-added, not in the reference
     QuantizedMinSumDecoder(max_iter, quant)                build-added, not in the reference: fixed-point layered min-sum
+    OSDDecoder(order=1)                                    build-added, not in the reference: ordered-statistics decoding
 
     decode(H, channel_word, snr) -> (codeword, ok)         same argument meaning as algo/algo.h:8:
         H: m x n 0/1 matrix (or a ParityCheckMatrix), channel_word: n raw channel symbols y
         (NOT LLRs), snr: Es/N0 in dB.  BP failure returns (empty array, False) like bp.h:198.
     decode_batch(H, Y, snr) -> (bits[F,n], ok[F], iters[F])
-    name() -> "BP" / "QP-ADMM" / "MS" / "QMS"
+    name() -> "BP" / "QP-ADMM" / "MS" / "QMS" / "OSD"
 
 Every call runs on the GPU through libacg_ldpc_hip.so; there is no CPU path.
 """
@@ -384,9 +385,59 @@ class QuantizedMinSumDecoder(Decoder):
             check(lib().acg_ldpc_quantize_dev(h, y_ptr, 1 if y_is_f64 else 0, int(count), float(snr), c_ptr, stream))
 
 
+class OSDDecoder(Decoder):
+    """Build-added ordered-statistics decoding of order 0 or 1 (algo = ACG_LDPC_OSD, include/acg_ldpc.h "OSD"; not in the
+    reference): one GF(2) elimination per frame on int16 soft values, always a codeword (ok = 1), iters = candidates flipped
+    (0 or 1).  Every value is an integer: tests/osd_ref.py restates it.  decode_batch quantises symbols (snr is ignored) and is
+    weak on channel reliabilities alone; the intended use is CascadeDecoder(QuantizedMinSumDecoder(...), OSDDecoder(...)), which
+    hands the first stage's posteriors over.  lanes_per_frame 0, 64, 128 or 256 = threads of the workgroup."""
+    _algo = _lib.ALGO_OSD
+    _name = "OSD"
+
+    def __init__(self, order=1, lanes_per_frame=0, **kw):
+        super().__init__(order, lanes_per_frame=lanes_per_frame, **kw)
+        self.order = int(order)
+
+    @staticmethod
+    def soft_values(Y):
+        """host symbols (float64, or float32) -> the int16 soft values the symbol entrance forms (acg_ldpc_debug_osd_soft)"""
+        f32 = isinstance(Y, np.ndarray) and Y.dtype == np.float32
+        Y = np.ascontiguousarray(Y, dtype=np.float32 if f32 else np.float64)
+        out = np.empty(Y.shape, dtype=np.int16)
+        check(lib().acg_ldpc_debug_osd_soft(Y.ctypes.data, 0 if f32 else 1, Y.size, out.ctypes.data))
+        return out
+
+    def decode_soft_batch(self, H, S):
+        """S: frames x n INTEGER soft values (sign = hard decision, magnitude = reliability; every value must fit int16)
+        -> (bits[F,n], ok[F], iters[F])"""
+        a = np.asarray(S)
+        if a.dtype.kind not in "iu":
+            raise TypeError("decode_soft_batch takes integer soft values, not %s" % a.dtype)
+        if a.dtype != np.int16:
+            if a.size and (a.min() < -32768 or a.max() > 32767):
+                raise ValueError("soft values must fit int16")
+            a = a.astype(np.int16)
+        a = np.ascontiguousarray(a)
+        with self._lease(H) as (h, code):
+            if a.ndim != 2 or a.shape[1] != code.n:
+                raise ValueError("S must be frames x n")
+            F = a.shape[0]
+            bits = np.empty((F, code.n), dtype=np.uint8)
+            ok = np.empty(F, dtype=np.uint8)
+            iters = np.empty(F, dtype=np.int32)
+            check(lib().acg_ldpc_osd_decode_batch(h, a.ctypes.data, F, bits.ctypes.data, ok.ctypes.data, iters.ctypes.data))
+        return bits, ok, iters
+
+    def decode_soft_batch_dev(self, H, s_ptr, frames, bits_ptr, ok_ptr, iters_ptr=None, stream=None):
+        """device pointers (ints): frames*n int16 soft values in; packed words, flags and iters out; asynchronous on `stream`"""
+        with self._lease(H) as (h, _):
+            check(lib().acg_ldpc_osd_decode_batch_dev(h, s_ptr, int(frames), bits_ptr, ok_ptr, iters_ptr, stream))
+
+
 class CascadeDecoder(_HandleCache):
     """Two-stage decoding (acg_ldpc_cascade_*): `first` decodes every frame, `second` only the frames `first` fails (ok = 0),
-    from the same symbols; the hand-over stays on the device.  first, second: Decoder objects as PARAMETER CARRIERS — their
+    from the same symbols — from the first's int16 posteriors where first is a QuantizedMinSumDecoder and second an OSDDecoder;
+    the hand-over stays on the device.  first, second: Decoder objects as PARAMETER CARRIERS — their
     _params() and, for a QuantizedMinSumDecoder, their quantiser.  Their own handles are not borrowed: a cascade handle owns
     its two decoders, and this object caches cascade handles per H with the discipline of every Decoder.
 

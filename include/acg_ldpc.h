@@ -38,7 +38,8 @@ typedef struct acg_ldpc_decoder acg_ldpc_decoder; /* device-resident graph, work
 enum {
     ACG_LDPC_BP_SUMPRODUCT = 0, /* algo/bp.h — the reference's BP (phi-domain sum-product) */
     ACG_LDPC_BP_MINSUM = 1,     /* build-added (north_star); NOT in the reference: parity unpinned */
-    ACG_LDPC_QPADMM = 2         /* algo/qp_admm.h */
+    ACG_LDPC_QPADMM = 2,        /* algo/qp_admm.h */
+    ACG_LDPC_OSD = 3            /* build-added: ordered-statistics decoding, order max_iter = 0 or 1 (see "OSD" below) */
 };
 
 /* arithmetic selector */
@@ -249,6 +250,41 @@ int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *dec, const int16_t *c_dev, int
 int acg_ldpc_decode_batch_q(acg_ldpc_decoder *dec, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
                             int16_t *post);
 
+/* ---- OSD: ordered-statistics decoding (Fossorier-Lin) of order 0 and 1 (build-added) ------ */
+
+/* acg_ldpc_decoder_create with algo = ACG_LDPC_OSD; max_iter is the ORDER, 0 or 1.  One GF(2) elimination per frame, no
+ * iterations, no transcendental, every value an integer; it always returns a codeword.  The algorithm:
+ *   A frame is n soft values s_v of type int16_t.  Hard decision z_v = (s_v < 0); reliability r_v = min(|s_v|, 32767) (so
+ *   -32768 counts as 32767).
+ *   Order        key_v = (r_v << 16) | v, ascending: least reliable first, ties broken by the lower v (hence n <= 65535).
+ *   Pivot set B  scan the variables in ascending key; v joins B iff column v of H is linearly independent over GF(2) of the
+ *                columns already in B.  |B| = rank(H).  The information set I is the complement of B: the n - rank most reliable
+ *                independent positions (the dual statement of the most-reliable-basis construction on a generator matrix).
+ *   Candidates   for T a subset of I, x_T is the unique codeword with x_v = z_v ^ [v in T] on I.
+ *   Metric       M(x) = sum_v r_v [x_v != z_v], an integer <= n * 32767.
+ *   Order 0      x_{}.   Order 1: the minimiser of M over x_{} and x_{j}, j in I; on a tie x_{} wins, then the lowest j.
+ *   Outputs      the word; ok = 1 for every frame; iters = |T| of the winner, 0 or 1.
+ * Symbol entrance (acg_ldpc_decode_batch, _f32, _dev, acg_ldpc_mc_run, _detail): y32 = the symbol as float (a double is rounded
+ * to nearest), s = clamp(truncf(y32 * 4096.0f), -32767, 32767), NaN -> 0, +-inf -> +-32767; snr is accepted and ignored.  So
+ * the symbol entrance equals acg_ldpc_debug_osd_soft followed by the integer entrance.  OSD on channel symbols alone is weak on
+ * the short codes here (H05: FER 0.63 at -2 dB); it is meant as the second stage of a cascade, on posteriors (below).
+ * Refused by acg_ldpc_decoder_create with a message naming the rule: max_iter other than 0 or 1; precision other than DEFAULT;
+ * engine other than AUTO or FUSED; schedule other than FLOODING; lanes_per_frame other than 0, 64, 128 or 256 (workgroup threads;
+ * 0 = the smallest that covers the n columns in at most two passes, else 256); n > 65535; a frame whose working matrix
+ * (n columns of ceil(m / 32) words), keys, permutation, pivot bookkeeping and word do not fit in the 160 KiB of LDS of a CU.
+ * alpha, mu, eps_stop, ms_scale and early_exit are ignored.  acg_ldpc_mc_run_grid and _quants refuse the handle. */
+
+/* the integer entrance: frames * n int16 soft values in (device; the same launch path as acg_ldpc_decode_batch_dev: work-counter
+ * ring, event pair, stream rules).  Null, negative and zero-frame rules are those of acg_ldpc_decode_batch_q*; both refuse a
+ * handle that is not OSD. */
+int acg_ldpc_osd_decode_batch_dev(acg_ldpc_decoder *dec, const int16_t *s_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                  int32_t *iters_dev, void *stream);
+/* host buffers, through the pipelined two-set staging path of acg_ldpc_decode_batch (2 bytes in per value) */
+int acg_ldpc_osd_decode_batch(acg_ldpc_decoder *dec, const int16_t *s, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters);
+/* the symbol entrance's quantiser on the device (test helper, the counterpart of acg_ldpc_debug_quantize): count symbols of
+ * float / double on the host -> count int16 */
+int acg_ldpc_debug_osd_soft(const void *y_host, int32_t y_is_f64, int64_t count, int16_t *out_host);
+
 /* replaces Decoder::decode(H, y, snr) (algo/algo.h:8) for `frames` frames at once.
  *   y      host, frames*n doubles, raw channel symbols (NOT LLRs; llr = 2y/sigma^2 is formed inside,
  *          channel.h:12-16, bp.h:66, qp_admm.h:27)
@@ -310,7 +346,15 @@ int32_t acg_ldpc_decoder_describe(const acg_ldpc_decoder *dec, char *buf, int32_
  * (work-counter ring, event pair and stream rules at the top of this header), cascade_scatter_kernel (words, flag, iterations,
  * stage = 2 back to their rows).  The tail of the last chunk is asynchronous, as acg_ldpc_decode_batch_dev is: outputs are
  * complete once the stream is idle.  The hand-over buffers belong to the cascade, so two calls on different streams are ordered
- * on the device, not concurrent.  A call holds the cascade's mutex, then stage 0's, then stage 1's. */
+ * on the device, not concurrent.  A call holds the cascade's mutex, then stage 0's, then stage 1's.
+ * Posterior hand-over.  When stage 0 is a handle of acg_ldpc_decoder_create_quantized and stage 1 is OSD, a failed frame's
+ * POSTERIORS go on, not its symbols: stage 0's result is unchanged, and for ok1 = 0 the cascade returns what
+ * acg_ldpc_osd_decode_batch_dev returns for the int16 posteriors that stage 0's integer entrance writes for the frame (those
+ * after max_iter iterations).  Per chunk: acg_ldpc_quantize_dev -> stage 0's integer entrance with post_dev (equal to its symbol
+ * entrance by the rule above) -> select -> cascade_gather_kernel on the posterior rows -> OSD's integer entrance over K frames ->
+ * scatter; still one host wait.  The host entries and acg_ldpc_cascade_mc_run take the same route (a host chunk is copied to the
+ * device) and return the same results.  Every other pairing with OSD as a stage hands over symbols as above; OSD on channel
+ * reliabilities is weak, see "OSD". */
 typedef struct acg_ldpc_cascade acg_ldpc_cascade;
 /* q_first / q_second: NULL = that stage comes from acg_ldpc_decoder_create, else from acg_ldpc_decoder_create_quantized with that
  * quantiser.  Refused (non-zero, message in acg_ldpc_last_error): null code, params or out; params that resolve to different
@@ -323,8 +367,8 @@ void acg_ldpc_cascade_destroy(acg_ldpc_cascade *c);
 acg_ldpc_decoder *acg_ldpc_cascade_stage(acg_ldpc_cascade *c, int32_t stage);
 /* "<first>+<second>" of acg_ldpc_decoder_name, e.g. "MS+BP", "BP+QP-ADMM" */
 const char *acg_ldpc_cascade_name(const acg_ldpc_cascade *c);
-/* "cascade <name> | first: <describe line> | second: <describe line> | chunk=<frames per chunk> last_second_frames=<K>", the
- * last two of the most recent call; buf / cap / return value as acg_ldpc_decoder_describe */
+/* "cascade <name> | first: <describe line> | second: <describe line> | chunk=<frames per chunk> last_second_frames=<K>
+ * handover=posteriors|symbols", chunk and K of the most recent call; buf / cap / return value as acg_ldpc_decoder_describe */
 int32_t acg_ldpc_cascade_describe(const acg_ldpc_cascade *c, char *buf, int32_t cap);
 
 /* buffers as acg_ldpc_decode_batch_dev; stage_dev: device, frames bytes, written 1 or 2 for every frame (may be NULL, and so may

@@ -400,6 +400,56 @@ private:
     acg_ldpc_quant _quant;
 };
 
+// build-added; not in the reference.  Ordered-statistics decoding of order 0 or 1 (acg_ldpc.h, "OSD"): one GF(2) elimination per
+// frame on int16 soft values, always a codeword.  decode() quantises the symbols (snr is ignored); name() == "OSD".
+class OSDDecoder : public HipDecoderBase {
+public:
+    explicit OSDDecoder(int order = 1, int lanes_per_frame = 0) : _order(order), _lanes(lanes_per_frame) {}
+    std::string name() const override { return "OSD"; }
+
+    // Y: symbols -> the int16 soft values the symbol entrance forms (acg_ldpc_debug_osd_soft)
+    static std::vector<int16_t> soft_values(const std::vector<double> &Y) {
+        std::vector<int16_t> s(Y.size());
+        check(acg_ldpc_debug_osd_soft(Y.data(), 1, (int64_t) Y.size(), s.data()));
+        return s;
+    }
+    struct SoftResult {
+        std::vector<uint8_t> bits, ok;   // frames*n bytes, frames flags (all 1)
+        std::vector<int32_t> iters;      // frames: positions of the information set flipped, 0 or 1
+    };
+    // S: frames*n soft values (sign = hard decision, magnitude = reliability)
+    SoftResult decode_soft_batch(const TMatrix &H, const std::vector<int16_t> &S) {
+        const size_t n = H[0].size(), frames = S.size() / n;
+        SoftResult r;
+        r.bits.resize(frames * n);
+        r.ok.resize(frames);
+        r.iters.resize(frames);
+        with_handle(H, [&](acg_ldpc_decoder *d) {
+            check(acg_ldpc_osd_decode_batch(d, S.data(), (int64_t) frames, r.bits.data(), r.ok.data(), r.iters.data()));
+        });
+        return r;
+    }
+    // device buffers, asynchronous on `stream` (null: the handle's own)
+    void decode_soft_batch_dev(const TMatrix &H, const int16_t *s_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                               int32_t *iters_dev = nullptr, void *stream = nullptr) {
+        with_handle(H, [&](acg_ldpc_decoder *d) { check(acg_ldpc_osd_decode_batch_dev(d, s_dev, frames, bits_dev, ok_dev, iters_dev, stream)); });
+    }
+
+protected:
+    void fill(acg_ldpc_params &p) const override {
+        p.algo = ACG_LDPC_OSD;
+        p.max_iter = _order;
+        p.lanes_per_frame = _lanes;
+    }
+    std::pair<TCodeword, bool> finish(const std::vector<uint8_t> &bits, bool ok) const override {
+        if (!ok) return {TCodeword(), false};
+        return {TCodeword(bits.begin(), bits.end()), true};
+    }
+
+private:
+    int _order, _lanes;
+};
+
 // Scores a batch of parity-check matrices of one m x n under one set of QP-ADMM parameters (acg_ldpc_mc_run_codes): the
 // scoring step of optimize_H.cpp:16-25 for many proposals at once.  Thin: one evaluator handle, results as the C ABI's.
 class QPADMMEvaluator {

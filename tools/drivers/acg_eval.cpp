@@ -16,6 +16,10 @@
 //                         stdout and one more row per SNR in report.csv, Method = the cascade's name (e.g. MS+BP), behind
 //                         the rows of the single decoders; stderr adds the share of frames the second stage saw.  The
 //                         detail files do not cover it.  Without the flag nothing changes.
+//                         A, B may also be qms (the fixed-point layered min-sum with the default quantiser, --qms-iters N,
+//                         default 25) and osd (order --osd-order, default 1); qms,osd hands the posteriors over.
+//            [--osd-order K]   also evaluate ordered-statistics decoding of order K = 0 or 1 on the channel symbols (build-added;
+//                         weak on its own on these codes: it is meant as the second stage behind qms)
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -44,10 +48,10 @@ int main(int argc, char **argv) {
     if (a.has("--cascade")) {
         const std::string spec = a.get("--cascade", "");
         const size_t comma = spec.find(',');
-        auto known = [](const std::string &w) { return w == "bp" || w == "admm" || w == "minsum"; };
+        auto known = [](const std::string &w) { return w == "bp" || w == "admm" || w == "minsum" || w == "qms" || w == "osd"; };
         if (comma != std::string::npos) cascade_first = spec.substr(0, comma), cascade_second = spec.substr(comma + 1);
         if (!known(cascade_first) || !known(cascade_second)) {
-            std::fprintf(stderr, "acg_eval: --cascade A,B with A and B of bp, admm, minsum\n");
+            std::fprintf(stderr, "acg_eval: --cascade A,B with A and B of bp, admm, minsum, qms, osd\n");
             return 2;
         }
     }
@@ -84,6 +88,13 @@ int main(int argc, char **argv) {
             p.ms_scale = a.num("--ms-scale", 0.75);
             if (a.has("--layered")) p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
             if (a.has("--ms-f16")) p.precision = ACG_LDPC_PREC_F16;
+        } else if (which == "qms") {  // build-added fixed-point layered min-sum, default quantiser (cascades only)
+            p.algo = ACG_LDPC_BP_MINSUM;
+            p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
+            p.max_iter = (int) a.integer("--qms-iters", 25);
+        } else if (which == "osd") {  // build-added ordered-statistics decoding: max_iter is the order
+            p.algo = ACG_LDPC_OSD;
+            p.max_iter = (int) a.integer("--osd-order", 1);
         } else
             return false;
         return true;
@@ -104,12 +115,20 @@ int main(int argc, char **argv) {
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
+    if (a.has("--osd-order")) {
+        params_of("osd", p);
+        decs.emplace_back();
+        decs.back().create(code, p, gpus, ndev);
+    }
     acg_ldpc_cascade *cascade = nullptr;
     if (a.has("--cascade")) {
         acg_ldpc_params p1, p2;
         params_of(cascade_first, p1);
         params_of(cascade_second, p2);
-        if (acg_ldpc_cascade_create(code, &p1, nullptr, &p2, nullptr, &cascade)) drv::die("acg_ldpc_cascade_create");
+        acg_ldpc_quant q;
+        acg_ldpc_quant_default(&q);
+        if (acg_ldpc_cascade_create(code, &p1, cascade_first == "qms" ? &q : nullptr, &p2, cascade_second == "qms" ? &q : nullptr, &cascade))
+            drv::die("acg_ldpc_cascade_create");
     }
 
     std::cout.precision(5);
