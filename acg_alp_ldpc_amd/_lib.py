@@ -135,6 +135,7 @@ SYMBOLS = {
     "acg_ldpc_debug_layers_wide": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_phi": (C.c_int, [_vp, _vp, _i32, _i32]),
     "acg_ldpc_debug_phi_sat": (C.c_int, [_vp, _vp, _i32]),
+    "acg_ldpc_debug_phi_split": (C.c_int, [_vp]),
     "acg_ldpc_debug_freeze_stats": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "acg_ldpc_debug_freeze_passes": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "acg_ldpc_debug_bp_trace": (C.c_int, [_vp, _vp, _i32, _f64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

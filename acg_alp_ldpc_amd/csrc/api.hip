@@ -893,6 +893,12 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     // a detection loads the snapshot and compares only where the lanes' checksums of their words allow a recurrence, and
     // otherwise only writes the new one; ACG_BP_FREEZE_NO_GATE=1 loads and compares at every detection behind a group's first
     d->freeze_gate = getenv("ACG_BP_FREEZE_NO_GATE") == nullptr;
+    // the instances whose all-latched wavefronts evaluate one of phi's two series where that gives phi's bits (bp_fused_body,
+    // SPLIT; split::).  Same results; on H05 3.2 % faster at -2 dB, 4.5 % at +2 dB, level at -3 dB
+    // (profiles/r17_phisplit_summary.md).  ACG_BP_NO_PHISPLIT=1 keeps the instances without it (bit-for-bit comparison, A/B
+    // runs).  Instances with the freeze path only: `fz` is what tells the kernel that a group has latched.
+    // (build-time instances, and the generic ones at 16 and 32 lanes; the Monte-Carlo launches of a handle run without it)
+    d->phi_split = d->freeze && getenv("ACG_BP_NO_PHISPLIT") == nullptr;
     // measured best on the headline among 3 ... 12 / 1 ... 4 (profiles/r09_freeze_summary.md), and again with the gate among
     // 1 ... 12 / 1 ... 4 (profiles/r12_freeze_gate_summary.md)
     d->freeze_first = 10;
@@ -905,7 +911,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
     for (int mc = 0; mc < 2; mc++) {
         const int variant = wp.variant;
         d->variant = variant;
-        const void *kp = bp_kernel_ptr(algo, d->f64, d->maxd, L, mc != 0, variant, sat);
+        const void *kp = bp_kernel_ptr(algo, d->f64, d->maxd, L, mc != 0, variant, sat, d->phi_split);
         if (!kp) {
             set_error("no kernel instance for this configuration");
             return 3;
@@ -914,15 +920,17 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
         // the fixed-work fp32 sum-product instances only; equal signature, whatever the matrix); ACG_BP_NO_SPEC=1 keeps
         // the generic instance (A/B runs)
         if (sat && algo == 0 && !d->f64 && d->maxd <= 8 && variant == 2 && getenv("ACG_BP_NO_SPEC") == nullptr) {
-            const char *name = nullptr, *rows = nullptr;
-            if (const void *ks = bp_spec_kernel_ptr(lay, mc != 0, &name, &rows)) {
+            const char *name = nullptr, *rows = nullptr, *srows = nullptr;
+            if (const void *ks = bp_spec_kernel_ptr(lay, mc != 0, &name, &rows, d->phi_split, &srows)) {
                 kp = ks;
                 d->spec = name;
                 d->spec_sat_rows = rows;
+                d->spec_split_rows = srows;
             }
         }
         if (int rc = bind_kernel(d, mc, kp)) return rc;
     }
+    if (!d->spec && L > 32) d->phi_split = false;  // (the generic instance at 64 lanes has none)
     return 0;
 }
 
@@ -1139,9 +1147,11 @@ static std::string describe(const acg_ldpc_decoder *d) {
                 if (d->freeze) t += " freeze=1 freeze_cadence=" + std::to_string(d->freeze_first) + "," + std::to_string(d->freeze_period) +
                                         " freeze_gate=" + (d->freeze_gate ? "1" : "0");
                 else t += " freeze=0";
+                t += d->phi_split ? " phi_split=1" : " phi_split=0";
             }
             // the build-time instance with the code's pass structure constant that this handle runs (bp_inst_spec.hip), or 0; in
             // front of it the rows of that instance that keep their phi fast-path test
+            if (d->spec && d->phi_split && d->spec_split_rows) t += std::string(" split_rows=") + d->spec_split_rows;
             if (d->spec && d->spec_sat_rows) t += std::string(" sat_rows=") + d->spec_sat_rows;
             t += std::string(" spec=") + (d->spec ? d->spec : "0");
             return t;

@@ -101,7 +101,29 @@ template <> struct Dom<float> {
         o = (x >= 66.0f) ? 0.0f : o;
         return o;
     }
+    // The two series of phi on their own, each with phi's operations, constants and order: what max(ps, pl) picks when x lies
+    // well inside one range.  pl >= ps for 2 <= x < 66 and ps >= pl for 0 < x <= 1, with a gap of more than 170 ulps at the
+    // thresholds (tests/phi_split_check.cpp in the float model, tests/test_phi_split_gpu.py on every bit pattern), so there
+    // the one series gives phi's bits.  See BpPass::word_c / word_v (SPLIT).
+    static __device__ __forceinline__ float phi_small(float x) {
+        const float w = x * x;
+        float g = fmaf(w, -1.7256659564749327e-06f, 5.431033644982242e-05f);
+        g = fmaf(g, w, -0.001618721877195048f);
+        g = fmaf(g, w, 0.057762255617977924f);
+        return fmaf(w, g, 1.5287663729448977f) - __builtin_amdgcn_logf(x);
+    }
+    static __device__ __forceinline__ float phi_large(float x) {
+        const float t = __builtin_amdgcn_exp2f(-x);
+        const float u = t * t;
+        float r = fmaf(u, 0.40731721508362195f, 0.40423844622223065f);
+        r = fmaf(r, u, 0.5773059513734762f);
+        r = fmaf(r, u, 0.961795680143378f);
+        return t * fmaf(u, r, 2.8853900817779268f);
+    }
 };
+// the thresholds of the split, in the scaled domain (not 1.397 and 1.5, where the two series are one ulp apart)
+#define ACG_PHI_SPLIT_LO 1.0f
+#define ACG_PHI_SPLIT_HI 2.0f
 template <> struct Dom<double> {
     static constexpr double scale = 1.0;
     static __device__ __forceinline__ double phi(double x) { return phi_f(x); }
@@ -181,21 +203,54 @@ struct BpPass {
     // test: the row keeps its fast-path test (bit of the pass's row mask, see PassRuntime); without it phi is evaluated under
     // the store predicate alone, which gives the same bits: phi(+0) = +inf, phi(>= 66) = +0, and the memo returns phi of the
     // bits phi would see.
-    static __device__ __forceinline__ U word_c(T s, U mb, T G, U sg, bool test) {
+    // SPLIT / split (fp32; a row that keeps its test and whose bit of the pass's split mask is set, see PassRuntime): the lanes
+    // that evaluate phi are those left under EXEC by the test.  A wavefront none of whose evaluating lanes lies on the wrong side
+    // of a threshold needs one series of phi only: check side every s <= 1 -> phi_small, variable side every ax >= 2 -> phi_large
+    // (the same bits, Dom<float>::phi_small).  One v_cmp into a scalar mask and a scalar branch between two alternative blocks;
+    // NaN fails both compares and takes the full phi, and the x >= 66 select exists on the full path only (a wavefront that is
+    // all <= 1 cannot reach it).  The decision per 32-lane half, with the second series under the mask of the halves that need
+    // it, evaluates fewer series and measured slower (DESIGN §3).
+    template <bool SPLIT = false>
+    static __device__ __forceinline__ U word_c(T s, U mb, T G, U sg, bool test, bool split = false) {
         if (!test) return (B::to(Dom<T>::phi(s)) & ~SIGN) | sg;
         U w = (B::to(G) & ~SIGN) | sg;
+        if constexpr (SPLIT && sizeof(T) == 4) {
+            if (split) {
+                if (B::to(s) != mb) {
+                    T o;
+                    if (__ballot(!(s <= (T) ACG_PHI_SPLIT_LO)) == 0ull) o = Dom<T>::phi_small(s);
+                    else o = Dom<T>::phi(s);
+                    w = (B::to(o) & ~SIGN) | sg;
+                }
+                return w;
+            }
+        }
         if (B::to(s) != mb) w = (B::to(Dom<T>::phi(s)) & ~SIGN) | sg;
         return w;
     }
-    static __device__ __forceinline__ U word_v(T ax, U w, bool test) {
+    template <bool SPLIT = false>
+    static __device__ __forceinline__ U word_v(T ax, U w, bool test, bool split = false) {
         if (!test) return w | (B::to(Dom<T>::phi(ax)) & ~SIGN & ~ONE);
+        if constexpr (SPLIT && sizeof(T) == 4) {
+            if (split) {
+                if (!(ax >= (T) 66)) {
+                    T o;
+                    if (__ballot(!(ax >= (T) ACG_PHI_SPLIT_HI)) == 0ull) o = Dom<T>::phi_large(ax);
+                    else o = Dom<T>::phi(ax);
+                    w |= B::to(o) & ~SIGN & ~ONE;
+                }
+                return w;
+            }
+        }
         if (!(ax >= (T) 66)) w |= B::to(Dom<T>::phi(ax)) & ~SIGN & ~ONE;
         return w;
     }
 
     // check(), sum-product with the fast path: the exclude-self sums first, phi per edge under its store predicate
     // rows: bit j set = edge row j keeps its fast-path test (a constant of the pass: all ones, or a static policy's c_sat_rows)
-    static __device__ __forceinline__ U check_sat(T *__restrict__ Ap, int slot, const int *cnt, bool write, unsigned rows) {
+    // SPLIT / srows: bit j set = edge row j takes the one-series phi where its unit allows (word_c; a constant of the pass as rows is)
+    template <bool SPLIT = false>
+    static __device__ __forceinline__ U check_sat(T *__restrict__ Ap, int slot, const int *cnt, bool write, unsigned rows, unsigned srows = 0u) {
         T x[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
@@ -219,7 +274,7 @@ struct BpPass {
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             if (write && slot < cnt[j + 1])
-                Ap[j * L] = B::from(word_c(es[j], (U) 0, (T) INFINITY, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u));
+                Ap[j * L] = B::from(word_c<SPLIT>(es[j], (U) 0, (T) INFINITY, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u, (srows >> j) & 1u));
         }
         return S;
     }
@@ -251,9 +306,9 @@ struct BpPass {
     // Returns the XOR of the incoming words: its LSB is the syndrome bit of this lane's check (padding words are +0).
     // UNI: every check of the code has degree D (the caller checked c_cnt_ge[D] == m): one write predicate for the whole
     // pass instead of one compare + EXEC mask + branch per edge
-    template <bool UNI = false>
-    static __device__ __forceinline__ U check(T *__restrict__ Ap, int slot, const int *cnt, bool write, T ms_scale, unsigned rows = ~0u) {
-        if constexpr (SAT && ALGO == 0 && !UNI) return check_sat(Ap, slot, cnt, write, rows);
+    template <bool UNI = false, bool SPLIT = false>
+    static __device__ __forceinline__ U check(T *__restrict__ Ap, int slot, const int *cnt, bool write, T ms_scale, unsigned rows = ~0u, unsigned srows = 0u) {
+        if constexpr (SAT && ALGO == 0 && !UNI) return check_sat<SPLIT>(Ap, slot, cnt, write, rows, srows);
         T x[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) x[j] = Ap[j * L];
@@ -331,8 +386,9 @@ struct BpPass {
     // saturated to +0 (or fall below half an ulp of m) it IS m, in every sweep that follows: the memo of phi_c holds m's
     // bits (aw & am; am = the magnitude mask, or 0 to turn the memo off) and ag = phi(m), built with aw (BpCore::abs_phi).
     // Edge D - 1 keeps the +0 rule.  rows: as check_sat's, bit D - 1 is the register edge's.
+    template <bool SPLIT = false>
     static __device__ __forceinline__ U check_abs(T *__restrict__ Ap, int slot, const int *cnt, bool write, U &aw, T allr, T &r_out,
-                                                  T ag = (T) INFINITY, U am = 0, unsigned rows = ~0u) {
+                                                  T ag = (T) INFINITY, U am = 0, unsigned rows = ~0u, unsigned srows = 0u) {
         T x[D];
 #pragma unroll
         for (int j = 0; j < D - 1; ++j) x[j] = Ap[j * L];
@@ -360,10 +416,10 @@ struct BpPass {
 #pragma unroll
             for (int j = 0; j < D - 1; ++j) {
                 if (write && slot < cnt[j + 2])
-                    Ap[j * L] = B::from(word_c(out[j], mb, ag, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u));
+                    Ap[j * L] = B::from(word_c<SPLIT>(out[j], mb, ag, (S ^ B::to(x[j])) & SIGN, (rows >> j) & 1u, (srows >> j) & 1u));
             }
             if (write && slot < cnt[1]) {
-                const T R = B::from(word_c(out[D - 1], (U) 0, (T) INFINITY, (S ^ aw) & SIGN, (rows >> (D - 1)) & 1u));
+                const T R = B::from(word_c<SPLIT>(out[D - 1], (U) 0, (T) INFINITY, (S ^ aw) & SIGN, (rows >> (D - 1)) & 1u, (srows >> (D - 1)) & 1u));
                 r_out = R;
                 aw = (aw & ~ONE) | ((allr + R <= (T) 0) ? ONE : (U) 0);
             }
@@ -395,20 +451,20 @@ struct BpPass {
     static __device__ __forceinline__ T &at(T *__restrict__ A, int pos) {
         return BYTES ? *reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(A) + pos) : A[pos];
     }
-    template <typename IdxPtr, bool BYTES = false>
-    static __device__ __forceinline__ U var(T *__restrict__ A, IdxPtr ip, T llr, int slot, const int *cnt, bool write, unsigned rows = ~0u) {
+    template <typename IdxPtr, bool BYTES = false, bool SPLIT = false>
+    static __device__ __forceinline__ U var(T *__restrict__ A, IdxPtr ip, T llr, int slot, const int *cnt, bool write, unsigned rows = ~0u, unsigned srows = 0u) {
         int pos[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) pos[k] = ip[k * L];
-        return var_at<false, BYTES>(A, pos, llr, slot, cnt, write, rows);
+        return var_at<false, BYTES, SPLIT>(A, pos, llr, slot, cnt, write, rows, srows);
     }
 
     // the same sweep with the D message positions already known (register-resident index table)
     // Returns the posterior hard decision (0 / 1).
-    // rows (SAT): bit k set = edge row k keeps its fast-path test, as check_sat's
-    template <bool UNI = false, bool BYTES = false>
+    // rows (SAT): bit k set = edge row k keeps its fast-path test, as check_sat's; SPLIT / srows: as check_sat's (word_v)
+    template <bool UNI = false, bool BYTES = false, bool SPLIT = false>
     static __device__ __forceinline__ U var_at(T *__restrict__ A, const int (&pos)[D], T llr, int slot, const int *cnt, bool write,
-                                               unsigned rows = ~0u) {
+                                               unsigned rows = ~0u, unsigned srows = 0u) {
         T c[D];
 #pragma unroll
         for (int k = 0; k < D; ++k) c[k] = at<BYTES>(A, pos[k]);
@@ -433,7 +489,7 @@ struct BpPass {
 #pragma unroll
             for (int k = 0; k < D; ++k) {
                 if (write && slot < cnt[k + 1])
-                    at<BYTES>(A, pos[k]) = B::from(word_v(B::from(B::to(xs[k]) & ~SIGN), (xs[k] <= (T) 0) ? hard_neg : hard, (rows >> k) & 1u));
+                    at<BYTES>(A, pos[k]) = B::from(word_v<SPLIT>(B::from(B::to(xs[k]) & ~SIGN), (xs[k] <= (T) 0) ? hard_neg : hard, (rows >> k) & 1u, (srows >> k) & 1u));
             }
             return hard;
         }
@@ -495,6 +551,9 @@ struct PassRuntime {
     static constexpr bool STATIC = false;
     static constexpr unsigned c_sat_rows(int) { return ~0u; }
     static constexpr unsigned v_sat_rows(int) { return ~0u; }
+    // rows that take the one-series phi where the wavefront allows (BpPass::word_c / word_v, SPLIT), same bit order: every row
+    static constexpr unsigned c_split_rows(int) { return ~0u; }
+    static constexpr unsigned v_split_rows(int) { return ~0u; }
 };
 // the pass loops: `for (p = 0 .. n - 1) BODY` as a loop (run-time policy) or as straight-line code (static policy: n is one
 // of its constants).  BODY is a macro that holds the braces of the loop body.
@@ -647,10 +706,12 @@ struct BpCore {
     // the hard decisions that ride in the v->c words (the estimate of the previous variable sweep).
     // aw / al / ar: the absorbed variables' words, LLRs and (debug trace) c->v messages, see BpPass::check_abs; ag / am: the
     // phi memo of the SATSKIP sweeps (abs_phi, wave-uniform mask am)
+    // SPLIT: the sweep compiled with the one-series phi of BpPass::word_c in the rows of PS::c_split_rows
+    template <bool SPLIT = false>
     __device__ __forceinline__ U check_phase(bool write, AbsWord &aw, const AbsLlr &al, AbsLlr &ar, const AbsLlr &ag, U am) {
         U acc = 0;
         const int nc = n_cpass() - n_apass();
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check(Ap, slot, ccnt, write, ms_scale, PS::c_sat_rows(p))
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::template check<false, SPLIT>(Ap, slot, ccnt, write, ms_scale, PS::c_sat_rows(p), PS::c_split_rows(p))
 #define ACG_BODY                                                       \
     {                                                                  \
         const int md = c_pass(2 * p);                                  \
@@ -673,7 +734,7 @@ struct BpCore {
                 const int md = c_pass(2 * p);
                 T *Ap = A + c_pass(2 * p + 1) + l;
                 const int slot = p * L + l;
-#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::check_abs(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am, PS::c_sat_rows(p))
+#define ACG_CALL(D) acc |= BpPass<T, D, L, ALGO, SATSKIP>::template check_abs<SPLIT>(Ap, slot, ccnt, write, aw[q], al[q], ar[q], ag[q], am, PS::c_sat_rows(p), PS::c_split_rows(p))
                 ACG_PASS_SWITCH(md, ACG_CALL)
 #undef ACG_CALL
             }
@@ -692,8 +753,9 @@ struct BpCore {
         return check_phase(write, aw, al, ar, ag, 0);
     }
 
+    template <bool SPLIT = false>
     __device__ __forceinline__ void var_phase(const LlrRegs &lr, bool write) {
-#define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB>(A, ip, llr, slot, vcnt, write, PS::v_sat_rows(p))
+#define ACG_CALL(D) BpPass<T, D, L, ALGO, SATSKIP>::template var<const uint16_t *, IDXB, SPLIT>(A, ip, llr, slot, vcnt, write, PS::v_sat_rows(p), PS::v_split_rows(p))
 #define ACG_BODY                                                       \
     {                                                                  \
         const int md = v_pass(2 * p);                                  \
@@ -1030,7 +1092,9 @@ constexpr int bp_min_waves() {
 // channel LLRs in slot order (a.dbg_post: [frame][n_vpass * L]); the product instances are compiled with DBG = false.
 // SAT: the phi fast path of the sweeps (BpCore::SATSKIP; fixed-work decoders), see sat::bp_fused_kernel
 // PS: the pass structure policy (PassRuntime: any code; a static policy: the instances of bp_inst_spec.hip)
-template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG, bool SAT, typename PS = PassRuntime>
+// SPLIT: the sweeps of a wavefront whose groups have all latched evaluate one series of phi where that gives phi's bits
+// (BpPass::word_c / word_v); instances of their own (split::), which a handle takes unless ACG_BP_NO_PHISPLIT=1 is set
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG, bool SAT, typename PS = PassRuntime, bool SPLIT = false>
 __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using Core = BpCore<T, MAXD, L, ALGO, IDXLDS, NVP, IDXLDS && ACG_IDX_BYTES, SAT, PS>;  // the LDS copy of the index table is in byte offsets
@@ -1058,6 +1122,8 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
     constexpr bool FREEZE = Core::SATSKIP && NVP > 0 && !DBG;  // (NVP > 0: the instances the host takes for fixed-work decoders)
     // (ACG_SPEC_VIREG: the static-policy instances, whose sweeps need fewer registers, hold them again — see DESIGN §3)
     constexpr bool VIREG = !FREEZE || (PS::STATIC && ACG_SPEC_VIREG);
+    // the one-series phi: the instances with the freeze path, and their debug twin (DBG: `latched` in the place of `fz`)
+    constexpr bool PHISPLIT = SPLIT && Core::SATSKIP && NVP > 0;
     typename Core::LlrRegs lr;
     typename Core::VarIds vi;
 #pragma unroll
@@ -1332,6 +1398,16 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
         if (__ballot(active) == 0ull) break;
         init_frames();
         // ---- one flooding iteration (bp.h:186-188) -------------------------------------------
+        // PHISPLIT: each sweep exists twice, and the one with the one-series phi runs while every group of the wavefront that has
+        // a frame has latched: before its latch a frame has next to no unit on one side of a threshold (0.6 % on the check side,
+        // 20 % on the variable side against 65 % and 92 % behind it, tools/phi_census.cpp --split), and a wavefront decides as a whole.
+        // One scalar branch per sweep, no predicate per row.
+        bool split_now = false;
+        if constexpr (PHISPLIT) split_now = __ballot(active && !is_latched()) == 0ull;
+        if constexpr (PHISPLIT) {
+            if (split_now) core.template check_phase<true>(active, aw, al, ar, ag, am);
+            else core.check_phase(active, aw, al, ar, ag, am);
+        } else
         core.check_phase(active, aw, al, ar, ag, am);
         wave_sync();
         // debug dumps: per frame the message array, then the absorbed edges' words (absorbed pass q, lane l at a_words + q*L + l);
@@ -1342,6 +1418,10 @@ __device__ __forceinline__ void bp_fused_body(const BpTables &t, const DecodeArg
             for (int q = 0; q < Core::NAP; ++q)
                 if (q < core.n_apass()) reinterpret_cast<T *>(a.dbg_c2v)[(size_t) frame * dbg_cw + t.a_words + q * L + l] = ar[q];
         }
+        if constexpr (PHISPLIT) {
+            if (split_now) core.template var_phase<true>(lr, active);
+            else core.var_phase(lr, active);
+        } else
         core.var_phase(lr, active);
         wave_sync();
         if (DBG && active && it == a.max_iter - 1 && a.dbg_v2c) {
@@ -1473,3 +1553,11 @@ __global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fus
     bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, true>(t, a);
 }
 }  // namespace sat
+
+// the fixed-work instances with the one-series phi as well (bp_fused_body, SPLIT): same name and template arguments again
+namespace split {
+template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>
+__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {
+    bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, true, PassRuntime, true>(t, a);
+}
+}  // namespace split

@@ -34,21 +34,23 @@
 namespace acg {
 #include "bp_core.inc"
 
-const void *bp_kernel_ptr_dbg(int f64, int L) {
+const void *bp_kernel_ptr_dbg(int f64, int L, int sat) {
+    if (sat != 0 && f64) return nullptr;
 #ifdef ACG_FAST_BUILD
-    return f64 ? nullptr : bp_kernel_ptr_spa_f32_dbg(L);
+    return f64 ? nullptr : bp_kernel_ptr_spa_f32_dbg(L, sat);
 #else
-    return f64 ? bp_kernel_ptr_spa_f64_dbg(L) : bp_kernel_ptr_spa_f32_dbg(L);
+    return f64 ? bp_kernel_ptr_spa_f64_dbg(L) : bp_kernel_ptr_spa_f32_dbg(L, sat);
 #endif
 }
 
-// algo: 0 sum-product, 1 min-sum; f64: 0/1; sat: the phi fast path where an instance has it (fp32 sum-product)
-const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat) {
+// algo: 0 sum-product, 1 min-sum; f64: 0/1; sat: the phi fast path where an instance has it (fp32 sum-product); split: of
+// those, the instance with the one-series phi
+const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat, bool split) {
 #ifdef ACG_FAST_BUILD
     if (f64 || algo) return nullptr;
-    return bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat);
+    return bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat, split);
 #else
-    if (algo == 0) return f64 ? bp_kernel_ptr_spa_f64(maxd, L, mc, variant) : bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat);
+    if (algo == 0) return f64 ? bp_kernel_ptr_spa_f64(maxd, L, mc, variant) : bp_kernel_ptr_spa_f32(maxd, L, mc, variant, sat, split);
     return f64 ? bp_kernel_ptr_ms_f64(maxd, L, mc, variant) : bp_kernel_ptr_ms_f32(maxd, L, mc, variant);
 #endif
 }
@@ -87,6 +89,45 @@ __global__ void phi_sat_debug_kernel(const float *x, uint32_t *out, int n) {
 
 hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s) {
     hipLaunchKernelGGL(phi_sat_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, out, n);
+    return hipGetLastError();
+}
+
+// The one-series phi of the split sweeps against the full evaluation, over every non-negative fp32 bit pattern (NaNs included).
+// out (PHI_SPLIT_NOUT words, set up by the launcher): [0] patterns whose one series does not give phi's bits — phi_large on
+// 2 <= x < 66, phi_small on 0 < x <= 1 — [1] the smallest such pattern, [2] the largest finite x > 0 with ps >= pl, [3] the
+// smallest x > 0 with pl >= ps (between them either series is right: the distance to the thresholds is the margin), [4]
+// patterns where max(ps, pl) behind phi's saturation select, the full path of a split row, does not give phi's bits, [5] the
+// smallest such pattern.  Grid-stride; one atomic per counter and thread.
+__global__ void phi_split_debug_kernel(uint32_t *out) {
+    uint32_t bad = 0, first = 0xFFFFFFFFu, top_small = 0u, low_large = 0xFFFFFFFFu, bad_full = 0, first_full = 0xFFFFFFFFu;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < 0x80000000ull; i += stride) {
+        const uint32_t b = (uint32_t) i;
+        const float x = __uint_as_float(b);
+        const uint32_t full = __float_as_uint(Dom<float>::phi(x));
+        const float ps = Dom<float>::phi_small(x), pl = Dom<float>::phi_large(x);
+        if (x >= ACG_PHI_SPLIT_HI && x < 66.0f && __float_as_uint(pl) != full) bad += 1, first = b < first ? b : first;
+        if (x > 0.0f && x <= ACG_PHI_SPLIT_LO && __float_as_uint(ps) != full) bad += 1, first = b < first ? b : first;
+        if (x > 0.0f && x < 66.0f) {
+            if (ps >= pl) top_small = b > top_small ? b : top_small;
+            if (pl >= ps) low_large = b < low_large ? b : low_large;
+        }
+        float o = __builtin_fmaxf(ps, pl);
+        o = (x >= 66.0f) ? 0.0f : o;
+        if (__float_as_uint(o) != full) bad_full += 1, first_full = b < first_full ? b : first_full;
+    }
+    if (bad) atomicAdd(&out[0], bad);
+    atomicMin(&out[1], first);
+    atomicMax(&out[2], top_small);
+    atomicMin(&out[3], low_large);
+    if (bad_full) atomicAdd(&out[4], bad_full);
+    atomicMin(&out[5], first_full);
+}
+
+hipError_t phi_split_debug_launch(uint32_t *out, hipStream_t s) {
+    const uint32_t init[PHI_SPLIT_NOUT] = {0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu};
+    if (hipError_t e = hipMemcpyAsync(out, init, sizeof(init), hipMemcpyHostToDevice, s)) return e;
+    hipLaunchKernelGGL(phi_split_debug_kernel, dim3(4096), dim3(256), 0, s, out);
     return hipGetLastError();
 }
 

@@ -71,12 +71,30 @@ struct SatCensusProbe {
     virtual ~SatCensusProbe() = default;
 };
 
+// Census of the one-series phi (BpPass::word_c / word_v with SPLIT): the units that still evaluate phi, by where their
+// evaluating lanes (those that store and do not take a fast path) lie: every one at or below lo (check side: phi_small alone would
+// do), every one at or above hi (variable side: phi_large alone), or mixed (NaN counts as mixed).  Kept apart for the sweeps before
+// a frame's latch — the first estimate that passes the syndrome — and behind it, where a fixed-work decoder spends most of its
+// sweeps.  Counted twice on the check side: with the +0 rule as the only fast path (a decoder under ACG_BP_NO_PHIMEMO=1), and with
+// the memo hits of the absorbed passes taken out as well (the default decoder; *_memo).  The variable side has one rule.
+struct SplitCensusRow {
+    long units = 0, skipped = 0, small = 0, large = 0;  // mixed = units - skipped - small - large
+    long skipped_memo = 0, small_memo = 0, large_memo = 0;
+};
+struct SplitCensus {
+    float lo = 1.0f, hi = 2.0f;                             // in the log2(e)-scaled domain
+    std::vector<std::vector<SplitCensusRow>> c[2], v[2];   // [0 before the latch or never latched, 1 behind it][pass][edge row]
+    long sweeps[2] = {0, 0};                                // sweeps run before / behind the latch, all frames
+    int latch = -1;  // of the last frame: the sweeps it had run when its estimate first passed the syndrome; -1: it never did
+};
+
 // One frame of the model from channel LLRs in the log2(e)-scaled domain (llr_of_var[n]); counts go to cs.  stop_at_repeat: the
 // frame ends at its first exact state repeat (the message words and the absorbed words after a sweep equal those after one of
 // the eight sweeps before it: every later state is one already seen), as a latched frame does on the device (the freeze).
-// Returns the number of sweeps run; est[n]: the last hard decisions.
+// Returns the number of sweeps run; est[n]: the last hard decisions.  split: also the census of the one-series phi and the
+// frame's latch sweep (SplitCensus::latch).
 inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *llr_of_var, int sweeps, bool stop_at_repeat, SatCensus &cs,
-                               std::vector<uint8_t> &est, SatCensusProbe *probe = nullptr) {
+                               std::vector<uint8_t> &est, SatCensusProbe *probe = nullptr, SplitCensus *split = nullptr) {
     using namespace sat_census;
     const int L = lay.L, n = c.n;
     auto cdeg = [&](int i) { return i < 0 ? 0 : c.row_ptr[i + 1] - c.row_ptr[i]; };
@@ -113,12 +131,14 @@ inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *
     constexpr int HIST = 8;
     std::vector<std::vector<uint32_t>> hist;  // the states after the last HIST sweeps (A, then aw)
     int run = 0;
+    int behind = 0;  // split: the frame has latched
+    if (split) split->latch = -1;
     for (int it = 0; it < sweeps; it++) {
         // ---- check sweep
         for (int p = 0; p < lay.n_cpass; p++) {
             const int D = lay.c_maxdeg[p];
             const bool absd = p >= nc;
-            std::vector<char> all_t(D, 1), all_m(D, 1), all_a(D, 1), any(D, 0);
+            std::vector<char> all_t(D, 1), all_m(D, 1), all_a(D, 1), any(D, 0), all_lo(D, 1), all_hi(D, 1), memo_lo(D, 1), memo_hi(D, 1);
             for (int l = 0; l < L; l++) {
                 const size_t sl = (size_t) p * L + l;
                 const int chk = lay.c_chk[sl], dg = cdeg(chk);
@@ -150,6 +170,14 @@ inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *
                     all_t[j] &= t;
                     all_m[j] &= t || (absd && memo_here && e == mb);
                     all_a[j] &= t || (memo_here && e == mb);
+                    if (split && !t) {
+                        all_lo[j] &= es[j] <= split->lo;
+                        all_hi[j] &= es[j] >= split->hi;
+                        if (!(absd && memo_here && e == mb)) {
+                            memo_lo[j] &= es[j] <= split->lo;
+                            memo_hi[j] &= es[j] >= split->hi;
+                        }
+                    }
                     const float o = t ? INFINITY : phi(es[j]);
                     if (absd && j == D - 1) {
                         const float R = flt((bits(o) & ~SIGN) | ((S ^ x[j]) & SIGN));
@@ -167,12 +195,22 @@ inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *
                     r.today += all_t[j];
                     r.memo += all_m[j];
                     r.memo_all += all_a[j];
+                    if (split) {
+                        SplitCensusRow &q = split->c[behind][p][j];
+                        q.units++;
+                        if (all_t[j]) q.skipped++;
+                        else if (all_lo[j]) q.small++;
+                        else if (all_hi[j]) q.large++;
+                        if (all_m[j]) q.skipped_memo++;
+                        else if (memo_lo[j]) q.small_memo++;
+                        else if (memo_hi[j]) q.large_memo++;
+                    }
                 }
         }
         // ---- variable sweep
         for (int p = 0; p < lay.n_vpass; p++) {
             const int D = lay.v_maxdeg[p];
-            std::vector<char> all_v(D, 1), any(D, 0);
+            std::vector<char> all_v(D, 1), any(D, 0), all_lo(D, 1), all_hi(D, 1);
             for (int l = 0; l < L; l++) {
                 const size_t sl = (size_t) p * L + l;
                 const int v = lay.v_var[sl], dg = vdeg(v);
@@ -199,6 +237,10 @@ inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *
                     const float ax = fabsf(xs[k]);
                     if (probe) probe->input(1, p, k, ax);
                     all_v[k] &= ax >= 66.0f;
+                    if (split && !(ax >= 66.0f)) {
+                        all_lo[k] &= ax <= split->lo;
+                        all_hi[k] &= ax >= split->hi;
+                    }
                     A[pos[k]] = (bits(phi(ax)) & ~SIGN & ~ONE) | (xs[k] <= 0 ? (hard | SIGN) : hard);
                 }
             }
@@ -209,9 +251,34 @@ inline int bp_sat_census_frame(const Code &c, const BpLayout &lay, const float *
                     r.today += all_v[k];
                     r.memo += all_v[k];
                     r.memo_all += all_v[k];
+                    if (split) {
+                        SplitCensusRow &q = split->v[behind][p][k];
+                        q.units++;
+                        if (all_v[k]) q.skipped++, q.skipped_memo++;
+                        else if (all_lo[k]) q.small++, q.small_memo++;
+                        else if (all_hi[k]) q.large++, q.large_memo++;
+                    }
                 }
         }
         run = it + 1;
+        if (split) {
+            split->sweeps[behind]++;
+            if (!behind) {
+                // the estimate of this sweep against the syndrome, as the head of the kernel's next trip takes it
+                std::vector<uint8_t> e(n, 0);
+                for (size_t s = 0; s < vhard.size(); s++)
+                    if (lay.v_var[s] >= 0) e[lay.v_var[s]] = (uint8_t) vhard[s];
+                for (size_t s = 0; s < aw.size(); s++)
+                    if (lay.a_var[s] >= 0) e[lay.a_var[s]] = (uint8_t) (aw[s] & ONE);
+                bool bad = false;
+                for (int i = 0; i < c.m && !bad; i++) {
+                    int x = 0;
+                    for (int k = c.row_ptr[i]; k < c.row_ptr[i + 1]; k++) x ^= e[c.edge_var[k]];
+                    bad = x != 0;
+                }
+                if (!bad) behind = 1, split->latch = run;
+            }
+        }
         if (stop_at_repeat) {
             std::vector<uint32_t> st(A);
             st.insert(st.end(), aw.begin(), aw.end());
@@ -239,8 +306,22 @@ inline SatCensus bp_sat_census_empty(const BpLayout &lay) {
     return cs;
 }
 
+inline SplitCensus bp_split_census_empty(const BpLayout &lay, float lo, float hi) {
+    SplitCensus sp;
+    sp.lo = lo;
+    sp.hi = hi;
+    for (int b = 0; b < 2; b++) {
+        sp.c[b].resize(lay.n_cpass);
+        sp.v[b].resize(lay.n_vpass);
+        for (int p = 0; p < lay.n_cpass; p++) sp.c[b][p].resize(lay.c_maxdeg[p]);
+        for (int p = 0; p < lay.n_vpass; p++) sp.v[b][p].resize(lay.v_maxdeg[p]);
+    }
+    return sp;
+}
+
 // `frames` frames of `sweeps` sweeps at most, at `snr` dB: frame f draws its noise from std::mt19937(f + 1)
-inline SatCensus bp_sat_census(const Code &c, const BpLayout &lay, int frames, int sweeps, double snr, bool stop_at_repeat) {
+// split (from bp_split_census_empty): the census of the one-series phi of the same frames
+inline SatCensus bp_sat_census(const Code &c, const BpLayout &lay, int frames, int sweeps, double snr, bool stop_at_repeat, SplitCensus *split = nullptr) {
     SatCensus cs = bp_sat_census_empty(lay);
     const double var = std::pow(10, -(snr / 10)) / 2, inv_var2 = 2.0 / var, sigma = std::sqrt(var);
     std::vector<float> ch(c.n);
@@ -249,7 +330,7 @@ inline SatCensus bp_sat_census(const Code &c, const BpLayout &lay, int frames, i
         std::mt19937 rng((uint32_t) (f + 1));
         std::normal_distribution<double> nd(0.0, 1.0);
         for (int v = 0; v < c.n; v++) ch[v] = (float) ((1.0 + sigma * nd(rng)) * (inv_var2 * 1.44269504088896341));
-        cs.sweeps += bp_sat_census_frame(c, lay, ch.data(), sweeps, stop_at_repeat, cs, est);
+        cs.sweeps += bp_sat_census_frame(c, lay, ch.data(), sweeps, stop_at_repeat, cs, est, nullptr, split);
         bool bad = false;
         for (int i = 0; i < c.m && !bad; i++) {
             int x = 0;

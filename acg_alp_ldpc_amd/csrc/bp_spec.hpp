@@ -27,6 +27,9 @@ struct BpSpecSig {
     // hexadecimal, one mask per pass: "c:7f,3f,30,1f,f/v:3f,...") with the census SNR and threshold they come from; results do
     // not depend on them
     const char *sat_rows = nullptr;
+    // likewise not part of the match: the rows that take the one-series phi where the wavefront allows (c_split_rows /
+    // v_split_rows, same form without the census part; all rows unless the generator was given -r)
+    const char *split_rows = nullptr;
 };
 
 // the signature's tables of a layout, owned

@@ -1,6 +1,7 @@
 // C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 4: the acg_ldpc_debug_* helpers (tests only).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 #include "handle.hpp"
@@ -35,7 +36,11 @@ static int acg_ldpc_debug_bp_trace_impl(const acg_ldpc_code *code, const double 
     size_t wc = (size_t) E * 64, wp = (size_t) n * 64;
     if (fused) {
         const void *kp = nullptr;
-        if (d->variant == 2 && d->maxd <= 8) kp = bp_kernel_ptr_dbg(f64, d->L);
+        // ACG_BP_TRACE_SAT=1 / 2 (tests): the dump from the fixed-work instance with the phi fast path / with the one-series phi
+        // as well, in the place of the plain instance (fp32, 32 lanes per frame)
+        const char *tenv = getenv("ACG_BP_TRACE_SAT");
+        const int tsat = tenv ? atoi(tenv) : 0;
+        if (d->variant == 2 && d->maxd <= 8) kp = bp_kernel_ptr_dbg(f64, d->L, tsat);
         else if (d->variant == -1 && d->L == 256 && d->blk_idxlds && !d->blk_idxreg) kp = bp_block_kernel_ptr_dbg(f64);
         if (!kp) {
             set_error("no debug instance of the fused kernel for this code / lanes_per_frame");
@@ -342,6 +347,23 @@ int acg_ldpc_debug_freeze_passes(acg_ldpc_decoder *d, int64_t *store_passes, int
 
 int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n) {
     return guarded([&] { return acg_ldpc_debug_phi_sat_impl(x_host, out_host, n); });
+}
+
+static int acg_ldpc_debug_phi_split_impl(uint32_t *out_host) {
+    if (!out_host) {
+        set_error("null argument");
+        return 1;
+    }
+    DeviceBuf dout;
+    if (int rc = dout.reserve(sizeof(uint32_t) * PHI_SPLIT_NOUT)) return rc;
+    HIP_OK(phi_split_debug_launch(dout.as<uint32_t>(), nullptr));
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out_host, dout.p, sizeof(uint32_t) * PHI_SPLIT_NOUT, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int acg_ldpc_debug_phi_split(uint32_t *out_host) {
+    return guarded([&] { return acg_ldpc_debug_phi_split_impl(out_host); });
 }
 
 }  // extern "C"

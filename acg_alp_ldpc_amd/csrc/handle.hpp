@@ -149,11 +149,13 @@ struct acg_ldpc_decoder {
     bool freeze = false;
     bool freeze_count = false;  // acg_ldpc_debug_freeze_stats asked for the counters
     bool freeze_gate = true;    // a per-lane checksum decides whether a detection loads and compares (ACG_BP_FREEZE_NO_GATE=1: always)
+    bool phi_split = false;     // the handle runs the instances with the one-series phi (split::; ACG_BP_NO_PHISPLIT=1: those without)
     int freeze_first = 0, freeze_period = 0;
     size_t freeze_slot_words = 0;
     acg::DeviceBuf freeze_ws;
     // name of the build-time instance with this code's pass structure constant that the handle runs (bp_inst_spec.hip); null: the generic one
     const char *spec = nullptr;
+    const char *spec_split_rows = nullptr;  // its rows with the one-series phi (BpSpecSig::split_rows), for describe()
     const char *spec_sat_rows = nullptr;  // that instance's fast-path row masks (BpSpecSig::sat_rows), for describe()
     bool pair = false;      // ACG_LDPC_PREC_F16: two frames per workgroup, packed half-precision messages (bp_pair.hip)
     bool blk_idxlds = false, blk_idxreg = false;

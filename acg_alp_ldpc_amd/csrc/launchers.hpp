@@ -16,24 +16,27 @@ namespace acg {
 struct Code;  // ldpc_internal.hpp
 
 // ---- bp_inst_{spa,ms}_{f32,f64}.hip: the instances of bp_fused_kernel (bp_core.inc) ----
-const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat);
+const void *bp_kernel_ptr_spa_f32(int maxd, int L, bool mc, int variant, bool sat, bool split = false);
 const void *bp_kernel_ptr_spa_f64(int maxd, int L, bool mc, int variant);
 const void *bp_kernel_ptr_ms_f32(int maxd, int L, bool mc, int variant);
 const void *bp_kernel_ptr_ms_f64(int maxd, int L, bool mc, int variant);
-const void *bp_kernel_ptr_spa_f32_dbg(int L);
+const void *bp_kernel_ptr_spa_f32_dbg(int L, int sat = 0);
 const void *bp_kernel_ptr_spa_f64_dbg(int L);
 
 // ---- bp_inst_spec.hip: build-time instances with a code's pass structure constant (bp_spec.hpp) ----
 struct BpLayout;  // ldpc_internal.hpp
-const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name, const char **sat_rows = nullptr);
+const void *bp_spec_kernel_ptr(const BpLayout &lay, bool mc, const char **name, const char **sat_rows = nullptr, bool split = false,
+                               const char **split_rows = nullptr);
 
 // ---- bp_kernels.hip ----
-const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat);
-const void *bp_kernel_ptr_dbg(int f64, int L);
+const void *bp_kernel_ptr(int algo, int f64, int maxd, int L, bool mc, int variant, bool sat, bool split = false);
+const void *bp_kernel_ptr_dbg(int f64, int L, int sat = 0);
 hipError_t bp_launch(const void *kernel, const BpTables &t, const DecodeArgs &a, int grid, int block, size_t lds,
                      hipStream_t s);
 hipError_t phi_debug_launch(const void *x, void *out, int n, int f64, hipStream_t s);
 hipError_t phi_sat_debug_launch(const float *x, uint32_t *out, int n, hipStream_t s);
+constexpr int PHI_SPLIT_NOUT = 6;  // words of phi_split_debug_launch's result (bp_kernels.hip: phi_split_debug_kernel)
+hipError_t phi_split_debug_launch(uint32_t *out, hipStream_t s);
 
 // ---- mc_kernels.hip ----
 hipError_t awgn_launch(float *y, int64_t frames, int n, int nwords, int64_t first_frame, uint64_t seed,

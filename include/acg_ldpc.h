@@ -590,6 +590,14 @@ int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f6
 /* diagnostics: the phi fast path of the fp32 sum-product sweeps on n float inputs in the kernels' log2(e)-scaled domain;
  * out: 3n uint32 = per input the bits of the full phi, of the check-side path and of the variable-side path (on |x|). */
 int acg_ldpc_debug_phi_sat(const void *x_host, void *out_host, int32_t n);
+/* diagnostics: the one-series phi of the fixed-work fused sum-product sweeps (phi_large where every evaluating lane of a
+ * wavefront has x >= 2, phi_small where every one has x <= 1; in instances that a handle takes unless ACG_BP_NO_PHISPLIT=1 is set at its
+ * creation; same results) against the full evaluation on every non-negative fp32 bit pattern, in the kernels'
+ * log2(e)-scaled domain.  out: 6 uint32 = patterns in
+ * [2, 66) / (0, 1] whose series does not give phi's bits; the smallest such pattern (all ones: none); the bits of the largest
+ * finite x with ps >= pl; of the smallest x > 0 with pl >= ps; patterns where max(ps, pl) behind the saturation select does not
+ * give phi's bits; the smallest such pattern. */
+int acg_ldpc_debug_phi_split(uint32_t *out_host);
 /* diagnostics: counters of the fixed-work fused sum-product kernels' freeze path (a latched frame whose message state recurs
  * bit for bit stops sweeping; outputs are those of max_iter sweeps; ACG_BP_NO_FREEZE=1 at handle creation runs every sweep).
  * Waits for the handle's launches, returns what they counted since the previous call (frames frozen; sweeps those frames did

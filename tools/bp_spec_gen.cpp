@@ -2,11 +2,11 @@
 // the fused fixed-work sum-product kernel with the code's pass structure as compile-time constants (bp_core.inc, static pass
 // policy).  Host only; csrc/Makefile builds and runs it:
 //   g++ -O2 -std=c++17 -Iinclude tools/bp_spec_gen.cpp acg_alp_ldpc_amd/csrc/code.cpp -o bp_spec_gen
-//   bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] <matrix.txt>[:L] ...
+//   bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] [-r c|v:<pass>:<row>]... <matrix.txt>[:L] ...
 //                                                                     (L = 16, 32 or 64; 0 or none: the library's own choice)
 // Per pair it calls bp_layout_build the way the handle set-up does (absorbed degree-1 variables included) and writes
 //   namespace spec_<name> { struct Pass (the constexpr tables); the kernel bp_fused_kernel<...>; the signature arrays }
-// and one line of the registry macro ACG_BP_SPEC_ENTRIES: name, L, signature, kernel pointers (MC off / on).  <name> is the
+// and one line of the registry macro ACG_BP_SPEC_ENTRIES: name, L, signature, kernel pointers (MC off / on, then MC off of the instance with the one-series phi).  <name> is the
 // file's base name and the group width, e.g. H05_L32.  A pair whose layout does not take the fp32 sum-product, degree <= 8,
 // register-LLR fixed-work path is skipped with a message.  --print: the structure of every accepted pair as plain lines on
 // stdout (name / c_pass / v_pass / c_cnt_ge / v_cnt_ge / n_apass), the histograms as the layout holds them.
@@ -15,6 +15,11 @@
 // -2) and clears the bit of every row whose share of fully skipped units is below -t per cent (default: SAT_ROWS_T below).  -t 0
 // keeps every test without running the census, -t 101 clears all.  The masks, the SNR and the threshold stand in the include as a
 // comment, as the two look-ups and as the registry's sat_rows string.
+// A second pair of look-ups, c_split_rows / v_split_rows, says which rows take the one-series phi where the wavefront allows
+// (BpPass::word_c / word_v, SPLIT): every row, unless -r c:<pass>:<row> or -r v:<pass>:<row> (repeatable) clears one for a
+// measured build.  Pass and row numbers are a code's own, so -r is meant for a run with one code; it is applied to every listed
+// code and refused where a code has no such row.  The masks stand in the registry as split_rows.  Results do not depend on
+// either pair.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -72,15 +77,25 @@ int main(int argc, char **argv) {
     bool print = false;
     double snr = -2.0, thr = SAT_ROWS_T;
     std::vector<std::string> pairs;
+    struct Clear { char side; int pass, row; };
+    std::vector<Clear> clears;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-o") && i + 1 < argc) out_path = argv[++i];
         else if (!strcmp(argv[i], "--print")) print = true;
         else if (!strcmp(argv[i], "-s") && i + 1 < argc) snr = atof(argv[++i]);
         else if (!strcmp(argv[i], "-t") && i + 1 < argc) thr = atof(argv[++i]);
+        else if (!strcmp(argv[i], "-r") && i + 1 < argc) {
+            Clear c{};
+            if (sscanf(argv[++i], "%c:%d:%d", &c.side, &c.pass, &c.row) != 3 || (c.side != 'c' && c.side != 'v') || c.pass < 0 || c.row < 0 || c.row > 31) {
+                fprintf(stderr, "bp_spec_gen: -r takes c:<pass>:<row> or v:<pass>:<row>, not %s\n", argv[i]);
+                return 2;
+            }
+            clears.push_back(c);
+        }
         else pairs.push_back(argv[i]);
     }
     if (pairs.empty() && !out_path) {
-        fprintf(stderr, "usage: bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] <matrix.txt>[:L] ...\n");
+        fprintf(stderr, "usage: bp_spec_gen [-o out.inc] [--print] [-s <dB>] [-t <per cent>] [-r c|v:<pass>:<row>]... <matrix.txt>[:L] ...\n");
         return 2;
     }
     std::string text = "// generated by tools/bp_spec_gen.cpp from SPEC_CODES (csrc/Makefile): do not edit, do not commit\n";
@@ -150,16 +165,35 @@ int main(int argc, char **argv) {
         text += "    // rows that keep their phi fast-path test (bit j = edge row j of the pass): census at " + std::string(snr_s) + "dB, threshold " + thr_s +
                 " per cent of fully skipped units\n    // " + rows_str + "\n";
         text += ulookup("c_sat_rows", rows.c) + ulookup("v_sat_rows", rows.v);
+        // rows that take the one-series phi where their unit allows
+        std::vector<uint32_t> split_c((size_t) s.n_cpass, ~0u), split_v((size_t) s.n_vpass, ~0u);
+        for (const Clear &cl : clears) {
+            std::vector<uint32_t> &m = cl.side == 'c' ? split_c : split_v;
+            const std::vector<int32_t> &pt = cl.side == 'c' ? s.c_pass : s.v_pass;
+            if ((size_t) cl.pass >= m.size() || cl.row >= pt[2 * (size_t) cl.pass]) {
+                fprintf(stderr, "bp_spec_gen: -r %c:%d:%d: %s has no such row\n", cl.side, cl.pass, cl.row, name.c_str());
+                return 2;
+            }
+            m[(size_t) cl.pass] &= ~(1u << cl.row);
+        }
+        const std::string split_str = "c:" + hexlist(split_c, s.c_pass) + "/v:" + hexlist(split_v, s.v_pass);
+        text += "    // rows that take the one-series phi where the wavefront allows (bit j = edge row j of the pass)\n    // " + split_str + "\n";
+        text += ulookup("c_split_rows", split_c) + ulookup("v_split_rows", split_v);
         text += "};\n";
         text += "template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>\n"
                 "__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {\n"
                 "    bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, true, Pass>(t, a);\n}\n";
+        text += "namespace split {\n"
+                "template <typename T, int MAXD, int L, int ALGO, bool MC, bool IDXLDS, int NVP, bool DBG = false>\n"
+                "__global__ void __launch_bounds__(256, (bp_min_waves<T, MAXD, L, NVP>())) bp_fused_kernel(const BpTables t, const DecodeArgs a) {\n"
+                "    bp_fused_body<T, MAXD, L, ALGO, MC, IDXLDS, NVP, DBG, true, Pass, true>(t, a);\n}\n}  // namespace split (the one-series phi; ACG_BP_NO_PHISPLIT=1: the kernel above)\n";
         text += host("sig_c_pass", s.c_pass) + host("sig_v_pass", s.v_pass) + host("sig_c_cnt_ge", s.c_cnt_ge) + host("sig_v_cnt_ge", s.v_cnt_ge);
         text += "}  // namespace " + ns + "\n";
         const std::string k = "(const void *) " + ns + "::bp_fused_kernel<float, 8, " + std::to_string(L) + ", 0, ";
+        const std::string ks = "(const void *) " + ns + "::split::bp_fused_kernel<float, 8, " + std::to_string(L) + ", 0, ";
         entries += " \\\n    {{\"" + name + "\", " + std::to_string(L) + ", " + std::to_string(s.n_cpass) + ", " + std::to_string(s.n_apass) + ", " +
-                   std::to_string(s.n_vpass) + ", " + ns + "::sig_c_pass, " + ns + "::sig_v_pass, " + ns + "::sig_c_cnt_ge, " + ns + "::sig_v_cnt_ge, \"" + rows_str + "\"}, {" + k +
-                   "false, true, BP_NVP>, " + k + "true, true, BP_NVP>}},";
+                   std::to_string(s.n_vpass) + ", " + ns + "::sig_c_pass, " + ns + "::sig_v_pass, " + ns + "::sig_c_cnt_ge, " + ns + "::sig_v_cnt_ge, \"" + rows_str + "\", \"" + split_str + "\"}, {" + k +
+                   "false, true, BP_NVP>, " + k + "true, true, BP_NVP>, " + ks + "false, true, BP_NVP>}},";
     }
     text += "\n#define ACG_BP_SPEC_ENTRIES" + entries + "\n";
     if (out_path) {
