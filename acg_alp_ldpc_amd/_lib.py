@@ -90,6 +90,7 @@ SYMBOLS = {
     "acg_ldpc_debug_quantize": (C.c_int, [_vp, _i32, _i64, _f64, C.POINTER(Quant), _vp]),
     "acg_ldpc_quantize_dev": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp]),
     "acg_ldpc_decode_batch_q_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_decoder_create_quantized_streamed": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(Quant), C.POINTER(_vp)]),
     "acg_ldpc_decode_batch_q": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "acg_ldpc_osd_decode_batch_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "acg_ldpc_osd_decode_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
@@ -133,6 +134,7 @@ SYMBOLS = {
     "acg_ldpc_debug_layers": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_block": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_wide": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
+    "acg_ldpc_debug_layers_any": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_phi": (C.c_int, [_vp, _vp, _i32, _i32]),
     "acg_ldpc_debug_phi_sat": (C.c_int, [_vp, _vp, _i32]),
     "acg_ldpc_debug_phi_split": (C.c_int, [_vp]),

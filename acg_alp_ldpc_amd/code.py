@@ -81,6 +81,15 @@ class ParityCheckMatrix:
         check(lib().acg_ldpc_debug_layers_wide(self._h, C.byref(nl), C.byref(w), C.byref(Z), chk.ctypes.data, chk.size))
         return Z.value, chk
 
+    def layers_any(self):
+        """the sets of layers_block() without a bound on the check degree: the order in which StreamedQuantizedMinSumDecoder takes
+        the checks, set by set (acg_ldpc_debug_layers_any); the same rule and the same return value"""
+        nl, w, Z = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib().acg_ldpc_debug_layers_any(self._h, C.byref(nl), C.byref(w), C.byref(Z), None, 0))
+        chk = np.full((nl.value, w.value), -1, dtype=np.int32)
+        check(lib().acg_ldpc_debug_layers_any(self._h, C.byref(nl), C.byref(w), C.byref(Z), chk.ctypes.data, chk.size))
+        return Z.value, chk
+
     def is_codeword(self, bits):
         b = np.ascontiguousarray(bits, dtype=np.uint8)
         assert b.shape[-1] == self.n

@@ -586,6 +586,89 @@ static int quant_params_check(const acg_ldpc_params &p) {
     return 0;
 }
 
+// what acg_ldpc_decoder_create_quantized_streamed requires of the params (include/acg_ldpc.h); host only
+static int streamq_params_check(const acg_ldpc_params &p) {
+    const char *why = nullptr;
+    if (p.algo != ACG_LDPC_BP_MINSUM) why = "algo must be ACG_LDPC_BP_MINSUM";
+    else if (p.schedule != ACG_LDPC_SCHEDULE_LAYERED) why = "schedule must be ACG_LDPC_SCHEDULE_LAYERED";
+    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (the number formats are the quantiser's)";
+    else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_STREAMED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (the state lives in device memory)";
+    else if (p.lanes_per_frame != 0) why = "lanes_per_frame must be 0 (one lane is one frame)";
+    if (why) {
+        set_error(std::string("streamed quantized layered min-sum: ") + why);
+        return 3;
+    }
+    return 0;
+}
+
+// Streamed fixed-point layered min-sum (bp_streamed_q.hip): a quantized handle whose frames live in slabs of device memory, one
+// per resident tile.  Any n, m, E and any check degree: the checks are the sets of bp_layered_block_build without a degree cap,
+// set by set, as a plain CSR.
+static int decoder_setup_streamq(acg_ldpc_decoder *d) {
+    const Code &c = d->c;
+    if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
+    const LayeredBlockLayout &ll = d->lblay;
+    std::vector<int32_t> row_ptr, edge_var;
+    row_ptr.reserve((size_t) c.m + 1);
+    edge_var.reserve((size_t) c.E);
+    row_ptr.push_back(0);
+    for (int k = 0; k < ll.n_sets; k++) {
+        const int cnt = ll.set[3 * k + 2];
+        for (int i = 0; i < cnt; i++) {
+            const int r = ll.chk[(size_t) k * ll.width + i];
+            edge_var.insert(edge_var.end(), c.edge_var.begin() + c.row_ptr[r], c.edge_var.begin() + c.row_ptr[r + 1]);
+            row_ptr.push_back((int32_t) edge_var.size());
+        }
+    }
+    StreamQTables &t = d->sqtab;
+    if (!(t.row_ptr = upload_keep(row_ptr, d->dev_allocs))) return 10;
+    if (!(t.edge_var = upload_keep(edge_var, d->dev_allocs))) return 10;
+    t.m = (int32_t) row_ptr.size() - 1;
+    t.n = c.n;
+    t.E = (int32_t) edge_var.size();
+    t.nwords = (c.n + 31) / 32;
+    const void *kp = bp_streamed_q_kernel_ptr();
+    const int T = 64;   // one lane is one frame
+    const size_t per_frame = 2 * (size_t) c.n + (size_t) t.E;
+    const size_t slab = (per_frame * T + 255) & ~(size_t) 255;
+    t.slab_bytes = (int64_t) slab;
+    // tiles: the resident wavefronts of the kernel, at most 12 per CU (measured on frames that never latch, 4 / 8 / 12 / 16 / 20 per
+    // CU: 386 / 576 / 762 / 780 / 770 k frames/s on the (3,6) 5000 x 10000, 153 / 233 / 223 / 223 from 8 on the 2050 x 41000 of
+    // degree 40), as many as a quarter of the free memory holds, and no more than ACG_STREAMQ_TILES (developer
+    // switch: tests force the reuse of a slab)
+    int occ = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, 64, 0));
+    int64_t tiles = (int64_t) std::max(1, std::min(occ, 12)) * d->cu_count;
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const int64_t fit = (int64_t) (free_b / 4 / slab);
+    if (fit < 1) {
+        set_error("streamed quantized layered min-sum: not one tile of " + std::to_string(T) + " frames (" + std::to_string(slab) +
+                  " bytes) fits in a quarter of the device's free memory (" + std::to_string(free_b / 4) + " bytes)");
+        return 3;
+    }
+    tiles = std::min(tiles, fit);
+    if (const char *e = getenv("ACG_STREAMQ_TILES")) {
+        const long want = atol(e);
+        if (want >= 1) tiles = std::min<int64_t>(tiles, want);
+    }
+    if (int rc = d->sq_ws.reserve((size_t) tiles * slab)) return rc;
+    d->streamq = true;
+    d->sq_tiles = (int) tiles;
+    d->layered_wg = acg_ldpc_decoder::LayeredWg::q;   // a quantized handle: the integer entrances and the unfused Monte-Carlo route take it
+    d->qargs = quant_args(d->quant);
+    d->kernel[0] = kp;
+    d->kernel[1] = nullptr;
+    d->L = 1;
+    d->f64 = 0;
+    d->block = 64;
+    d->frames_per_block = T;
+    d->lds_block = 0;
+    d->grid_cap[0] = d->grid_cap[1] = (int) tiles;
+    d->tab.lds_bytes_per_frame = 0;
+    return 0;
+}
+
 // schedule = LAYERED: min-sum over conflict-free layers of checks with in-place posteriors (bp_layered.hip)
 static int decoder_setup_layered(acg_ldpc_decoder *d) {
     const Code &c = d->c;
@@ -935,7 +1018,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
 }
 
 int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                      hipStream_t on_stream, const acg_ldpc_quant *quant) {
+                                      hipStream_t on_stream, const acg_ldpc_quant *quant, bool q_streamed) {
     if (!code || !params || !out) {
         set_error("null argument");
         return 1;
@@ -946,8 +1029,8 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
     }
     if (quant) {   // (host-only refusals first: they need no device)
         if (int rc = quant_check(quant)) return rc;
-        if (int rc = quant_params_check(*params)) return rc;
-        if (code->c.max_cdeg > 32) {
+        if (int rc = q_streamed ? streamq_params_check(*params) : quant_params_check(*params)) return rc;
+        if (!q_streamed && code->c.max_cdeg > 32) {
             set_error("quantized layered min-sum: check degree above 32 is not supported");
             return 3;
         }
@@ -999,7 +1082,7 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
         if (quant) {
             d->name = "QMS";
             d->quant = *quant;
-            rc = decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::q, d->p.lanes_per_frame);
+            rc = q_streamed ? decoder_setup_streamq(d) : decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::q, d->p.lanes_per_frame);
         } else if (params->algo == ACG_LDPC_QPADMM) {
             d->name = "QP-ADMM";  // qp_admm.h:189
             std::string err;
@@ -1053,6 +1136,17 @@ int acg_ldpc_decoder_create_quantized(const acg_ldpc_code *code, const acg_ldpc_
     });
 }
 
+int acg_ldpc_decoder_create_quantized_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
+                                               acg_ldpc_decoder **out) {
+    return guarded([&] {
+        if (!q) {
+            set_error("null argument");
+            return 1;
+        }
+        return acg_ldpc_decoder_create_impl(code, params, out, nullptr, q, true);
+    });
+}
+
 void acg_ldpc_decoder_destroy(acg_ldpc_decoder *d) {
     if (!d) return;
     (void) hipSetDevice(d->device);
@@ -1079,7 +1173,7 @@ void acg_ldpc_decoder_layout(const acg_ldpc_decoder *d, int32_t *lds_bytes_per_f
         admm_device_layout(d->admm.get(), lds_bytes_per_frame, lanes_per_frame, frames_per_block, grid_blocks);
         return;
     }
-    if (lds_bytes_per_frame) *lds_bytes_per_frame = d->streamed ? 0 : d->tab.lds_bytes_per_frame;
+    if (lds_bytes_per_frame) *lds_bytes_per_frame = d->streamed || d->streamq ? 0 : d->tab.lds_bytes_per_frame;
     if (lanes_per_frame) *lanes_per_frame = d->L;
     if (frames_per_block) *frames_per_block = d->frames_per_block;
     if (grid_blocks) *grid_blocks = d->grid_cap[0];
@@ -1121,6 +1215,14 @@ static std::string describe(const acg_ldpc_decoder *d) {
             }
             return t;
         }
+    } else if (d->streamq) {
+        const acg_ldpc_quant &q = d->quant;
+        snprintf(b, sizeof b, "%s engine=streamed kernel=bp_streamed_q_kernel schedule=layered T=%d tiles=%d state_bytes_per_frame=%zu "
+                               "slab_bytes=%lld workspace_bytes=%zu workspace=hipMalloc sets=%d checks=%d messages=int8 posteriors=int16 "
+                               "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d mc_quants=refused",
+                 algo, d->frames_per_block, d->sq_tiles, 2 * (size_t) d->c.n + (size_t) d->sqtab.E, (long long) d->sqtab.slab_bytes,
+                 (size_t) d->sq_tiles * (size_t) d->sqtab.slab_bytes, d->lblay.n_sets, d->sqtab.m, q.llr_step, q.ch_bits, q.msg_bits, q.post_bits,
+                 q.scale_num, q.scale_shift, q.offset);
     } else if (d->layered_wg == acg_ldpc_decoder::LayeredWg::q) {
         const acg_ldpc_quant &q = d->quant;
         snprintf(b, sizeof b, "%s engine=fused kernel=bp_layered_q_kernel lanes_per_frame=%d f64=0 block=%d frames_per_block=1 lds_block=%zu "

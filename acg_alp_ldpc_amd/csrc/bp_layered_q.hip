@@ -32,6 +32,7 @@
 #include <algorithm>
 
 #include "launchers.hpp"
+#include "quant_arith.hpp"
 
 namespace acg {
 
@@ -54,40 +55,12 @@ __device__ __forceinline__ int quantize_symbol(const DecodeArgs &a, const QuantA
     return (int) __builtin_fminf(__builtin_fmaxf(__builtin_rintf(t), -cm), cm);
 }
 
-// mu -> max(((mu * scale_num + rnd) >> scale_shift) - offset, 0)
-__device__ __forceinline__ int q_normalise(const int mu, const QuantArgs &qa) {
-    const int v = ((mu * qa.scale_num + qa.rnd) >> qa.scale_shift) - qa.offset;
-    return v > 0 ? v : 0;
-}
-
-// The arithmetic of a check, ONE definition for both forms of q_layer_step: what pass 1 gathers over the edges, and what an edge
-// becomes once all of them have been seen.
-struct QCheck {
-    int m1, m2;             // the two smallest min(|q|, rmax); both start at rmax — every a_j <= rmax, so the two smallest of {a_j}
-                            // and two rmax ARE the two smallest a_j, and a check of one variable gets m2 = rmax
-    uint32_t parity, S;     // bit 0: XOR of (P < 0) and of (q < 0) over the edges
-    int mu1, mu2;           // normalised m1, m2 (q_close)
-};
-__device__ __forceinline__ void q_open(QCheck &c, const QuantArgs &qa) {
-    c.m1 = c.m2 = qa.rmax;
-    c.parity = c.S = 0;
-}
-__device__ __forceinline__ void q_reduce(QCheck &c, const int p, const int q, const QuantArgs &qa) {
-    c.parity ^= (uint32_t) p >> 31;
-    c.S ^= (uint32_t) q >> 31;
-    const int m = min(abs(q), qa.rmax);
-    c.m2 = min(c.m2, max(m, c.m1));
-    c.m1 = min(c.m1, m);
-}
-__device__ __forceinline__ void q_close(QCheck &c, const QuantArgs &qa) {
-    c.mu1 = q_normalise(c.m1, qa);
-    c.mu2 = q_normalise(c.m2, qa);
-}
+// The arithmetic of a check (quant_arith.hpp: QCheck, q_open / q_reduce / q_close / q_update) is ONE definition for both forms
+// of q_layer_step, and for the streamed engine (bp_streamed_q.hip).
 // the edge with posterior p and q = p - r: new message and posterior into their cells -> bit 0: its hard decision flipped
 __device__ __forceinline__ uint32_t q_edge(const QCheck &c, const int p, const int q, const QuantArgs &qa, short *const pc, signed char *const rc) {
-    const int mag = (min(abs(q), qa.rmax) == c.m1) ? c.mu2 : c.mu1;   // a tie makes m2 == m1: either answer is the same
-    const int rn = ((c.S ^ ((uint32_t) q >> 31)) & 1u) ? -mag : mag;
-    const int pn = min(max(q + rn, -qa.pmax), qa.pmax);
+    int rn, pn;
+    q_update(c, q, qa, rn, pn);
     *pc = (short) pn;
     *rc = (signed char) rn;
     return ((uint32_t) pn >> 31) ^ ((uint32_t) p >> 31);

@@ -193,6 +193,10 @@ int acg_ldpc_debug_layers_wide(const acg_ldpc_code *code, int32_t *n_layers, int
     return debug_layers_block(code, 32, n_layers, width, qc_Z, chk, cap);
 }
 
+int acg_ldpc_debug_layers_any(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap) {
+    return debug_layers_block(code, INT32_MAX, n_layers, width, qc_Z, chk, cap);
+}
+
 int acg_ldpc_debug_layers(const acg_ldpc_code *code, int32_t *lanes, int32_t *n_layers, int32_t *qc_Z, int32_t *chk, int64_t cap) {
     return guarded([&]() -> int {
         if (!code) {

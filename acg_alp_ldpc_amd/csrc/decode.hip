@@ -97,7 +97,7 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
 int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid) {
-    if (qio && d->osd ? qio->post_out != nullptr : qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qio)) {
+    if (qio && d->osd ? qio->post_out != nullptr : qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || (!d->kernel_qio && !d->streamq))) {
         set_error("internal: channel values handed to a decoder that is not quantized");
         return 11;
     }
@@ -115,7 +115,7 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
     if (d->ring_used[slot]) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[slot], 0));
     // engines whose HBM workspace belongs to the handle (streamed BP, streamed QP-ADMM): a launch on another stream waits
     // (and the snapshot slots of the fused kernels' freeze path)
-    const bool owns_ws = d->streamed || d->freeze || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
+    const bool owns_ws = d->streamed || d->streamq || d->freeze || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
     if (owns_ws && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
     a.work_counter = d->work_counter(slot);
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
@@ -155,6 +155,38 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
             HIP_OK(bp_streamed_ring_launch(kp, d->stab, a, (uint32_t *) d->sws.va, grid, s));
         } else {
             HIP_OK(bp_streamed_launch(d->skernel, d->stab, a, (uint32_t *) d->sws.va, grid, W * 64, s));
+        }
+    } else if (d->streamq) {
+        if (a.mc) {
+            set_error("internal: the streamed quantized engine has no in-kernel generator");
+            return 11;
+        }
+        const int T = d->frames_per_block;
+        QuantArgs q = d->qargs;
+        if (qio) {
+            q.c_in = qio->c_in;
+            q.post_out = qio->post_out;
+            const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sq_tiles);
+            HIP_OK(bp_streamed_q_launch(d->kernel[0], d->sqtab, a, q, d->sq_ws.as<unsigned char>(), grid, s));
+        } else {
+            // the symbol entrance: the handle's quantiser into its staging buffer, then the integer path, a residency of tiles at a time
+            const int64_t chunk = std::min<int64_t>(a.frames, (int64_t) d->sq_tiles * T);
+            const size_t n = (size_t) d->c.n, nwords = (n + 31) / 32;
+            if (int rc = d->sq_stage.reserve((size_t) chunk * n * sizeof(int16_t))) return rc;
+            q.c_in = d->sq_stage.as<int16_t>();
+            q.post_out = nullptr;
+            for (int64_t f0 = 0; f0 < a.frames; f0 += chunk) {
+                DecodeArgs ac = a;
+                ac.frames = std::min(chunk, a.frames - f0);
+                ac.y = static_cast<const unsigned char *>(a.y) + (size_t) f0 * n * (a.y_is_f64 ? 8 : 4);
+                if (a.out_bits) ac.out_bits = a.out_bits + (size_t) f0 * nwords;
+                if (a.out_ok) ac.out_ok = a.out_ok + f0;
+                if (a.out_iters) ac.out_iters = a.out_iters + f0;
+                if (f0 > 0) HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));   // (the chunks share the launch's counter)
+                HIP_OK(quantize_debug_launch(ac, q, ac.frames * (int64_t) n, d->sq_stage.as<int16_t>(), s));
+                const int grid = (int) std::min<int64_t>((ac.frames + T - 1) / T, d->sq_tiles);
+                HIP_OK(bp_streamed_q_launch(d->kernel[0], d->sqtab, ac, q, d->sq_ws.as<unsigned char>(), grid, s));
+            }
         }
     } else if (d->osd) {
         if (a.mc) {

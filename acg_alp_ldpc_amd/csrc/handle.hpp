@@ -177,6 +177,13 @@ struct acg_ldpc_decoder {
     acg::LayeredBlockLayout lblay;
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
+    // streamed fixed-point layered min-sum (bp_streamed_q.hip; handles of acg_ldpc_decoder_create_quantized_streamed only): a
+    // quantized handle (layered_wg == q, quant, qargs, the sets in lblay) whose frames live in the slabs of sq_ws, one per resident
+    // tile of 64 frames.  sq_stage: the symbol entrance's int16 channel values of the frames in flight.
+    bool streamq = false;
+    acg::StreamQTables sqtab{};
+    int sq_tiles = 0;
+    acg::DeviceBuf sq_ws, sq_stage;
     // ordered-statistics decoding (osd.hip; algo = ACG_LDPC_OSD): the packed column table, and what the kernel reads.  One kernel
     // for both entrances (OsdArgs::s_in set per launch); decode only: Monte-Carlo runs take the unfused route.
     bool osd = false;
@@ -277,9 +284,10 @@ struct acg_ldpc_cascade {
 namespace acg {
 
 // ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own;
-// quant != null: the fixed-point layered min-sum engine of acg_ldpc_decoder_create_quantized) ----
+// quant != null: the fixed-point layered min-sum engine of acg_ldpc_decoder_create_quantized, or with q_streamed the one of
+// acg_ldpc_decoder_create_quantized_streamed) ----
 int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                 hipStream_t on_stream = nullptr, const acg_ldpc_quant *quant = nullptr);
+                                 hipStream_t on_stream = nullptr, const acg_ldpc_quant *quant = nullptr, bool q_streamed = false);
 QuantArgs quant_args(const acg_ldpc_quant &q);
 
 // ---- decode.hip ----

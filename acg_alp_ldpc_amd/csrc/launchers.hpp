@@ -93,6 +93,12 @@ hipError_t bp_layered_wg_launch(const void *kernel, const LayerBlockTables &t, c
 // the kernel's quantiser on `count` symbols (a: y, y_is_f64 and the channel terms) -> count int16
 hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_t count, int16_t *out, hipStream_t s);
 
+// ---- bp_streamed_q.hip: streamed fixed-point layered min-sum, a wavefront per tile of 64 frames ----
+const void *bp_streamed_q_kernel_ptr();
+// q: the quantiser with c_in set (and post_out, or null); ws: grid slabs of t.slab_bytes
+hipError_t bp_streamed_q_launch(const void *kernel, const StreamQTables &t, const DecodeArgs &a, const QuantArgs &q, unsigned char *ws,
+                                int grid, hipStream_t s);
+
 // ---- osd.hip: ordered-statistics decoding, one workgroup of L = 64, 128 or 256 threads per frame ----
 const void *osd_kernel_ptr(int L);
 size_t osd_lds_bytes(int n, int m);   // dynamic LDS of a workgroup

@@ -599,6 +599,10 @@ static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cf
         set_error("acg_ldpc_mc_run_quants: n_points must be >= 1");
         return 1;
     }
+    if (d->streamq) {
+        set_error("acg_ldpc_mc_run_quants: the streamed quantized engine has no grid form (use a decoder of acg_ldpc_decoder_create_quantized)");
+        return 3;
+    }
     if (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || !d->kernel_qgrid) {
         set_error("acg_ldpc_mc_run_quants needs a decoder of acg_ldpc_decoder_create_quantized");
         return 3;

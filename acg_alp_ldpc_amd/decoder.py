@@ -4,6 +4,7 @@
     QPADMMDecoder(alpha, mu, max_iter=2000, eps_stop=1e-5) algo/qp_admm.h:180-194
     MinSumDecoder(max_iter, scale)                         build-added, not in the reference
     QuantizedMinSumDecoder(max_iter, quant)                build-added, not in the reference: fixed-point layered min-sum
+    StreamedQuantizedMinSumDecoder(max_iter, quant)        build-added: the same decoder, state in device memory, any code
     OSDDecoder(order=1)                                    build-added, not in the reference: ordered-statistics decoding
 
     decode(H, channel_word, snr) -> (codeword, ok)         same argument meaning as algo/algo.h:8:
@@ -383,6 +384,21 @@ class QuantizedMinSumDecoder(Decoder):
         """device pointers (ints): `count` symbols -> `count` int16 channel values; asynchronous on `stream`"""
         with self._lease(H) as (h, _):
             check(lib().acg_ldpc_quantize_dev(h, y_ptr, 1 if y_is_f64 else 0, int(count), float(snr), c_ptr, stream))
+
+
+class StreamedQuantizedMinSumDecoder(QuantizedMinSumDecoder):
+    """Build-added (acg_ldpc_decoder_create_quantized_streamed; not in the reference): QuantizedMinSumDecoder with a frame's state in
+    device memory instead of LDS — one lane per frame, 2 n + E bytes per frame — for the codes that one refuses: any size, any
+    check degree.  Word, flag, iteration and posterior of every frame are equal on every code both accept, and a code whose
+    frame fits in LDS is decoded faster there.  Bit-true: tests/streamed_q_ref.py restates it.  The same methods; lanes_per_frame
+    must stay 0 and engine ENGINE_AUTO or ENGINE_STREAMED.  CascadeDecoder and run_experiment_quants build and need the LDS engine."""
+
+    def _key(self, H):
+        return super()._key(H) + ("streamed",)
+
+    def _create(self, code, p, h):
+        q = self.quant.as_struct()
+        return lib().acg_ldpc_decoder_create_quantized_streamed(code._h, C.byref(p), C.byref(q), C.byref(h))
 
 
 class OSDDecoder(Decoder):

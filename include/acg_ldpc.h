@@ -167,7 +167,7 @@ int acg_ldpc_code_is_codeword(const acg_ldpc_code *code, const uint8_t *bits);
 int acg_ldpc_decoder_create(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out);
 void acg_ldpc_decoder_destroy(acg_ldpc_decoder *dec);
 /* replaces Decoder::name() (algo/algo.h:10): "BP" (bp.h:218), "QP-ADMM" (qp_admm.h:189), "MS"; "QMS" for a handle of
- * acg_ldpc_decoder_create_quantized */
+ * acg_ldpc_decoder_create_quantized or acg_ldpc_decoder_create_quantized_streamed */
 const char *acg_ldpc_decoder_name(const acg_ldpc_decoder *dec);
 
 /* ---- fixed-point layered min-sum (build-added; not in the reference) ------------------------ */
@@ -233,7 +233,7 @@ int acg_ldpc_debug_quantize(const void *y_host, int32_t y_is_f64, int64_t count,
  *                      word is formed — with early_exit = 0 the frame is swept on, the posterior written is still the latched
  *                      one; for a frame that fails, the posteriors after max_iter iterations (its word is zeros as everywhere);
  *                      for max_iter = 0 the clamped channel value.  So (post < 0) is the word of every frame with ok = 1.
- * All three take a handle of acg_ldpc_decoder_create_quantized only.  Each returns non-zero, leaves a message in
+ * All three take a handle of acg_ldpc_decoder_create_quantized or acg_ldpc_decoder_create_quantized_streamed only.  Each returns non-zero, leaves a message in
  * acg_ldpc_last_error and launches nothing for a null handle, a handle of acg_ldpc_decoder_create, frames (count) < 0, or
  * frames (count) > 0 with a null input (the host call: also null bits or ok).  frames == 0 is a no-op that returns 0. */
 
@@ -249,6 +249,35 @@ int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *dec, const int16_t *c_dev, int
  * when post is given); post may be NULL */
 int acg_ldpc_decode_batch_q(acg_ldpc_decoder *dec, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
                             int16_t *post);
+
+/* ---- streamed fixed-point layered min-sum: any code size, any check degree (build-added) ---- */
+
+/* The arithmetic, schedule, stopping rule, latching, final syndrome pass and iteration count of acg_ldpc_decoder_create_quantized
+ * — word, flag, iteration and posterior of every frame are equal on every code both accept — with a frame's state in device
+ * memory instead of LDS (bp_streamed_q_kernel): one lane is one frame, a wavefront owns a tile of T frames and walks the edges
+ * of a check in a loop, so neither the size of a frame nor the degree of a check is bounded.  State of a frame: 2 n + E bytes
+ * (int16 posteriors, one byte per edge).  The checks are taken in the order of the sets acg_ldpc_debug_layers_any reports,
+ * set by set.  tests/streamed_q_ref.py restates it.
+ * Required of *params, anything else is refused with a message before a device is looked for:
+ *   algo = ACG_LDPC_BP_MINSUM, schedule = ACG_LDPC_SCHEDULE_LAYERED, precision = ACG_LDPC_PREC_DEFAULT,
+ *   engine = ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (ACG_LDPC_ENGINE_FUSED is refused), lanes_per_frame = 0,
+ *   and a *q that acg_ldpc_quant_check accepts.  ms_scale is ignored as above.
+ * Workspace: one allocation of tiles x (T (2 n + E) bytes, rounded up to 256), T = 64, tiles = min(12 per compute unit, what fits
+ * in a quarter of the device's free memory); creation fails with a message when not one tile fits.  ACG_STREAMQ_TILES=<count>
+ * (developer switch, read at creation) lowers the tile count.  The symbol entrances quantise into a staging buffer of the handle
+ * (2 n bytes per frame, at most tiles x T frames at a time) and run the integer path.
+ * The handle is an ordinary quantized handle: acg_ldpc_decode_batch, _f32, _dev, acg_ldpc_decode_batch_q, _q_dev and
+ * acg_ldpc_quantize_dev take it; acg_ldpc_mc_run and _detail go noise kernel -> decode -> classification kernel;
+ * acg_ldpc_mc_run_quants and acg_ldpc_mc_run_grid refuse it with a message.  The workspace belongs to the handle, so launches
+ * of one handle on different streams are ordered on the device.  acg_ldpc_decoder_name returns "QMS"; acg_ldpc_decoder_layout
+ * reports as for the streamed engines (no LDS bytes, one lane per frame, T frames per block, tiles); acg_ldpc_decoder_describe
+ * names the kernel, T, the tiles, the bytes of state per frame, the sets and the seven values of *q.
+ * A code whose frame fits in LDS is decoded faster by acg_ldpc_decoder_create_quantized: use this call for the codes that one
+ * refuses.
+ * Not provided: a cascade stage of this engine (acg_ldpc_cascade_create builds its own stages with the two create calls
+ * above), a grid form for acg_ldpc_mc_run_quants, float messages. */
+int acg_ldpc_decoder_create_quantized_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
+                                               acg_ldpc_decoder **out);
 
 /* ---- OSD: ordered-statistics decoding (Fossorier-Lin) of order 0 and 1 (build-added) ------ */
 
@@ -648,6 +677,11 @@ int acg_ldpc_debug_layers_block(const acg_ldpc_code *code, int32_t *n_layers, in
 /* diagnostics (host only, no device needed): the same sets by the same rule for the wide-check engine (bp_layered_wide_kernel):
  * the contract of acg_ldpc_debug_layers_block with check degree up to 32 (non-zero for a check degree above 32). */
 int acg_ldpc_debug_layers_wide(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap);
+
+/* diagnostics (host only, no device needed): the same sets by the same rule without a bound on the check degree — the order in
+ * which a handle of acg_ldpc_decoder_create_quantized_streamed takes the checks, set by set.  The contract of
+ * acg_ldpc_debug_layers_wide otherwise (non-zero only for a matrix without checks). */
+int acg_ldpc_debug_layers_any(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap);
 
 #ifdef __cplusplus
 }

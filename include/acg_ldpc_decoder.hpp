@@ -395,9 +395,24 @@ protected:
         return {TCodeword(bits.begin(), bits.end()), true};
     }
 
+    const acg_ldpc_quant &quant() const { return _quant; }
+
 private:
     int _max_iter, _lanes;
     acg_ldpc_quant _quant;
+};
+
+// build-added; not in the reference.  The same decoder with a frame's state in device memory
+// (acg_ldpc_decoder_create_quantized_streamed): any code size, any check degree, the same results on every code both accept.
+// A code whose frame fits in LDS is decoded faster by QuantizedMinSumDecoder.
+class StreamedQuantizedMinSumDecoder : public QuantizedMinSumDecoder {
+public:
+    explicit StreamedQuantizedMinSumDecoder(int max_iter, const acg_ldpc_quant &quant = default_quant()) : QuantizedMinSumDecoder(max_iter, quant, 0) {}
+
+protected:
+    int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
+        return acg_ldpc_decoder_create_quantized_streamed(code, &p, &quant(), out);
+    }
 };
 
 // build-added; not in the reference.  Ordered-statistics decoding of order 0 or 1 (acg_ldpc.h, "OSD"): one GF(2) elimination per

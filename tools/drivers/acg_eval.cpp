@@ -20,6 +20,10 @@
 //                         default 25) and osd (order --osd-order, default 1); qms,osd hands the posteriors over.
 //            [--osd-order K]   also evaluate ordered-statistics decoding of order K = 0 or 1 on the channel symbols (build-added;
 //                         weak on its own on these codes: it is meant as the second stage behind qms)
+//            [--qms-engine lds|streamed]   also evaluate the fixed-point layered min-sum on its own (default quantiser, --qms-iters N):
+//                         lds = acg_ldpc_decoder_create_quantized (a frame in LDS), streamed =
+//                         acg_ldpc_decoder_create_quantized_streamed (a frame in device memory: any code size, any check
+//                         degree).  One more block, Method = QMS; both engines give the same rows.
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -55,6 +59,11 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    const std::string qms_engine = a.get("--qms-engine", "");
+    if (a.has("--qms-engine") && qms_engine != "lds" && qms_engine != "streamed") {
+        std::fprintf(stderr, "acg_eval: --qms-engine lds or streamed\n");
+        return 2;
+    }
     acg_ldpc_code *code = nullptr;
     if (acg_ldpc_code_load_txt(hpath, &code)) drv::die("read_pcm");
     int m, n, E;
@@ -88,7 +97,7 @@ int main(int argc, char **argv) {
             p.ms_scale = a.num("--ms-scale", 0.75);
             if (a.has("--layered")) p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
             if (a.has("--ms-f16")) p.precision = ACG_LDPC_PREC_F16;
-        } else if (which == "qms") {  // build-added fixed-point layered min-sum, default quantiser (cascades only)
+        } else if (which == "qms") {  // build-added fixed-point layered min-sum, default quantiser (cascades, --qms-engine)
             p.algo = ACG_LDPC_BP_MINSUM;
             p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
             p.max_iter = (int) a.integer("--qms-iters", 25);
@@ -119,6 +128,13 @@ int main(int argc, char **argv) {
         params_of("osd", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
+    }
+    if (a.has("--qms-engine")) {
+        params_of("qms", p);
+        acg_ldpc_quant q;
+        acg_ldpc_quant_default(&q);
+        decs.emplace_back();
+        decs.back().create(code, p, gpus, ndev, &q, qms_engine == "streamed");
     }
     acg_ldpc_cascade *cascade = nullptr;
     if (a.has("--cascade")) {

@@ -158,11 +158,18 @@ inline std::vector<uint8_t> make_codewords(const acg_ldpc_code *code, const char
 struct MultiGpu {
     std::vector<acg_ldpc_decoder *> dec;
 
-    void create(const acg_ldpc_code *code, acg_ldpc_params p, int gpus, int device_count) {
+    // quant != null: the fixed-point layered min-sum engine with that quantiser, in LDS or (streamed) in device memory
+    void create(const acg_ldpc_code *code, acg_ldpc_params p, int gpus, int device_count, const acg_ldpc_quant *quant = nullptr,
+                bool streamed = false) {
         for (int k = 0; k < gpus; k++) {
             p.device = device_count > 0 ? k % device_count : -1;
             acg_ldpc_decoder *d = nullptr;
-            if (acg_ldpc_decoder_create(code, &p, &d)) die("acg_ldpc_decoder_create");
+            if (quant && streamed) {
+                if (acg_ldpc_decoder_create_quantized_streamed(code, &p, quant, &d)) die("acg_ldpc_decoder_create_quantized_streamed");
+            } else if (quant) {
+                if (acg_ldpc_decoder_create_quantized(code, &p, quant, &d)) die("acg_ldpc_decoder_create_quantized");
+            } else if (acg_ldpc_decoder_create(code, &p, &d))
+                die("acg_ldpc_decoder_create");
             dec.push_back(d);
         }
     }
