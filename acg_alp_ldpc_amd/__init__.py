@@ -10,7 +10,7 @@ from .channel import gen_random_codewords, llr, llr_variance, transmit_frames  #
 from .code import ParityCheckMatrix  # noqa: F401
 from .codes import regular_ldpc  # noqa: F401
 from .decoder import (BeliefPropagationDecoder, CascadeDecoder, Decoder, MinSumDecoder, OSDDecoder, QPADMMDecoder, QuantConfig,  # noqa: F401
-                      QuantizedMinSumDecoder, StreamedQuantizedMinSumDecoder)
+                      QuantizedMinSumDecoder, StreamedLayeredBPDecoder, StreamedLayeredMinSumDecoder, StreamedQuantizedMinSumDecoder)
 from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_cascade_results, merge_exp_details,  # noqa: F401
                          merge_exp_results, quant_structs, run_experiment, run_experiment_cascade, run_experiment_codes,
                          run_experiment_detail, run_experiment_grid, run_experiment_inproc, run_experiment_quants,

@@ -601,14 +601,8 @@ static int streamq_params_check(const acg_ldpc_params &p) {
     return 0;
 }
 
-// Streamed fixed-point layered min-sum (bp_streamed_q.hip): a quantized handle whose frames live in slabs of device memory, one
-// per resident tile.  Any n, m, E and any check degree: the checks are the sets of bp_layered_block_build without a degree cap,
-// set by set, as a plain CSR.
-static int decoder_setup_streamq(acg_ldpc_decoder *d) {
-    const Code &c = d->c;
-    if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
-    const LayeredBlockLayout &ll = d->lblay;
-    std::vector<int32_t> row_ptr, edge_var;
+// the checks of the streamed layered engines in processing order — the sets of `ll`, set by set — as a plain CSR
+static void streamed_layered_csr(const Code &c, const LayeredBlockLayout &ll, std::vector<int32_t> &row_ptr, std::vector<int32_t> &edge_var) {
     row_ptr.reserve((size_t) c.m + 1);
     edge_var.reserve((size_t) c.E);
     row_ptr.push_back(0);
@@ -620,6 +614,16 @@ static int decoder_setup_streamq(acg_ldpc_decoder *d) {
             row_ptr.push_back((int32_t) edge_var.size());
         }
     }
+}
+
+// Streamed fixed-point layered min-sum (bp_streamed_q.hip): a quantized handle whose frames live in slabs of device memory, one
+// per resident tile.  Any n, m, E and any check degree: the checks are the sets of bp_layered_block_build without a degree cap,
+// set by set, as a plain CSR.
+static int decoder_setup_streamq(acg_ldpc_decoder *d) {
+    const Code &c = d->c;
+    if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
+    std::vector<int32_t> row_ptr, edge_var;
+    streamed_layered_csr(c, d->lblay, row_ptr, edge_var);
     StreamQTables &t = d->sqtab;
     if (!(t.row_ptr = upload_keep(row_ptr, d->dev_allocs))) return 10;
     if (!(t.edge_var = upload_keep(edge_var, d->dev_allocs))) return 10;
@@ -657,6 +661,86 @@ static int decoder_setup_streamq(acg_ldpc_decoder *d) {
     d->sq_tiles = (int) tiles;
     d->layered_wg = acg_ldpc_decoder::LayeredWg::q;   // a quantized handle: the integer entrances and the unfused Monte-Carlo route take it
     d->qargs = quant_args(d->quant);
+    d->kernel[0] = kp;
+    d->kernel[1] = nullptr;
+    d->L = 1;
+    d->f64 = 0;
+    d->block = 64;
+    d->frames_per_block = T;
+    d->lds_block = 0;
+    d->grid_cap[0] = d->grid_cap[1] = (int) tiles;
+    d->tab.lds_bytes_per_frame = 0;
+    return 0;
+}
+
+// what acg_ldpc_decoder_create_layered_streamed requires of the params (include/acg_ldpc.h); host only
+static int streaml_params_check(const acg_ldpc_params &p) {
+    const char *why = nullptr;
+    if (p.algo != ACG_LDPC_BP_SUMPRODUCT && p.algo != ACG_LDPC_BP_MINSUM) why = "algo must be ACG_LDPC_BP_SUMPRODUCT or ACG_LDPC_BP_MINSUM";
+    else if (p.schedule != ACG_LDPC_SCHEDULE_LAYERED) why = "schedule must be ACG_LDPC_SCHEDULE_LAYERED";
+    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (posteriors and messages are fp32)";
+    else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_STREAMED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (the state lives in device memory)";
+    else if (p.lanes_per_frame != 0) why = "lanes_per_frame must be 0 (one lane is one frame)";
+    if (why) {
+        set_error(std::string("streamed layered BP: ") + why);
+        return 3;
+    }
+    return 0;
+}
+
+// Streamed float layered BP (bp_streamed_layered.hip): sum-product or min-sum, fp32 posteriors and messages in slabs of device
+// memory, one per resident tile.  Any n, m, E and any check degree; the checks as for decoder_setup_streamq.
+// Resident tiles per CU: the integer engine's 12.  Measured for this kernel at 4 / 8 / 12 / 16 per CU, 25 iterations fixed, k frames/s
+// (tools/streamed_layered_rate.py): (3,6) 5000 x 10000 at +2 dB, sum-product 332 / 477 / 701 / 680, min-sum 421 / 581 /
+// 844 / 772; 2050 x 41000 of degree 40 at 5.3 dB, where a quarter of the free memory holds 8.9 per CU whatever is asked beyond
+// that, sum-product 88 / 123 / 115 / 126, min-sum 121 / 141 / 134 / 140 (the last two columns are one configuration).
+constexpr int STREAML_TILES_PER_CU = 12;
+static int decoder_setup_streaml(acg_ldpc_decoder *d) {
+    const Code &c = d->c;
+    if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
+    std::vector<int32_t> row_ptr, edge_var;
+    streamed_layered_csr(c, d->lblay, row_ptr, edge_var);
+    StreamLTables &t = d->sltab;
+    if (!(t.row_ptr = upload_keep(row_ptr, d->dev_allocs))) return 10;
+    if (!(t.edge_var = upload_keep(edge_var, d->dev_allocs))) return 10;
+    t.m = (int32_t) row_ptr.size() - 1;
+    t.n = c.n;
+    t.E = (int32_t) edge_var.size();
+    t.nwords = (c.n + 31) / 32;
+    t.max_deg = 0;
+    for (int i = 0; i < t.m; i++) t.max_deg = std::max(t.max_deg, row_ptr[i + 1] - row_ptr[i]);
+    const int algo = d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1;
+    const void *kp = bp_streamed_layered_kernel_ptr(algo);
+    const int T = 64;   // one lane is one frame
+    const size_t per_frame = 4 * ((size_t) c.n + (size_t) t.E + bp_streamed_layered_scratch_words(algo, t.max_deg));
+    const size_t slab = (per_frame * T + 255) & ~(size_t) 255;
+    t.slab_bytes = (int64_t) slab;
+    // tiles: the resident wavefronts of the kernel, at most STREAML_TILES_PER_CU per CU, as many as a quarter of the free memory
+    // holds, and no more than ACG_STREAML_TILES (developer switch: tests force the reuse of a slab)
+    int occ = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, 64, 0));
+    int64_t per_cu = std::max(1, std::min(occ, STREAML_TILES_PER_CU));
+    if (const char *e = getenv("ACG_STREAML_PER_CU")) {   // (developer switch: the sweep next to the constant)
+        const long want = atol(e);
+        if (want >= 1) per_cu = std::max<int64_t>(1, std::min<int64_t>(occ, want));
+    }
+    int64_t tiles = per_cu * d->cu_count;
+    size_t free_b = 0, total_b = 0;
+    HIP_OK(hipMemGetInfo(&free_b, &total_b));
+    const int64_t fit = (int64_t) (free_b / 4 / slab);
+    if (fit < 1) {
+        set_error("streamed layered BP: not one tile of " + std::to_string(T) + " frames (" + std::to_string(slab) +
+                  " bytes) fits in a quarter of the device's free memory (" + std::to_string(free_b / 4) + " bytes)");
+        return 3;
+    }
+    tiles = std::min(tiles, fit);
+    if (const char *e = getenv("ACG_STREAML_TILES")) {
+        const long want = atol(e);
+        if (want >= 1) tiles = std::min<int64_t>(tiles, want);
+    }
+    if (int rc = d->sl_ws.reserve((size_t) tiles * slab)) return rc;
+    d->streaml = true;
+    d->sl_tiles = (int) tiles;
     d->kernel[0] = kp;
     d->kernel[1] = nullptr;
     d->L = 1;
@@ -1018,7 +1102,7 @@ static int decoder_setup_bp(acg_ldpc_decoder *d) {
 }
 
 int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                      hipStream_t on_stream, const acg_ldpc_quant *quant, bool q_streamed) {
+                                      hipStream_t on_stream, const acg_ldpc_quant *quant, bool q_streamed, bool l_streamed) {
     if (!code || !params || !out) {
         set_error("null argument");
         return 1;
@@ -1034,6 +1118,13 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
             set_error("quantized layered min-sum: check degree above 32 is not supported");
             return 3;
         }
+    }
+    if (l_streamed) {
+        if (quant) {
+            set_error("internal: the streamed float layered engine takes no quantiser");
+            return 11;
+        }
+        if (int rc = streaml_params_check(*params)) return rc;
     }
     if (!quant && params->algo == ACG_LDPC_OSD) {
         if (int rc = osd_params_check(*params, code->c)) return rc;
@@ -1083,6 +1174,9 @@ int acg::acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_
             d->name = "QMS";
             d->quant = *quant;
             rc = q_streamed ? decoder_setup_streamq(d) : decoder_setup_layered_wg(d, acg_ldpc_decoder::LayeredWg::q, d->p.lanes_per_frame);
+        } else if (l_streamed) {
+            d->name = params->algo == ACG_LDPC_BP_SUMPRODUCT ? "BP" : "MS";
+            rc = decoder_setup_streaml(d);
         } else if (params->algo == ACG_LDPC_QPADMM) {
             d->name = "QP-ADMM";  // qp_admm.h:189
             std::string err;
@@ -1147,6 +1241,10 @@ int acg_ldpc_decoder_create_quantized_streamed(const acg_ldpc_code *code, const 
     });
 }
 
+int acg_ldpc_decoder_create_layered_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out) {
+    return guarded([&] { return acg_ldpc_decoder_create_impl(code, params, out, nullptr, nullptr, false, true); });
+}
+
 void acg_ldpc_decoder_destroy(acg_ldpc_decoder *d) {
     if (!d) return;
     (void) hipSetDevice(d->device);
@@ -1173,7 +1271,7 @@ void acg_ldpc_decoder_layout(const acg_ldpc_decoder *d, int32_t *lds_bytes_per_f
         admm_device_layout(d->admm.get(), lds_bytes_per_frame, lanes_per_frame, frames_per_block, grid_blocks);
         return;
     }
-    if (lds_bytes_per_frame) *lds_bytes_per_frame = d->streamed || d->streamq ? 0 : d->tab.lds_bytes_per_frame;
+    if (lds_bytes_per_frame) *lds_bytes_per_frame = d->streamed || d->streamq || d->streaml ? 0 : d->tab.lds_bytes_per_frame;
     if (lanes_per_frame) *lanes_per_frame = d->L;
     if (frames_per_block) *frames_per_block = d->frames_per_block;
     if (grid_blocks) *grid_blocks = d->grid_cap[0];
@@ -1215,6 +1313,14 @@ static std::string describe(const acg_ldpc_decoder *d) {
             }
             return t;
         }
+    } else if (d->streaml) {
+        const size_t scratch = bp_streamed_layered_scratch_words(d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1, d->sltab.max_deg);
+        snprintf(b, sizeof b, "%s engine=streamed kernel=bp_streamed_layered_kernel<%s> schedule=layered messages=fp32 posteriors=fp32 T=%d tiles=%d "
+                               "state_bytes_per_frame=%zu scratch_bytes_per_frame=%zu wide_mag=%s slab_bytes=%lld workspace_bytes=%zu "
+                               "workspace=hipMalloc sets=%d checks=%d max_check_degree=%d",
+                 algo, algo, d->frames_per_block, d->sl_tiles, 4 * ((size_t) d->c.n + (size_t) d->sltab.E), 4 * scratch,
+                 scratch == 0 ? "none" : (bp_streamed_layered_stores_mag() ? "stored" : "recomputed"), (long long) d->sltab.slab_bytes,
+                 (size_t) d->sl_tiles * (size_t) d->sltab.slab_bytes, d->lblay.n_sets, d->sltab.m, d->sltab.max_deg);
     } else if (d->streamq) {
         const acg_ldpc_quant &q = d->quant;
         snprintf(b, sizeof b, "%s engine=streamed kernel=bp_streamed_q_kernel schedule=layered T=%d tiles=%d state_bytes_per_frame=%zu "

@@ -1,0 +1,333 @@
+// Streamed float layered BP: sum-product and normalised min-sum with fp32 posteriors and fp32 messages, the per-check arithmetic
+// of the workgroup-per-frame layered engines (bp_layer_math.inc; wide_layer_step of bp_layered_wide.hip) in the engine shape of
+// bp_streamed_q.hip, so neither the size of a frame nor the degree of a check is bounded.  Reached through
+// acg_ldpc_decoder_create_layered_streamed only.  tests/layered_ref.py restates it (layered_minsum, layered_sumproduct_exact).
+//
+// Mapping, as in bp_streamed_q.hip: ONE LANE IS ONE FRAME.  A wavefront — a workgroup of 64 threads — owns a tile of T = 64 frames
+// and a slab of device memory:
+//     P[v][T] fp32 posteriors | R[e][T] fp32 messages, edges in processing order | scratch of a wide sum-product check (below)
+// so a wavefront's access to one variable or one edge is 256 consecutive bytes, and no lane reads another lane's data.
+// The graph is a plain CSR of the checks in processing order — the sets of bp_layered_block_build without a degree cap, set by
+// set — read through wave-uniform scalar loads.  The degree of a check is a loop bound.  Tiles are dealt by the launch's work
+// counter; a slab belongs to a resident workgroup.
+//
+// A check of up to LMAXD = 8 variables is worked off in one pass with its cells in registers: layer_back / layer_back_spa of
+// bp_layer_math.inc, the very functions of the LDS engines, with a message stride of T cells (16 bytes per edge and frame).  A
+// wider one takes two passes in chunks of 8 edges, as wide_layer_step does, with any number of chunks:
+//   pass 1, chunks ascending: q_j = p_j - r_j and the reductions over the whole check — min-sum: m1, m2; sum-product: mag_j =
+//           phi(|q_j|) and ONE ascending sum of them, whose value at the start of every chunk goes to the scratch area; both: the
+//           XOR of the signs of q and of p.  Nothing of P or R is written.
+//   pass 2, chunks descending: p_j and r_j read again (the same bits: nothing of the check was written before all of it was
+//           read, and what pass 2 writes belongs to chunks it has finished), q_j recomputed, the new message, p'_j = q_j + r'_j.
+//           Sum-product: pre_j restarts from the chunk's saved prefix and adds the same mag in the same order as pass 1 did, so
+//           it has the bits of one ascending sum over all D edges; suf runs on from chunk to chunk in descending edge order.
+// mag_j of pass 2 is formed again from q_j — the same bits, phi being a pure function, at three phi per edge — so the scratch
+// area holds the prefixes alone, base[ceil(Dmax / 8)][T].  Reading it back from a scratch area mag[Dmax][T] that pass 1 fills (two
+// phi, 8 bytes more per edge; ACG_SL_STORE_MAG=1) was measured and was 12 to 18 % slower: DESIGN 3i.
+//
+// Control: layered_ref._run_layered, the lines of bp_streamed_q_kernel.  A frame latches after the first iteration in which every
+// check was quiet; from then on its lane computes on but writes nothing of P or R, so its P stays the latched posterior.  Frames
+// out of iterations get one syndrome pass.  early_exit = 1 ends the tile when every frame of it has latched; early_exit = 0 runs
+// max_iter rounds; the outputs are the same.
+//
+// No stale state: a tile writes every P cell of its slab at its start (tail frames: 0), and in its first iteration takes every
+// message as 0 WITHOUT reading R and writes it, so every R cell a live frame reads later was written by that frame in this
+// tile; a scratch cell is written by pass 1 of the check whose pass 2 reads it.
+#include <hip/hip_runtime.h>
+
+#include "launchers.hpp"
+
+namespace acg {
+#include "bp_core.inc"   // Dom<float>::phi for the sum-product instance
+#include "bp_layer_math.inc"
+
+__device__ __forceinline__ int sl_sload(const int32_t *p, size_t i) { return ((lsconst_i32) (p))[i]; }
+
+constexpr int SL_T = 64;              // frames of a tile: one per lane
+// sum-product, wide checks: pass 2 forms mag_j again (0) or reads it back (1; make EXTRA=-DACG_SL_STORE_MAG=1, the build that
+// tools/streamed_layered_rate.py measured this one against: DESIGN 3i)
+#ifndef ACG_SL_STORE_MAG
+#define ACG_SL_STORE_MAG 0
+#endif
+constexpr bool SL_STORE_MAG = ACG_SL_STORE_MAG != 0;
+
+__device__ __forceinline__ uint32_t sl_bits(const float x) { return __float_as_uint(x); }
+__device__ __forceinline__ float sl_abs(const float x) { return __uint_as_float(__float_as_uint(x) & 0x7FFFFFFFu); }
+
+// ALGO: 1 = normalised min-sum, 0 = sum-product
+template <int ALGO>
+struct SlTile {
+    float *P;            // this lane's posterior of variable v: P[(size_t) v * SL_T]
+    float *R;            // this lane's message of edge e: R[(size_t) e * SL_T]
+    float *M;            // this lane's scratch: mag of the j-th edge of the wide check under way, M[(size_t) j * SL_T]
+    float *B;            // ... and its prefix sum at the start of chunk c, B[(size_t) c * SL_T]
+    const int32_t *ev;
+    float scale;
+    bool first;      // the tile's first iteration: every message is 0 and R is not read
+    bool live;       // the frame is updated: it exists and has not latched
+    uint32_t loud;   // bit 0: some step of the iteration was not quiet for this frame
+
+    // N edges from e: the addresses of this lane's posteriors, their values, and q = p - r
+    template <int N>
+    __device__ __forceinline__ void load(const size_t e, float *(&addr)[LMAXD], float (&p)[LMAXD], float (&q)[LMAXD]) const {
+        float r[LMAXD];
+#pragma unroll
+        for (int j = 0; j < N; ++j) addr[j] = P + (size_t) sl_sload(ev, e + j) * SL_T;
+#pragma unroll
+        for (int j = 0; j < N; ++j) p[j] = *addr[j];
+#pragma unroll
+        for (int j = 0; j < N; ++j) r[j] = first ? 0.0f : R[(e + j) * SL_T];
+#pragma unroll
+        for (int j = 0; j < N; ++j) q[j] = p[j] - r[j];
+    }
+
+    // a check of D <= 8 edges from e: the step of the LDS engines
+    template <int D>
+    __device__ __forceinline__ void small_check(const size_t e) {
+        float *addr[LMAXD];
+        float p[LMAXD], q[LMAXD];
+        load<D>(e, addr, p, q);
+        uint32_t noisy;
+        if constexpr (ALGO == 0) noisy = layer_back_spa<D, SL_T, float>(R + e * SL_T, addr, p, q, live);
+        else noisy = layer_back<D, SL_T, float>(R + e * SL_T, addr, p, q, live, scale);
+        loud |= noisy >> 31;
+    }
+
+    // what pass 1 hands to pass 2 in registers
+    struct Wide {
+        uint32_t S = 0, parity = 0, flipped = 0;
+        float m1 = INFINITY, m2 = INFINITY;   // min-sum
+        uint32_t m1s = 0, m2s = 0;
+        float s = 0.0f, suf = 0.0f;           // sum-product: the ascending sum so far, the descending one
+    };
+
+    // chunk c of a wide check: its N edges from e, the first of them edge number j0 = 8 c of the check
+    template <int N>
+    __device__ __forceinline__ void pass1(Wide &w, const size_t e, const int c) const {
+        float *addr[LMAXD];
+        float p[LMAXD], q[LMAXD];
+        load<N>(e, addr, p, q);
+        if constexpr (ALGO == 0) B[(size_t) c * SL_T] = w.s;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            w.parity ^= sl_bits(p[j]);                      // parity of the hard decisions this check sees
+            w.S ^= sl_bits(q[j]);
+            const float a = sl_abs(q[j]);
+            if constexpr (ALGO == 0) {
+                const float m = Dom<float>::phi(a);
+                if constexpr (SL_STORE_MAG) M[(size_t) (c * LMAXD + j) * SL_T] = m;
+                w.s += m;
+            } else {
+                w.m2 = __builtin_amdgcn_fmed3f(a, w.m1, w.m2);
+                w.m1 = __builtin_fminf(w.m1, a);
+            }
+        }
+    }
+    template <int N>
+    __device__ __forceinline__ void pass2(Wide &w, const size_t e, const int c) {
+        float *addr[LMAXD];
+        float p[LMAXD], q[LMAXD];
+        load<N>(e, addr, p, q);
+        float mag[LMAXD], pre[LMAXD];
+        if constexpr (ALGO == 0) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                if constexpr (SL_STORE_MAG) mag[j] = M[(size_t) (c * LMAXD + j) * SL_T];
+                else mag[j] = Dom<float>::phi(sl_abs(q[j]));
+            }
+            float t = B[(size_t) c * SL_T];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                pre[j] = t;
+                t += mag[j];
+            }
+        }
+        float rn[LMAXD], pn[LMAXD];
+#pragma unroll
+        for (int j = N - 1; j >= 0; --j) {
+            uint32_t mg;
+            if constexpr (ALGO == 0) {
+                const float out = __builtin_fminf(Dom<float>::phi(pre[j] + w.suf), LAYERED_SPA_SATURATION);
+                w.suf += mag[j];
+                mg = sl_bits(out) & 0x7FFFFFFFu;
+            } else {
+                mg = (sl_abs(q[j]) == w.m1) ? w.m2s : w.m1s;     // a tie makes m2 == m1: either answer is the same
+            }
+            rn[j] = __uint_as_float(mg | ((w.S ^ sl_bits(q[j])) & 0x80000000u));
+            pn[j] = q[j] + rn[j];
+            w.flipped |= sl_bits(pn[j]) ^ sl_bits(p[j]);         // a hard decision flipped
+        }
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) *addr[j] = pn[j];
+#pragma unroll
+            for (int j = 0; j < N; ++j) R[(e + j) * SL_T] = rn[j];
+        }
+    }
+
+#define ACG_SL_TAIL(n, CALL) \
+    switch (n) {             \
+        case 1: CALL(1); break; \
+        case 2: CALL(2); break; \
+        case 3: CALL(3); break; \
+        case 4: CALL(4); break; \
+        case 5: CALL(5); break; \
+        case 6: CALL(6); break; \
+        case 7: CALL(7); break; \
+        default: break;      \
+    }
+
+    // the check of the edges [e0, e1), e1 > e0 (wave-uniform)
+    __device__ __forceinline__ void check(const size_t e0, const size_t e1) {
+        const int D = (int) (e1 - e0);
+        if (D <= LMAXD) {
+#define ACG_CALL(N) small_check<N>(e0)
+            ACG_LAYER_SWITCH(D, ACG_CALL)
+#undef ACG_CALL
+            return;
+        }
+        Wide w;
+        const int full = D / LMAXD, tail = D - full * LMAXD;   // chunks of 8 edges, and the edges of the last, shorter one
+        const size_t et = e0 + (size_t) full * LMAXD;
+        for (int c = 0; c < full; ++c) pass1<LMAXD>(w, e0 + (size_t) c * LMAXD, c);
+#define ACG_CALL(N) pass1<N>(w, et, full)
+        ACG_SL_TAIL(tail, ACG_CALL)
+#undef ACG_CALL
+        // the two minima are scaled once per check (layer_back; D > 8, so no one-variable check here)
+        if constexpr (ALGO == 1) {
+            w.m1s = sl_bits(scale * w.m1) & 0x7FFFFFFFu;
+            w.m2s = sl_bits(scale * w.m2) & 0x7FFFFFFFu;
+            asm volatile("" : "+v"(w.m1s), "+v"(w.m2s));
+        }
+#define ACG_CALL(N) pass2<N>(w, et, full)
+        ACG_SL_TAIL(tail, ACG_CALL)
+#undef ACG_CALL
+        for (int c = full - 1; c >= 0; --c) pass2<LMAXD>(w, e0 + (size_t) c * LMAXD, c);
+        loud |= (w.parity | w.flipped) >> 31;
+    }
+#undef ACG_SL_TAIL
+};
+
+// grid <= the slabs behind ws
+template <int ALGO>
+__global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLTables t, const DecodeArgs a, unsigned char *__restrict__ ws) {
+    constexpr int T = SL_T;
+    constexpr int XV = 32;      // variables of a trip through the transposing buffer
+    constexpr int XS = T + 1;   // words per row of it: rows an odd number of words apart
+    __shared__ float X[XV * XS];
+    const int l = threadIdx.x;
+    float *const slab = reinterpret_cast<float *>(ws + (size_t) blockIdx.x * (size_t) t.slab_bytes);
+    SlTile<ALGO> tl;
+    tl.P = slab + l;
+    tl.R = tl.P + (size_t) t.n * T;
+    tl.M = tl.R + (size_t) t.E * T;
+    tl.B = SL_STORE_MAG ? tl.M + (size_t) t.max_deg * T : tl.M;
+    tl.ev = t.edge_var;
+    tl.scale = a.ms_scale;
+    const int n = t.n;
+
+    for (;;) {
+        unsigned long long tv = 0;
+        if (l == 0) tv = atomicAdd(a.work_counter, 1ull);
+        const int64_t tile = (int64_t) (((unsigned long long) (uint32_t) __builtin_amdgcn_readfirstlane((int) (tv >> 32)) << 32) |
+                                        (uint32_t) __builtin_amdgcn_readfirstlane((int) tv));
+        const int64_t frame0 = tile * T;
+        if (frame0 >= a.frames) break;
+        const int nf = (int) (a.frames - frame0 < T ? a.frames - frame0 : T);   // frames of this tile (wave-uniform)
+        const bool exists = l < nf;
+        const size_t frame = (size_t) frame0 + l;
+
+        // ---- start of the tile: P = channel LLR (channel.h:14-16), [frame][n] -> [n][T] through LDS, 32 variables at a time; a
+        // lane takes one variable of every second frame -------------------------------------------------------------------------------
+        for (int v0 = 0; v0 < n; v0 += XV) {
+            const int vl = l & (XV - 1), h = l / XV;
+            const bool mine = v0 + vl < n;
+            const size_t y0 = (size_t) frame0 * n + v0 + vl;
+#pragma unroll 8
+            for (int k = 0; k < T / 2; ++k) {
+                const int fr = 2 * k + h;
+                float x = 0.0f;
+                if (fr < nf && mine) {
+                    float llr;
+                    if (a.y_is_f64) llr = (float) (2 * reinterpret_cast<const double *>(a.y)[y0 + (size_t) fr * n] / a.var);
+                    else llr = (float) ((double) reinterpret_cast<const float *>(a.y)[y0 + (size_t) fr * n] * a.inv_var2);
+                    x = (ALGO == 0) ? llr * (float) Dom<float>::scale : llr;
+                }
+                X[vl * XS + fr] = x;
+            }
+            __syncthreads();
+            const int nv = n - v0 < XV ? n - v0 : XV;
+            for (int vv = 0; vv < nv; ++vv) tl.P[(size_t) (v0 + vv) * T] = X[vv * XS + l];
+            __syncthreads();
+        }
+
+        bool latched = false;
+        int iters = a.max_iter;
+        tl.live = exists;
+        // ---- the iterations ------------------------------------------------------------------------------------------------------
+        for (int it = 1; it <= a.max_iter; ++it) {
+            if (a.early_exit && __ballot(tl.live) == 0ull) break;
+            tl.loud = 0;
+            tl.first = it == 1;
+            size_t e0 = (size_t) sl_sload(t.row_ptr, 0);
+            for (int i = 0; i < t.m; ++i) {
+                const size_t e1 = (size_t) sl_sload(t.row_ptr, (size_t) i + 1);
+                tl.check(e0, e1);
+                e0 = e1;
+            }
+            if (tl.live && (tl.loud & 1u) == 0u) {
+                latched = true;
+                iters = it;
+                tl.live = false;
+            }
+        }
+        // ---- frames out of iterations: one syndrome pass over the posteriors' signs ---------------------------------------------
+        bool good = latched;
+        if (a.max_iter > 0 && __ballot(tl.live) != 0ull) {
+            uint32_t bad = 0;
+            size_t e0 = (size_t) sl_sload(t.row_ptr, 0);
+            for (int i = 0; i < t.m; ++i) {
+                const size_t e1 = (size_t) sl_sload(t.row_ptr, (size_t) i + 1);
+                uint32_t S = 0;
+#pragma unroll 4
+                for (size_t e = e0; e < e1; ++e) S ^= sl_bits(tl.P[(size_t) sl_sload(t.edge_var, e) * T]);
+                bad |= S;
+                e0 = e1;
+            }
+            if (tl.live) good = (bad >> 31) == 0u;
+        }
+        // ---- the tile's outputs: packed words (zeros for a failed frame), flags, iterations -------------------------------------
+        if (exists) {
+            if (a.out_ok) a.out_ok[frame] = good ? 1 : 0;
+            if (a.out_iters) a.out_iters[frame] = iters;
+        }
+        if (a.out_bits) {
+            for (int w = 0; w < t.nwords; ++w) {
+                uint32_t word = 0;
+                const int nb = n - 32 * w < 32 ? n - 32 * w : 32;
+#pragma unroll 8
+                for (int b = 0; b < nb; ++b) word |= (sl_bits(tl.P[(size_t) (32 * w + b) * T]) >> 31) << b;
+                if (exists) a.out_bits[frame * t.nwords + w] = good ? word : 0u;
+            }
+        }
+    }
+}
+
+// algo: 0 sum-product, 1 min-sum
+const void *bp_streamed_layered_kernel_ptr(int algo) {
+    return algo == 0 ? (const void *) bp_streamed_layered_kernel<0> : (const void *) bp_streamed_layered_kernel<1>;
+}
+
+// floats per frame behind P and R: the scratch of a wide sum-product check (0: the code has none, or min-sum)
+size_t bp_streamed_layered_scratch_words(int algo, int max_deg) {
+    if (algo != 0 || max_deg <= LMAXD) return 0;
+    return (size_t) (SL_STORE_MAG ? max_deg : 0) + (size_t) (max_deg + LMAXD - 1) / LMAXD;
+}
+bool bp_streamed_layered_stores_mag() { return SL_STORE_MAG; }
+
+hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLTables &t, const DecodeArgs &a, unsigned char *ws, int grid, hipStream_t s) {
+    void *args[] = {(void *) &t, (void *) &a, (void *) &ws};
+    return hipLaunchKernel(kernel, dim3((unsigned) grid), dim3(64), args, 0, s);
+}
+
+}  // namespace acg

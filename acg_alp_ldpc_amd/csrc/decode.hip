@@ -115,7 +115,7 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
     if (d->ring_used[slot]) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[slot], 0));
     // engines whose HBM workspace belongs to the handle (streamed BP, streamed QP-ADMM): a launch on another stream waits
     // (and the snapshot slots of the fused kernels' freeze path)
-    const bool owns_ws = d->streamed || d->streamq || d->freeze || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
+    const bool owns_ws = d->streamed || d->streamq || d->streaml || d->freeze || (d->admm && admm_device_streamed(d->admm.get(), nullptr, nullptr, nullptr));
     if (owns_ws && d->last_slot >= 0 && d->last_stream != s) HIP_OK(hipStreamWaitEvent(s, d->ring_ev[d->last_slot], 0));
     a.work_counter = d->work_counter(slot);
     HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));
@@ -188,6 +188,14 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
                 HIP_OK(bp_streamed_q_launch(d->kernel[0], d->sqtab, ac, q, d->sq_ws.as<unsigned char>(), grid, s));
             }
         }
+    } else if (d->streaml) {
+        if (a.mc) {
+            set_error("internal: the streamed layered engine has no in-kernel generator");
+            return 11;
+        }
+        const int T = d->frames_per_block;
+        const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sl_tiles);
+        HIP_OK(bp_streamed_layered_launch(d->kernel[0], d->sltab, a, d->sl_ws.as<unsigned char>(), grid, s));
     } else if (d->osd) {
         if (a.mc) {
             set_error("internal: the OSD engine has no in-kernel generator");

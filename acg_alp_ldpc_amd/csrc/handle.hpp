@@ -184,6 +184,14 @@ struct acg_ldpc_decoder {
     acg::StreamQTables sqtab{};
     int sq_tiles = 0;
     acg::DeviceBuf sq_ws, sq_stage;
+    // streamed float layered BP (bp_streamed_layered.hip; handles of acg_ldpc_decoder_create_layered_streamed only): sum-product
+    // or min-sum with fp32 posteriors and messages, a frame in the slabs of sl_ws, one per resident tile of 64 frames; the sets in
+    // lblay.  NOT a quantized handle (layered_wg stays none): the integer entrances refuse it.  Decode only: Monte-Carlo runs take
+    // the unfused route.
+    bool streaml = false;
+    acg::StreamLTables sltab{};
+    int sl_tiles = 0;
+    acg::DeviceBuf sl_ws;
     // ordered-statistics decoding (osd.hip; algo = ACG_LDPC_OSD): the packed column table, and what the kernel reads.  One kernel
     // for both entrances (OsdArgs::s_in set per launch); decode only: Monte-Carlo runs take the unfused route.
     bool osd = false;
@@ -285,9 +293,11 @@ namespace acg {
 
 // ---- api.hip (on_stream != null: the handle works on that stream of the caller's instead of one of its own;
 // quant != null: the fixed-point layered min-sum engine of acg_ldpc_decoder_create_quantized, or with q_streamed the one of
-// acg_ldpc_decoder_create_quantized_streamed) ----
+// acg_ldpc_decoder_create_quantized_streamed; l_streamed (quant null): the streamed float layered engine of
+// acg_ldpc_decoder_create_layered_streamed) ----
 int acg_ldpc_decoder_create_impl(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out,
-                                 hipStream_t on_stream = nullptr, const acg_ldpc_quant *quant = nullptr, bool q_streamed = false);
+                                 hipStream_t on_stream = nullptr, const acg_ldpc_quant *quant = nullptr, bool q_streamed = false,
+                                 bool l_streamed = false);
 QuantArgs quant_args(const acg_ldpc_quant &q);
 
 // ---- decode.hip ----

@@ -163,6 +163,15 @@ struct StreamQTables {
     int64_t slab_bytes;        // bytes of a tile's slab: P[n][T] int16 | R[E][T] int8, rounded up to 256
 };
 
+// Streamed float layered BP (bp_streamed_layered.hip): the same CSR, and the slab of a tile
+struct StreamLTables {
+    const int32_t *row_ptr;    // [m + 1] first edge of the i-th check processed (the sets of bp_layered_block_build, set by set)
+    const int32_t *edge_var;   // [E] variables of those edges, ascending inside a check
+    int32_t m, n, E, nwords;   // m: checks with at least one variable
+    int32_t max_deg;           // largest check degree: rows of the wide-check scratch
+    int64_t slab_bytes;        // bytes of a tile's slab: P[n][T] | R[E][T] | scratch, fp32, rounded up to 256
+};
+
 // Ordered-statistics decoding (osd.hip): what the kernel reads next to DecodeArgs
 struct OsdArgs {
     const uint32_t *cols;   // [n][stride] H column-major, bit r % 32 of word r / 32 of column v = H[r][v]

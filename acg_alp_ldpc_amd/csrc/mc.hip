@@ -245,7 +245,7 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
     int rc = 0;
     if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
         rc = mc_run_host_noise(d, cfg, res);
-    } else if (d->streamed || d->pair || d->osd || d->layered_wg != acg_ldpc_decoder::LayeredWg::none || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
+    } else if (d->streamed || d->streaml || d->pair || d->osd || d->layered_wg != acg_ldpc_decoder::LayeredWg::none || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
         // AWGN kernel -> decode -> classify kernel, in bounded chunks, all on the device.  Used by the streamed BP
         // engine and the workgroup-per-frame layered engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
         // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.

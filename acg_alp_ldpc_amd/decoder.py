@@ -5,6 +5,8 @@
     MinSumDecoder(max_iter, scale)                         build-added, not in the reference
     QuantizedMinSumDecoder(max_iter, quant)                build-added, not in the reference: fixed-point layered min-sum
     StreamedQuantizedMinSumDecoder(max_iter, quant)        build-added: the same decoder, state in device memory, any code
+    StreamedLayeredBPDecoder(max_iter)                     build-added: layered sum-product, state in device memory, any code
+    StreamedLayeredMinSumDecoder(max_iter, scale)          build-added: layered min-sum, state in device memory, any code
     OSDDecoder(order=1)                                    build-added, not in the reference: ordered-statistics decoding
 
     decode(H, channel_word, snr) -> (codeword, ok)         same argument meaning as algo/algo.h:8:
@@ -399,6 +401,38 @@ class StreamedQuantizedMinSumDecoder(QuantizedMinSumDecoder):
     def _create(self, code, p, h):
         q = self.quant.as_struct()
         return lib().acg_ldpc_decoder_create_quantized_streamed(code._h, C.byref(p), C.byref(q), C.byref(h))
+
+
+class _StreamedLayered:
+    """the create call and handle key of the streamed float layered engine (acg_ldpc_decoder_create_layered_streamed)"""
+
+    def _key(self, H):
+        return super()._key(H) + ("layered-streamed",)
+
+    def _create(self, code, p, h):
+        return lib().acg_ldpc_decoder_create_layered_streamed(code._h, C.byref(p), C.byref(h))
+
+
+class StreamedLayeredBPDecoder(_StreamedLayered, BeliefPropagationDecoder):
+    """Build-added (acg_ldpc_decoder_create_layered_streamed; not in the reference): layered sum-product — the reference's check
+    rule, bp.h:49-57 — with fp32 posteriors and messages in device memory instead of LDS: one lane per frame, 4 n + 4 E bytes per
+    frame, any code size and any check degree.  Word, flag and iteration of every frame equal those of
+    BeliefPropagationDecoder(schedule=SCHEDULE_LAYERED, lanes_per_frame=256) on every code both accept, and a code whose frame
+    fits in LDS is decoded faster there.  tests/layered_ref.py (layered_sumproduct_exact) restates it.  lanes_per_frame must stay
+    0, precision PREC_DEFAULT and engine ENGINE_AUTO or ENGINE_STREAMED; not a stage of CascadeDecoder."""
+
+    def __init__(self, max_iter, **kw):
+        kw.setdefault("schedule", _lib.SCHEDULE_LAYERED)
+        super().__init__(max_iter, **kw)
+
+
+class StreamedLayeredMinSumDecoder(_StreamedLayered, MinSumDecoder):
+    """Build-added: StreamedLayeredBPDecoder with the normalised min-sum check rule of MinSumDecoder(schedule=SCHEDULE_LAYERED,
+    lanes_per_frame=256), equal to it frame for frame on every code both accept.  tests/layered_ref.py (layered_minsum)."""
+
+    def __init__(self, max_iter, scale=1.0, **kw):
+        kw.setdefault("schedule", _lib.SCHEDULE_LAYERED)
+        super().__init__(max_iter, scale, **kw)
 
 
 class OSDDecoder(Decoder):

@@ -275,9 +275,39 @@ int acg_ldpc_decode_batch_q(acg_ldpc_decoder *dec, const int16_t *c, int64_t fra
  * A code whose frame fits in LDS is decoded faster by acg_ldpc_decoder_create_quantized: use this call for the codes that one
  * refuses.
  * Not provided: a cascade stage of this engine (acg_ldpc_cascade_create builds its own stages with the two create calls
- * above), a grid form for acg_ldpc_mc_run_quants, float messages. */
+ * above), a grid form for acg_ldpc_mc_run_quants.  (Float messages: acg_ldpc_decoder_create_layered_streamed below.) */
 int acg_ldpc_decoder_create_quantized_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, const acg_ldpc_quant *q,
                                                acg_ldpc_decoder **out);
+
+/* ---- streamed float layered BP: sum-product and min-sum at any code size and check degree (build-added) ---- */
+
+/* Layered sum-product (the reference's check rule, bp.h:49-57) and normalised min-sum with fp32 posteriors and fp32 messages, a
+ * frame's state in device memory instead of LDS (bp_streamed_layered_kernel): one lane is one frame, a wavefront owns a tile of
+ * T frames and walks the edges of a check in a loop, so neither the size of a frame nor the degree of a check is bounded.
+ * The arithmetic, stopping rule, latching, final syndrome pass and iteration count are those of acg_ldpc_decoder_create with
+ * schedule = ACG_LDPC_SCHEDULE_LAYERED and lanes_per_frame = 256 / 512 / 1024 (the workgroup-per-frame engines) — word, flag
+ * and iteration of every frame are equal on every code both accept.  The checks are taken in the order of the sets
+ * acg_ldpc_debug_layers_any reports, set by set.  tests/layered_ref.py restates it.  State of a frame: 4 n + 4 E bytes.
+ * Required of *params, anything else is refused with a message before a device is looked for:
+ *   algo = ACG_LDPC_BP_SUMPRODUCT or ACG_LDPC_BP_MINSUM, schedule = ACG_LDPC_SCHEDULE_LAYERED,
+ *   precision = ACG_LDPC_PREC_DEFAULT, engine = ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (ACG_LDPC_ENGINE_FUSED is
+ *   refused), lanes_per_frame = 0.  ms_scale, max_iter, early_exit and device apply as everywhere.
+ * Workspace: one allocation of tiles x (the state of T frames plus, for sum-product on a code with a check of more than 8
+ * variables, 4 ceil(Dmax / 8) bytes per frame of scratch; rounded up to 256), T = 64, tiles = min(12 per compute unit,
+ * what fits in a quarter of the device's free memory); creation fails with a message when not one tile fits.
+ * ACG_STREAML_TILES=<count> (developer switch, read at creation) lowers the tile count.
+ * The handle is an ordinary decoder: acg_ldpc_decode_batch, _f32 and _dev take it; acg_ldpc_mc_run and _detail go noise kernel
+ * -> decode -> classification kernel; acg_ldpc_mc_run_grid refuses it as it refuses every handle that is not QP-ADMM; the integer
+ * entrances (acg_ldpc_decode_batch_q, _q_dev, acg_ldpc_quantize_dev, acg_ldpc_mc_run_quants) refuse it as a handle that is not
+ * quantized.  The workspace belongs to the handle, so launches of one handle on different streams are ordered on the device.
+ * acg_ldpc_decoder_name returns "BP" or "MS"; acg_ldpc_decoder_layout reports as for the streamed engines (no LDS bytes, one
+ * lane per frame, T frames per block, tiles); acg_ldpc_decoder_describe names the kernel, the algorithm, T, the tiles, the bytes
+ * of state per frame and the sets.
+ * A code whose frame fits in LDS is decoded faster by acg_ldpc_decoder_create: use this call for the codes that one refuses
+ * (check degree above 32, a frame beyond 160 KiB).
+ * Not provided: a cascade stage of this engine (acg_ldpc_cascade_create keeps building its stages with the create calls it uses
+ * today), LLR input, posterior output, fp16 messages, fp64, a fused Monte-Carlo kernel. */
+int acg_ldpc_decoder_create_layered_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out);
 
 /* ---- OSD: ordered-statistics decoding (Fossorier-Lin) of order 0 and 1 (build-added) ------ */
 

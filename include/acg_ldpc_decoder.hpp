@@ -261,7 +261,9 @@ class BeliefPropagationDecoder : public HipDecoderBase {
 public:
     // layered (build-added, default off = the reference's flooding schedule, bit-exact hard decisions): the same check rule with the
     // posteriors updated per block row — the reference's FER at about half the iterations, FER-level parity only
-    explicit BeliefPropagationDecoder(int max_iter, bool layered = false) : _max_iter(max_iter), _layered(layered) {}
+    // lanes_per_frame: acg_ldpc_params::lanes_per_frame (with layered, 256 / 512 / 1024 = the engine with one workgroup per frame)
+    explicit BeliefPropagationDecoder(int max_iter, bool layered = false, int lanes_per_frame = 0)
+        : _max_iter(max_iter), _layered(layered), _lanes(lanes_per_frame) {}
     std::string name() const override { return "BP"; }  // bp.h:218
 
 protected:
@@ -269,6 +271,7 @@ protected:
         p.algo = ACG_LDPC_BP_SUMPRODUCT;
         p.max_iter = _max_iter;
         p.schedule = _layered ? ACG_LDPC_SCHEDULE_LAYERED : ACG_LDPC_SCHEDULE_FLOODING;
+        p.lanes_per_frame = _lanes;
     }
     std::pair<TCodeword, bool> finish(const std::vector<uint8_t> &bits, bool ok) const override {
         if (!ok) return {TCodeword(), false};  // bp.h:198
@@ -278,6 +281,7 @@ protected:
 private:
     int _max_iter;
     bool _layered;
+    int _lanes;
 };
 
 // algo/qp_admm.h:180-194 (same defaults)
@@ -308,7 +312,8 @@ private:
 // iterations for the same FER; FER-level parity only)
 class MinSumDecoder : public HipDecoderBase {
 public:
-    explicit MinSumDecoder(int max_iter, double scale = 1.0, bool layered = false) : _max_iter(max_iter), _scale(scale), _layered(layered) {}
+    explicit MinSumDecoder(int max_iter, double scale = 1.0, bool layered = false, int lanes_per_frame = 0)
+        : _max_iter(max_iter), _scale(scale), _layered(layered), _lanes(lanes_per_frame) {}
     std::string name() const override { return "MS"; }
 
 protected:
@@ -317,6 +322,7 @@ protected:
         p.max_iter = _max_iter;
         p.ms_scale = _scale;
         p.schedule = _layered ? ACG_LDPC_SCHEDULE_LAYERED : ACG_LDPC_SCHEDULE_FLOODING;
+        p.lanes_per_frame = _lanes;
     }
     std::pair<TCodeword, bool> finish(const std::vector<uint8_t> &bits, bool ok) const override {
         if (!ok) return {TCodeword(), false};
@@ -327,6 +333,31 @@ private:
     int _max_iter;
     double _scale;
     bool _layered;
+    int _lanes;
+};
+
+// build-added; not in the reference.  Layered sum-product and min-sum with fp32 posteriors and messages in device memory
+// (acg_ldpc_decoder_create_layered_streamed): any code size, any check degree; word and flag of every frame equal those of
+// BeliefPropagationDecoder(max_iter, true, 256) / MinSumDecoder(max_iter, scale, true, 256) on every code both accept.  A code
+// whose frame fits in LDS is decoded faster by those.
+class StreamedLayeredBPDecoder : public BeliefPropagationDecoder {
+public:
+    explicit StreamedLayeredBPDecoder(int max_iter) : BeliefPropagationDecoder(max_iter, true, 0) {}
+
+protected:
+    int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
+        return acg_ldpc_decoder_create_layered_streamed(code, &p, out);
+    }
+};
+
+class StreamedLayeredMinSumDecoder : public MinSumDecoder {
+public:
+    explicit StreamedLayeredMinSumDecoder(int max_iter, double scale = 1.0) : MinSumDecoder(max_iter, scale, true, 0) {}
+
+protected:
+    int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
+        return acg_ldpc_decoder_create_layered_streamed(code, &p, out);
+    }
 };
 
 // build-added; not in the reference.  Fixed-point layered min-sum (acg_ldpc_decoder_create_quantized): integer channel values,

@@ -24,6 +24,10 @@
 //                         lds = acg_ldpc_decoder_create_quantized (a frame in LDS), streamed =
 //                         acg_ldpc_decoder_create_quantized_streamed (a frame in device memory: any code size, any check
 //                         degree).  One more block, Method = QMS; both engines give the same rows.
+//            [--layered-streamed bp|minsum|bp,minsum]   also evaluate the layered sum-product (--bp-iters) and / or the layered
+//                         min-sum (--minsum-iters, --ms-scale) on the streamed float layered engine,
+//                         acg_ldpc_decoder_create_layered_streamed (fp32 state in device memory: any code size, any check
+//                         degree).  One more block each, Method = BP / MS, behind the others.
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -63,6 +67,16 @@ int main(int argc, char **argv) {
     if (a.has("--qms-engine") && qms_engine != "lds" && qms_engine != "streamed") {
         std::fprintf(stderr, "acg_eval: --qms-engine lds or streamed\n");
         return 2;
+    }
+    std::vector<std::string> layered_streamed;
+    if (a.has("--layered-streamed")) {
+        const std::string spec = a.get("--layered-streamed", "");
+        if (spec == "bp" || spec == "minsum") layered_streamed = {spec};
+        else if (spec == "bp,minsum") layered_streamed = {"bp", "minsum"};
+        else {
+            std::fprintf(stderr, "acg_eval: --layered-streamed bp, minsum or bp,minsum\n");
+            return 2;
+        }
     }
     acg_ldpc_code *code = nullptr;
     if (acg_ldpc_code_load_txt(hpath, &code)) drv::die("read_pcm");
@@ -135,6 +149,13 @@ int main(int argc, char **argv) {
         acg_ldpc_quant_default(&q);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev, &q, qms_engine == "streamed");
+    }
+    for (const std::string &which : layered_streamed) {
+        params_of(which, p);
+        p.schedule = ACG_LDPC_SCHEDULE_LAYERED;
+        p.precision = ACG_LDPC_PREC_DEFAULT;
+        decs.emplace_back();
+        decs.back().create(code, p, gpus, ndev, nullptr, false, true);
     }
     acg_ldpc_cascade *cascade = nullptr;
     if (a.has("--cascade")) {

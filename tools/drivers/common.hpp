@@ -158,13 +158,16 @@ inline std::vector<uint8_t> make_codewords(const acg_ldpc_code *code, const char
 struct MultiGpu {
     std::vector<acg_ldpc_decoder *> dec;
 
-    // quant != null: the fixed-point layered min-sum engine with that quantiser, in LDS or (streamed) in device memory
+    // quant != null: the fixed-point layered min-sum engine with that quantiser, in LDS or (streamed) in device memory;
+    // layered_streamed (quant null): the streamed float layered engine
     void create(const acg_ldpc_code *code, acg_ldpc_params p, int gpus, int device_count, const acg_ldpc_quant *quant = nullptr,
-                bool streamed = false) {
+                bool streamed = false, bool layered_streamed = false) {
         for (int k = 0; k < gpus; k++) {
             p.device = device_count > 0 ? k % device_count : -1;
             acg_ldpc_decoder *d = nullptr;
-            if (quant && streamed) {
+            if (layered_streamed) {
+                if (acg_ldpc_decoder_create_layered_streamed(code, &p, &d)) die("acg_ldpc_decoder_create_layered_streamed");
+            } else if (quant && streamed) {
                 if (acg_ldpc_decoder_create_quantized_streamed(code, &p, quant, &d)) die("acg_ldpc_decoder_create_quantized_streamed");
             } else if (quant) {
                 if (acg_ldpc_decoder_create_quantized(code, &p, quant, &d)) die("acg_ldpc_decoder_create_quantized");
