@@ -136,6 +136,7 @@ SYMBOLS = {
     "acg_ldpc_debug_layers_block": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_wide": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_any": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
+    "acg_ldpc_debug_streamed_slab": (C.c_int, [_vp, _i32, _vp, _i64, C.POINTER(_i64)]),
     "acg_ldpc_debug_phi": (C.c_int, [_vp, _vp, _i32, _i32]),
     "acg_ldpc_debug_phi_sat": (C.c_int, [_vp, _vp, _i32]),
     "acg_ldpc_debug_phi_split": (C.c_int, [_vp]),

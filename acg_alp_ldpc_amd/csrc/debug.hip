@@ -370,4 +370,44 @@ int acg_ldpc_debug_phi_split(uint32_t *out_host) {
     return guarded([&] { return acg_ldpc_debug_phi_split_impl(out_host); });
 }
 
+// host only: a copy out of the workspace the streamed layered engines keep a tile's state in; no kernel takes part
+static int acg_ldpc_debug_streamed_slab_impl(acg_ldpc_decoder *d, int32_t slab, void *out_host, int64_t cap_bytes, int64_t *slab_bytes) {
+    if (!slab_bytes) {
+        set_error("null slab_bytes");
+        return 1;
+    }
+    *slab_bytes = 0;
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    if (!d->streaml && !d->streamq) {
+        set_error("acg_ldpc_debug_streamed_slab needs a decoder of acg_ldpc_decoder_create_layered_streamed or acg_ldpc_decoder_create_quantized_streamed");
+        return 3;
+    }
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    const int tiles = d->streaml ? d->sl_tiles : d->sq_tiles;
+    const int64_t bytes = d->streaml ? d->sltab.slab_bytes : d->sqtab.slab_bytes;
+    const unsigned char *ws = d->streaml ? d->sl_ws.as<unsigned char>() : d->sq_ws.as<unsigned char>();
+    *slab_bytes = bytes;
+    if (slab < 0 || slab >= tiles) {
+        set_error("slab " + std::to_string(slab) + " is outside 0 ... " + std::to_string(tiles - 1) + " (the handle's tiles)");
+        return 1;
+    }
+    if (!out_host) return 0;  // the size query
+    if (cap_bytes < 0) {
+        set_error("negative cap_bytes");
+        return 1;
+    }
+    HIP_OK(hipSetDevice(d->device));
+    HIP_OK(hipDeviceSynchronize());  // every launch of the handle so far, on its own stream or a caller's
+    const size_t take = (size_t) std::min<int64_t>(cap_bytes, bytes);
+    if (take) HIP_OK(hipMemcpy(out_host, ws + (size_t) slab * (size_t) bytes, take, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int acg_ldpc_debug_streamed_slab(acg_ldpc_decoder *d, int32_t slab, void *out_host, int64_t cap_bytes, int64_t *slab_bytes) {
+    return guarded([&] { return acg_ldpc_debug_streamed_slab_impl(d, slab, out_host, cap_bytes, slab_bytes); });
+}
+
 }  // extern "C"

@@ -236,6 +236,26 @@ class Decoder(_HandleCache):
         check(lib().acg_ldpc_debug_freeze_passes(h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def streamed_slab(self, H, slab=0):
+        """(P [64, n], R [64, E]): the posteriors and messages slab `slab` of the handle for H holds, row l = lane l = frame
+        64 tile + l of the tile that used the slab last (acg_ldpc_debug_streamed_slab; the layout and which tile that is: see
+        include/acg_ldpc.h).  fp32 and fp32 for the streamed float layered decoders, int16 and int8 for
+        StreamedQuantizedMinSumDecoder; edges in processing order.  Any other decoder is refused by the library."""
+        h, code = self.handle(H)
+        size = C.c_int64()
+        check(lib().acg_ldpc_debug_streamed_slab(h, int(slab), None, 0, C.byref(size)))
+        tp, tr = (np.int16, np.int8) if isinstance(self, QuantizedMinSumDecoder) else (np.float32, np.float32)
+        n, E = code.n, code.E
+        nbytes = 64 * (n * np.dtype(tp).itemsize + E * np.dtype(tr).itemsize)
+        if nbytes > size.value:
+            raise _lib.LdpcError("a slab of %d bytes does not hold P[%d][64] and R[%d][64]" % (size.value, n, E))
+        buf = np.empty(nbytes, dtype=np.uint8)
+        check(lib().acg_ldpc_debug_streamed_slab(h, int(slab), buf.ctypes.data, nbytes, C.byref(size)))
+        split = 64 * n * np.dtype(tp).itemsize
+        P = buf[:split].view(tp).reshape(n, 64).T.copy()
+        R = buf[split:].view(tr).reshape(E, 64).T.copy()
+        return P, R
+
     def layout(self, H):
         h, _ = self.handle(H)
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()

@@ -713,6 +713,20 @@ int acg_ldpc_debug_layers_wide(const acg_ldpc_code *code, int32_t *n_layers, int
  * acg_ldpc_debug_layers_wide otherwise (non-zero only for a matrix without checks). */
 int acg_ldpc_debug_layers_any(const acg_ldpc_code *code, int32_t *n_layers, int32_t *width, int32_t *qc_Z, int32_t *chk, int64_t cap);
 
+/* diagnostics (host code only: a wait and a copy, no kernel): the state a handle of acg_ldpc_decoder_create_layered_streamed or
+ * acg_ldpc_decoder_create_quantized_streamed keeps in its workspace for the tile that used slab `slab` last.  Waits for the
+ * device, then copies min(cap_bytes, *slab_bytes) bytes of the slab to out_host.  *slab_bytes (required) is always written: the
+ * bytes of one slab, 0 where the handle is refused; out_host = NULL is the size query.  Layout of a slab, T = 64:
+ *   float engine      P[n][T] fp32 posteriors (sum-product: in the kernels' log2(e)-scaled domain), then R[E][T] fp32 messages,
+ *                     then the scratch of wide sum-product checks (unspecified content), rounded up to 256 bytes;
+ *   quantised engine  P[n][T] int16 posteriors, then R[E][T] int8 messages, rounded up to 256 bytes.
+ * Edges are in processing order: the sets of acg_ldpc_debug_layers_any, set by set, each check's variables ascending.  Lane l
+ * of the slab is frame 64 tile + l of the launch.  A workgroup takes tiles as they come, so which tile a slab held last is
+ * known only with one slab (ACG_STREAML_TILES=1 / ACG_STREAMQ_TILES=1 at creation: slab 0 holds the last tile of the last
+ * launch).  P of a lane beyond the launch's frames is +0; its R, and every R after a launch with max_iter = 0, is unspecified.
+ * Refused with a message: a null handle, a handle of any other create call, slab outside 0 ... tiles - 1, a negative cap_bytes. */
+int acg_ldpc_debug_streamed_slab(acg_ldpc_decoder *d, int32_t slab, void *out_host, int64_t cap_bytes, int64_t *slab_bytes);
+
 #ifdef __cplusplus
 }
 #endif

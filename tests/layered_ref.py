@@ -72,11 +72,21 @@ def _run_layered(Hm, layers, P, max_iter, layer_step):
     return bits, ok, iters
 
 
-def layered_minsum(Hm, layers, y, snr, max_iter, scale, msg_dtype=np.float32, symbols_f32=False):
+def _messages_in_processing_order(layers, of_check, F):
+    """[F, E] fp32: the messages of the checks of `layers`, set by set in processing order, each check's edges in the order the
+    restatement took them (of_check(c) -> [F, D])"""
+    parts = [of_check(c) for layer in layers for c in np.asarray(layer)[np.asarray(layer) >= 0]]
+    return np.concatenate(parts + [np.zeros((F, 0), dtype=np.float32)], axis=1).astype(np.float32)
+
+
+def layered_minsum(Hm, layers, y, snr, max_iter, scale, msg_dtype=np.float32, symbols_f32=False, posteriors=None, messages=None):
     """Hm: m x n 0/1; layers: [n_layers, G] check ids (-1 = none) in processing order; y: frames x n symbols.
     msg_dtype: storage type of the check-to-variable messages (np.float16 = precision PREC_F16: the scaled minima are rounded
     to half precision once per check; the posteriors stay fp32 and add / subtract exactly the rounded message).
     symbols_f32: the symbols reach the kernel as float32 (the (double) y * (2 / var) LLR path).
+    posteriors: optional list; the final [F, n] fp32 posteriors are appended to it.
+    messages: optional list; the final [F, E] fp32 messages are appended to it, edges in processing order (the sets of `layers`,
+    set by set, each check's variables ascending).
     -> bits [F, n] uint8 (zeros for failed frames), ok [F] uint8, iters [F] int32"""
     Hm = np.asarray(Hm)
     F, n = y.shape
@@ -112,7 +122,12 @@ def layered_minsum(Hm, layers, y, snr, max_iter, scale, msg_dtype=np.float32, sy
             P[np.ix_(live, v)] = pn[live]
             R[c][live] = rn[live]
         return loud
-    return _run_layered(Hm, layers, P, max_iter, layer_step)
+    res = _run_layered(Hm, layers, P, max_iter, layer_step)
+    if posteriors is not None:
+        posteriors.append(P)
+    if messages is not None:
+        messages.append(_messages_in_processing_order(layers, lambda c: R[c], F))
+    return res
 
 
 def host_phi(x):
@@ -166,7 +181,7 @@ def spa_messages(q, phi, msg_dtype=np.float32, variant=None):
 
 
 def layered_sumproduct_exact(Hm, layers, y, snr, max_iter, phi, msg_dtype=np.float32, symbols_f32=False, variant=None,
-                             posteriors=None):
+                             posteriors=None, messages=None):
     """fp32 restatement of the SUM-PRODUCT layered kernel (layer_back_spa), operation for operation, in the log2(e)-scaled
     message domain.  phi: float32 array -> float32 array of the same shape, the map F of Dom<float>::phi; with the device's own
     (acg_ldpc_debug_phi_sat) every other operation is reproduced exactly: word, flag and iteration count of every frame are
@@ -183,6 +198,8 @@ def layered_sumproduct_exact(Hm, layers, y, snr, max_iter, phi, msg_dtype=np.flo
     each check at its last variable; "suffix_ascending" accumulates the suffix sums in ascending edge order; "round_twice"
     rounds out to msg_dtype twice (idempotent: the kernel's second (RT) at the store).
     posteriors: optional list; the final [F, n] fp32 posteriors are appended to it.
+    messages: optional list; the final [F, E] fp32 messages are appended to it, edges in processing order (the sets of `layers`,
+    set by set, each check's edges in the order this run took them: variables ascending unless a variant says otherwise).
     -> bits [F, n] uint8 (zeros for failed frames), ok [F] uint8, iters [F] int32"""
     assert variant in (None, "reverse_edges", "rotate_edges", "suffix_ascending", "round_twice")
     Hm = np.asarray(Hm)
@@ -214,6 +231,8 @@ def layered_sumproduct_exact(Hm, layers, y, snr, max_iter, phi, msg_dtype=np.flo
     res = _run_layered(Hm, layers, P, max_iter, layer_step)
     if posteriors is not None:
         posteriors.append(P)
+    if messages is not None:
+        messages.append(np.concatenate([R[li].reshape(F, -1) for li in sorted(R)] + [np.zeros((F, 0), dtype=np.float32)], axis=1))
     return res
 
 

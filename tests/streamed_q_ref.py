@@ -24,9 +24,11 @@ def single_check_layers(edges):
     return [[c] for c, e in enumerate(edges) if len(e)]
 
 
-def decode_int_sparse(edges, n, layers, c, max_iter, quant=DEFAULT):
+def decode_int_sparse(edges, n, layers, c, max_iter, quant=DEFAULT, messages=None):
     """edges: check -> variables ascending; layers: sets of check ids in processing order (-1 = none); c: frames x n integer
     channel values.
+    messages: optional list; the final [F, E] int8 messages are appended to it, edges in processing order (the sets of `layers`,
+    set by set, each check's variables ascending).
     -> bits [F, n] uint8 (zeros for failed frames), ok [F] uint8, iters [F] int32, post [F, n] int16"""
     P = clamp_channel(c, quant)
     F = P.shape[0]
@@ -67,4 +69,8 @@ def decode_int_sparse(edges, n, layers, c, max_iter, quant=DEFAULT):
         bits[good] = hb[~bad]
         ok[good] = 1
     assert np.abs(P).max(initial=0) <= limits(quant)[2]
+    if messages is not None:
+        R = np.concatenate([r.reshape(F, -1) for _, r in sets] + [np.zeros((F, 0), dtype=np.int32)], axis=1)
+        assert np.abs(R).max(initial=0) <= 127
+        messages.append(R.astype(np.int8))
     return bits, ok, iters, P.astype(np.int16)
