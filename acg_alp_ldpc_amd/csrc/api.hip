@@ -586,19 +586,32 @@ static int quant_params_check(const acg_ldpc_params &p) {
     return 0;
 }
 
-// what acg_ldpc_decoder_create_quantized_streamed requires of the params (include/acg_ldpc.h); host only
-static int streamq_params_check(const acg_ldpc_params &p) {
+// what the two streamed layered engines require of the params, in the order in which a message wins.  algo_why: the engine's own
+// objection to p.algo, or null; precision_why: its text for a precision other than the default.  Host only.
+static int streamed_layered_params_check(const acg_ldpc_params &p, const char *what, const char *algo_why, const char *precision_why) {
     const char *why = nullptr;
-    if (p.algo != ACG_LDPC_BP_MINSUM) why = "algo must be ACG_LDPC_BP_MINSUM";
+    if (algo_why) why = algo_why;
     else if (p.schedule != ACG_LDPC_SCHEDULE_LAYERED) why = "schedule must be ACG_LDPC_SCHEDULE_LAYERED";
-    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (the number formats are the quantiser's)";
+    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = precision_why;
     else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_STREAMED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (the state lives in device memory)";
     else if (p.lanes_per_frame != 0) why = "lanes_per_frame must be 0 (one lane is one frame)";
     if (why) {
-        set_error(std::string("streamed quantized layered min-sum: ") + why);
+        set_error(std::string(what) + why);
         return 3;
     }
     return 0;
+}
+
+// what acg_ldpc_decoder_create_quantized_streamed requires of the params (include/acg_ldpc.h)
+static int streamq_params_check(const acg_ldpc_params &p) {
+    return streamed_layered_params_check(p, "streamed quantized layered min-sum: ", p.algo != ACG_LDPC_BP_MINSUM ? "algo must be ACG_LDPC_BP_MINSUM" : nullptr,
+                                         "precision must be ACG_LDPC_PREC_DEFAULT (the number formats are the quantiser's)");
+}
+// what acg_ldpc_decoder_create_layered_streamed requires of them
+static int streaml_params_check(const acg_ldpc_params &p) {
+    return streamed_layered_params_check(p, "streamed layered BP: ",
+                                         p.algo != ACG_LDPC_BP_SUMPRODUCT && p.algo != ACG_LDPC_BP_MINSUM ? "algo must be ACG_LDPC_BP_SUMPRODUCT or ACG_LDPC_BP_MINSUM" : nullptr,
+                                         "precision must be ACG_LDPC_PREC_DEFAULT (posteriors and messages are fp32)");
 }
 
 // the checks of the streamed layered engines in processing order — the sets of `ll`, set by set — as a plain CSR
@@ -616,111 +629,43 @@ static void streamed_layered_csr(const Code &c, const LayeredBlockLayout &ll, st
     }
 }
 
-// Streamed fixed-point layered min-sum (bp_streamed_q.hip): a quantized handle whose frames live in slabs of device memory, one
-// per resident tile.  Any n, m, E and any check degree: the checks are the sets of bp_layered_block_build without a degree cap,
-// set by set, as a plain CSR.
-static int decoder_setup_streamq(acg_ldpc_decoder *d) {
+// Resident tiles per CU of the streamed layered engines, at most.
+// The integer engine, measured on frames that never latch, 4 / 8 / 12 / 16 / 20 per CU: 386 / 576 / 762 / 780 / 770 k frames/s on the
+// (3,6) 5000 x 10000, 153 / 233 / 223 / 223 from 8 on the 2050 x 41000 of degree 40; DESIGN 3h.
+// The float engine at 4 / 8 / 12 / 16 per CU, 25 iterations fixed, k frames/s (tools/streamed_layered_rate.py): (3,6)
+// 5000 x 10000 at +2 dB, sum-product 332 / 477 / 701 / 680, min-sum 421 / 581 / 844 / 772; 2050 x 41000 of degree 40 at 5.3 dB, where
+// a quarter of the free memory holds 8.9 per CU whatever is asked beyond that, sum-product 88 / 123 / 115 / 126, min-sum 121 / 141 /
+// 134 / 140 (the last two columns are one configuration).
+constexpr int STREAMED_LAYERED_TILES_PER_CU = 12;
+
+// What the two streamed layered engines set up alike: the checks — the sets of bp_layered_block_build without a degree cap, set
+// by set — as a plain CSR on the device, the slab of a tile of 64 frames at bytes_per_frame (P, R and the engine's scratch), the
+// tiles and their slabs, and the handle's launch shape.  Any n, m, E and any check degree.
+// `what` opens the error texts; tiles_env and per_cu_env (or null) name the engine's developer switches.
+static int decoder_setup_streamed_layered(acg_ldpc_decoder *d, const void *kernel, size_t bytes_per_frame, const char *what, const char *tiles_env,
+                                          const char *per_cu_env) {
     const Code &c = d->c;
     if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
     std::vector<int32_t> row_ptr, edge_var;
     streamed_layered_csr(c, d->lblay, row_ptr, edge_var);
-    StreamQTables &t = d->sqtab;
+    StreamLayTables &t = d->sltab;
     if (!(t.row_ptr = upload_keep(row_ptr, d->dev_allocs))) return 10;
     if (!(t.edge_var = upload_keep(edge_var, d->dev_allocs))) return 10;
     t.m = (int32_t) row_ptr.size() - 1;
     t.n = c.n;
-    t.E = (int32_t) edge_var.size();
-    t.nwords = (c.n + 31) / 32;
-    const void *kp = bp_streamed_q_kernel_ptr();
-    const int T = 64;   // one lane is one frame
-    const size_t per_frame = 2 * (size_t) c.n + (size_t) t.E;
-    const size_t slab = (per_frame * T + 255) & ~(size_t) 255;
-    t.slab_bytes = (int64_t) slab;
-    // tiles: the resident wavefronts of the kernel, at most 12 per CU (measured on frames that never latch, 4 / 8 / 12 / 16 / 20 per
-    // CU: 386 / 576 / 762 / 780 / 770 k frames/s on the (3,6) 5000 x 10000, 153 / 233 / 223 / 223 from 8 on the 2050 x 41000 of
-    // degree 40), as many as a quarter of the free memory holds, and no more than ACG_STREAMQ_TILES (developer
-    // switch: tests force the reuse of a slab)
-    int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, 64, 0));
-    int64_t tiles = (int64_t) std::max(1, std::min(occ, 12)) * d->cu_count;
-    size_t free_b = 0, total_b = 0;
-    HIP_OK(hipMemGetInfo(&free_b, &total_b));
-    const int64_t fit = (int64_t) (free_b / 4 / slab);
-    if (fit < 1) {
-        set_error("streamed quantized layered min-sum: not one tile of " + std::to_string(T) + " frames (" + std::to_string(slab) +
-                  " bytes) fits in a quarter of the device's free memory (" + std::to_string(free_b / 4) + " bytes)");
-        return 3;
-    }
-    tiles = std::min(tiles, fit);
-    if (const char *e = getenv("ACG_STREAMQ_TILES")) {
-        const long want = atol(e);
-        if (want >= 1) tiles = std::min<int64_t>(tiles, want);
-    }
-    if (int rc = d->sq_ws.reserve((size_t) tiles * slab)) return rc;
-    d->streamq = true;
-    d->sq_tiles = (int) tiles;
-    d->layered_wg = acg_ldpc_decoder::LayeredWg::q;   // a quantized handle: the integer entrances and the unfused Monte-Carlo route take it
-    d->qargs = quant_args(d->quant);
-    d->kernel[0] = kp;
-    d->kernel[1] = nullptr;
-    d->L = 1;
-    d->f64 = 0;
-    d->block = 64;
-    d->frames_per_block = T;
-    d->lds_block = 0;
-    d->grid_cap[0] = d->grid_cap[1] = (int) tiles;
-    d->tab.lds_bytes_per_frame = 0;
-    return 0;
-}
-
-// what acg_ldpc_decoder_create_layered_streamed requires of the params (include/acg_ldpc.h); host only
-static int streaml_params_check(const acg_ldpc_params &p) {
-    const char *why = nullptr;
-    if (p.algo != ACG_LDPC_BP_SUMPRODUCT && p.algo != ACG_LDPC_BP_MINSUM) why = "algo must be ACG_LDPC_BP_SUMPRODUCT or ACG_LDPC_BP_MINSUM";
-    else if (p.schedule != ACG_LDPC_SCHEDULE_LAYERED) why = "schedule must be ACG_LDPC_SCHEDULE_LAYERED";
-    else if (p.precision != ACG_LDPC_PREC_DEFAULT) why = "precision must be ACG_LDPC_PREC_DEFAULT (posteriors and messages are fp32)";
-    else if (p.engine != ACG_LDPC_ENGINE_AUTO && p.engine != ACG_LDPC_ENGINE_STREAMED) why = "engine must be ACG_LDPC_ENGINE_AUTO or ACG_LDPC_ENGINE_STREAMED (the state lives in device memory)";
-    else if (p.lanes_per_frame != 0) why = "lanes_per_frame must be 0 (one lane is one frame)";
-    if (why) {
-        set_error(std::string("streamed layered BP: ") + why);
-        return 3;
-    }
-    return 0;
-}
-
-// Streamed float layered BP (bp_streamed_layered.hip): sum-product or min-sum, fp32 posteriors and messages in slabs of device
-// memory, one per resident tile.  Any n, m, E and any check degree; the checks as for decoder_setup_streamq.
-// Resident tiles per CU: the integer engine's 12.  Measured for this kernel at 4 / 8 / 12 / 16 per CU, 25 iterations fixed, k frames/s
-// (tools/streamed_layered_rate.py): (3,6) 5000 x 10000 at +2 dB, sum-product 332 / 477 / 701 / 680, min-sum 421 / 581 /
-// 844 / 772; 2050 x 41000 of degree 40 at 5.3 dB, where a quarter of the free memory holds 8.9 per CU whatever is asked beyond
-// that, sum-product 88 / 123 / 115 / 126, min-sum 121 / 141 / 134 / 140 (the last two columns are one configuration).
-constexpr int STREAML_TILES_PER_CU = 12;
-static int decoder_setup_streaml(acg_ldpc_decoder *d) {
-    const Code &c = d->c;
-    if (!bp_layered_block_build(c, d->lblay, INT32_MAX)) return 3;
-    std::vector<int32_t> row_ptr, edge_var;
-    streamed_layered_csr(c, d->lblay, row_ptr, edge_var);
-    StreamLTables &t = d->sltab;
-    if (!(t.row_ptr = upload_keep(row_ptr, d->dev_allocs))) return 10;
-    if (!(t.edge_var = upload_keep(edge_var, d->dev_allocs))) return 10;
-    t.m = (int32_t) row_ptr.size() - 1;
-    t.n = c.n;
-    t.E = (int32_t) edge_var.size();
+    t.E = (int32_t) edge_var.size();   // (= c.E, and max_deg = c.max_cdeg: every check with a variable is in one set)
     t.nwords = (c.n + 31) / 32;
     t.max_deg = 0;
     for (int i = 0; i < t.m; i++) t.max_deg = std::max(t.max_deg, row_ptr[i + 1] - row_ptr[i]);
-    const int algo = d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1;
-    const void *kp = bp_streamed_layered_kernel_ptr(algo);
     const int T = 64;   // one lane is one frame
-    const size_t per_frame = 4 * ((size_t) c.n + (size_t) t.E + bp_streamed_layered_scratch_words(algo, t.max_deg));
-    const size_t slab = (per_frame * T + 255) & ~(size_t) 255;
+    const size_t slab = (bytes_per_frame * T + 255) & ~(size_t) 255;
     t.slab_bytes = (int64_t) slab;
-    // tiles: the resident wavefronts of the kernel, at most STREAML_TILES_PER_CU per CU, as many as a quarter of the free memory
-    // holds, and no more than ACG_STREAML_TILES (developer switch: tests force the reuse of a slab)
+    // tiles: the resident wavefronts of the kernel, at most STREAMED_LAYERED_TILES_PER_CU per CU, as many as a quarter of the free
+    // memory holds, and no more than tiles_env asks for (developer switch: tests force the reuse of a slab)
     int occ = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, 64, 0));
-    int64_t per_cu = std::max(1, std::min(occ, STREAML_TILES_PER_CU));
-    if (const char *e = getenv("ACG_STREAML_PER_CU")) {   // (developer switch: the sweep next to the constant)
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 64, 0));
+    int64_t per_cu = std::max(1, std::min(occ, STREAMED_LAYERED_TILES_PER_CU));
+    if (const char *e = per_cu_env ? getenv(per_cu_env) : nullptr) {   // (developer switch: the sweep next to the constant)
         const long want = atol(e);
         if (want >= 1) per_cu = std::max<int64_t>(1, std::min<int64_t>(occ, want));
     }
@@ -729,19 +674,18 @@ static int decoder_setup_streaml(acg_ldpc_decoder *d) {
     HIP_OK(hipMemGetInfo(&free_b, &total_b));
     const int64_t fit = (int64_t) (free_b / 4 / slab);
     if (fit < 1) {
-        set_error("streamed layered BP: not one tile of " + std::to_string(T) + " frames (" + std::to_string(slab) +
+        set_error(what + ("not one tile of " + std::to_string(T)) + " frames (" + std::to_string(slab) +
                   " bytes) fits in a quarter of the device's free memory (" + std::to_string(free_b / 4) + " bytes)");
         return 3;
     }
     tiles = std::min(tiles, fit);
-    if (const char *e = getenv("ACG_STREAML_TILES")) {
+    if (const char *e = getenv(tiles_env)) {
         const long want = atol(e);
         if (want >= 1) tiles = std::min<int64_t>(tiles, want);
     }
     if (int rc = d->sl_ws.reserve((size_t) tiles * slab)) return rc;
-    d->streaml = true;
     d->sl_tiles = (int) tiles;
-    d->kernel[0] = kp;
+    d->kernel[0] = kernel;
     d->kernel[1] = nullptr;
     d->L = 1;
     d->f64 = 0;
@@ -750,6 +694,28 @@ static int decoder_setup_streaml(acg_ldpc_decoder *d) {
     d->lds_block = 0;
     d->grid_cap[0] = d->grid_cap[1] = (int) tiles;
     d->tab.lds_bytes_per_frame = 0;
+    return 0;
+}
+
+// Streamed fixed-point layered min-sum (bp_streamed_q.hip): a quantized handle whose frames live in slabs of device memory, one
+// per resident tile: 2 n + E bytes of a frame.
+static int decoder_setup_streamq(acg_ldpc_decoder *d) {
+    const size_t per_frame = 2 * (size_t) d->c.n + (size_t) d->c.E;
+    if (int rc = decoder_setup_streamed_layered(d, bp_streamed_q_kernel_ptr(), per_frame, "streamed quantized layered min-sum: ", "ACG_STREAMQ_TILES", nullptr)) return rc;
+    d->streamq = true;
+    d->layered_wg = acg_ldpc_decoder::LayeredWg::q;   // a quantized handle: the integer entrances and the unfused Monte-Carlo route take it
+    d->qargs = quant_args(d->quant);
+    return 0;
+}
+
+// Streamed float layered BP (bp_streamed_layered.hip): sum-product or min-sum, fp32 posteriors and messages in slabs of device
+// memory, one per resident tile: n + E words of a frame and the scratch of a wide sum-product check.
+static int decoder_setup_streaml(acg_ldpc_decoder *d) {
+    const int algo = d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1;
+    const size_t per_frame = 4 * ((size_t) d->c.n + (size_t) d->c.E + bp_streamed_layered_scratch_words(algo, d->c.max_cdeg));
+    if (int rc = decoder_setup_streamed_layered(d, bp_streamed_layered_kernel_ptr(algo), per_frame, "streamed layered BP: ", "ACG_STREAML_TILES", "ACG_STREAML_PER_CU"))
+        return rc;
+    d->streaml = true;
     return 0;
 }
 
@@ -1326,8 +1292,8 @@ static std::string describe(const acg_ldpc_decoder *d) {
         snprintf(b, sizeof b, "%s engine=streamed kernel=bp_streamed_q_kernel schedule=layered T=%d tiles=%d state_bytes_per_frame=%zu "
                                "slab_bytes=%lld workspace_bytes=%zu workspace=hipMalloc sets=%d checks=%d messages=int8 posteriors=int16 "
                                "quant=llr_step:%.9g,ch_bits:%d,msg_bits:%d,post_bits:%d,scale_num:%d,scale_shift:%d,offset:%d mc_quants=refused",
-                 algo, d->frames_per_block, d->sq_tiles, 2 * (size_t) d->c.n + (size_t) d->sqtab.E, (long long) d->sqtab.slab_bytes,
-                 (size_t) d->sq_tiles * (size_t) d->sqtab.slab_bytes, d->lblay.n_sets, d->sqtab.m, q.llr_step, q.ch_bits, q.msg_bits, q.post_bits,
+                 algo, d->frames_per_block, d->sl_tiles, 2 * (size_t) d->c.n + (size_t) d->sltab.E, (long long) d->sltab.slab_bytes,
+                 (size_t) d->sl_tiles * (size_t) d->sltab.slab_bytes, d->lblay.n_sets, d->sltab.m, q.llr_step, q.ch_bits, q.msg_bits, q.post_bits,
                  q.scale_num, q.scale_shift, q.offset);
     } else if (d->layered_wg == acg_ldpc_decoder::LayeredWg::q) {
         const acg_ldpc_quant &q = d->quant;

@@ -7,7 +7,9 @@
 // calling lane's check: the group width in bp_layered.hip (R[layer][edge][lane]), 1 in bp_layered_block.hip (R[check][edge]).
 
 typedef const int32_t __attribute__((address_space(4))) *lsconst_i32;
-__device__ __forceinline__ int lsload(const int32_t *p, int i) { return ((lsconst_i32) (p))[i]; }
+// a wave-uniform scalar load (I: int here, size_t in the streamed layered engines, whose edge numbers are size_t throughout)
+template <typename I>
+__device__ __forceinline__ int lsload(const int32_t *p, I i) { return ((lsconst_i32) (p))[i]; }
 
 constexpr int LMAXD = 8;
 constexpr float LAYERED_SATURATION = 59968.0f;   // message of a one-variable check ("certainly 0"); representable in fp16

@@ -25,14 +25,9 @@
 // area holds the prefixes alone, base[ceil(Dmax / 8)][T].  Reading it back from a scratch area mag[Dmax][T] that pass 1 fills (two
 // phi, 8 bytes more per edge; ACG_SL_STORE_MAG=1) was measured and was 12 to 18 % slower: DESIGN 3i.
 //
-// Control: layered_ref._run_layered, the lines of bp_streamed_q_kernel.  A frame latches after the first iteration in which every
-// check was quiet; from then on its lane computes on but writes nothing of P or R, so its P stays the latched posterior.  Frames
-// out of iterations get one syndrome pass.  early_exit = 1 ends the tile when every frame of it has latched; early_exit = 0 runs
-// max_iter rounds; the outputs are the same.
-//
-// No stale state: a tile writes every P cell of its slab at its start (tail frames: 0), and in its first iteration takes every
-// message as 0 WITHOUT reading R and writes it, so every R cell a live frame reads later was written by that frame in this
-// tile; a scratch cell is written by pass 1 of the check whose pass 2 reads it.
+// The tile loop — the claim of a tile, the iterations and the latch, the syndrome pass, the outputs — is streamed_tile_loop of
+// bp_streamed_tile.inc, shared with bp_streamed_q.hip; "Control" and "No stale state" are written there.  Of this engine's own:
+// a scratch cell is written by pass 1 of the check whose pass 2 reads it.
 #include <hip/hip_runtime.h>
 
 #include "launchers.hpp"
@@ -40,10 +35,8 @@
 namespace acg {
 #include "bp_core.inc"   // Dom<float>::phi for the sum-product instance
 #include "bp_layer_math.inc"
+#include "bp_streamed_tile.inc"
 
-__device__ __forceinline__ int sl_sload(const int32_t *p, size_t i) { return ((lsconst_i32) (p))[i]; }
-
-constexpr int SL_T = 64;              // frames of a tile: one per lane
 // sum-product, wide checks: pass 2 forms mag_j again (0) or reads it back (1; make EXTRA=-DACG_SL_STORE_MAG=1, the build that
 // tools/streamed_layered_rate.py measured this one against: DESIGN 3i)
 #ifndef ACG_SL_STORE_MAG
@@ -57,13 +50,18 @@ __device__ __forceinline__ float sl_abs(const float x) { return __uint_as_float(
 // ALGO: 1 = normalised min-sum, 0 = sum-product
 template <int ALGO>
 struct SlTile {
-    float *P;            // this lane's posterior of variable v: P[(size_t) v * SL_T]
-    float *R;            // this lane's message of edge e: R[(size_t) e * SL_T]
-    float *M;            // this lane's scratch: mag of the j-th edge of the wide check under way, M[(size_t) j * SL_T]
-    float *B;            // ... and its prefix sum at the start of chunk c, B[(size_t) c * SL_T]
+    float *P;            // this lane's posterior of variable v: P[(size_t) v * TILE_T]
+    float *R;            // this lane's message of edge e: R[(size_t) e * TILE_T]
+    float *M;            // this lane's scratch: mag of the j-th edge of the wide check under way, M[(size_t) j * TILE_T]
+    float *B;            // ... and its prefix sum at the start of chunk c, B[(size_t) c * TILE_T]
     const int32_t *ev;
+    float *X;            // the workgroup's transposing buffer: XV variables x T frames, rows of XS words
+    const DecodeArgs *a; // the channel values and terms of fill()
+    int n;
     float scale;
-    bool first;      // the tile's first iteration: every message is 0 and R is not read
+    static constexpr int XV = 32;           // variables of a trip through the transposing buffer
+    static constexpr int XS = TILE_T + 1;   // words per row of it: rows an odd number of words apart
+    bool first;     // the tile's first iteration: every message is 0 and R is not read
     bool live;       // the frame is updated: it exists and has not latched
     uint32_t loud;   // bit 0: some step of the iteration was not quiet for this frame
 
@@ -72,11 +70,11 @@ struct SlTile {
     __device__ __forceinline__ void load(const size_t e, float *(&addr)[LMAXD], float (&p)[LMAXD], float (&q)[LMAXD]) const {
         float r[LMAXD];
 #pragma unroll
-        for (int j = 0; j < N; ++j) addr[j] = P + (size_t) sl_sload(ev, e + j) * SL_T;
+        for (int j = 0; j < N; ++j) addr[j] = P + (size_t) lsload(ev, e + j) * TILE_T;
 #pragma unroll
         for (int j = 0; j < N; ++j) p[j] = *addr[j];
 #pragma unroll
-        for (int j = 0; j < N; ++j) r[j] = first ? 0.0f : R[(e + j) * SL_T];
+        for (int j = 0; j < N; ++j) r[j] = first ? 0.0f : R[(e + j) * TILE_T];
 #pragma unroll
         for (int j = 0; j < N; ++j) q[j] = p[j] - r[j];
     }
@@ -88,8 +86,8 @@ struct SlTile {
         float p[LMAXD], q[LMAXD];
         load<D>(e, addr, p, q);
         uint32_t noisy;
-        if constexpr (ALGO == 0) noisy = layer_back_spa<D, SL_T, float>(R + e * SL_T, addr, p, q, live);
-        else noisy = layer_back<D, SL_T, float>(R + e * SL_T, addr, p, q, live, scale);
+        if constexpr (ALGO == 0) noisy = layer_back_spa<D, TILE_T, float>(R + e * TILE_T, addr, p, q, live);
+        else noisy = layer_back<D, TILE_T, float>(R + e * TILE_T, addr, p, q, live, scale);
         loud |= noisy >> 31;
     }
 
@@ -107,7 +105,7 @@ struct SlTile {
         float *addr[LMAXD];
         float p[LMAXD], q[LMAXD];
         load<N>(e, addr, p, q);
-        if constexpr (ALGO == 0) B[(size_t) c * SL_T] = w.s;
+        if constexpr (ALGO == 0) B[(size_t) c * TILE_T] = w.s;
 #pragma unroll
         for (int j = 0; j < N; ++j) {
             w.parity ^= sl_bits(p[j]);                      // parity of the hard decisions this check sees
@@ -115,7 +113,7 @@ struct SlTile {
             const float a = sl_abs(q[j]);
             if constexpr (ALGO == 0) {
                 const float m = Dom<float>::phi(a);
-                if constexpr (SL_STORE_MAG) M[(size_t) (c * LMAXD + j) * SL_T] = m;
+                if constexpr (SL_STORE_MAG) M[(size_t) (c * LMAXD + j) * TILE_T] = m;
                 w.s += m;
             } else {
                 w.m2 = __builtin_amdgcn_fmed3f(a, w.m1, w.m2);
@@ -132,10 +130,10 @@ struct SlTile {
         if constexpr (ALGO == 0) {
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-                if constexpr (SL_STORE_MAG) mag[j] = M[(size_t) (c * LMAXD + j) * SL_T];
+                if constexpr (SL_STORE_MAG) mag[j] = M[(size_t) (c * LMAXD + j) * TILE_T];
                 else mag[j] = Dom<float>::phi(sl_abs(q[j]));
             }
-            float t = B[(size_t) c * SL_T];
+            float t = B[(size_t) c * TILE_T];
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 pre[j] = t;
@@ -161,20 +159,8 @@ struct SlTile {
 #pragma unroll
             for (int j = 0; j < N; ++j) *addr[j] = pn[j];
 #pragma unroll
-            for (int j = 0; j < N; ++j) R[(e + j) * SL_T] = rn[j];
+            for (int j = 0; j < N; ++j) R[(e + j) * TILE_T] = rn[j];
         }
-    }
-
-#define ACG_SL_TAIL(n, CALL) \
-    switch (n) {             \
-        case 1: CALL(1); break; \
-        case 2: CALL(2); break; \
-        case 3: CALL(3); break; \
-        case 4: CALL(4); break; \
-        case 5: CALL(5); break; \
-        case 6: CALL(6); break; \
-        case 7: CALL(7); break; \
-        default: break;      \
     }
 
     // the check of the edges [e0, e1), e1 > e0 (wave-uniform)
@@ -191,7 +177,7 @@ struct SlTile {
         const size_t et = e0 + (size_t) full * LMAXD;
         for (int c = 0; c < full; ++c) pass1<LMAXD>(w, e0 + (size_t) c * LMAXD, c);
 #define ACG_CALL(N) pass1<N>(w, et, full)
-        ACG_SL_TAIL(tail, ACG_CALL)
+        ACG_TILE_TAIL(tail, ACG_CALL)
 #undef ACG_CALL
         // the two minima are scaled once per check (layer_back; D > 8, so no one-variable check here)
         if constexpr (ALGO == 1) {
@@ -200,45 +186,19 @@ struct SlTile {
             asm volatile("" : "+v"(w.m1s), "+v"(w.m2s));
         }
 #define ACG_CALL(N) pass2<N>(w, et, full)
-        ACG_SL_TAIL(tail, ACG_CALL)
+        ACG_TILE_TAIL(tail, ACG_CALL)
 #undef ACG_CALL
         for (int c = full - 1; c >= 0; --c) pass2<LMAXD>(w, e0 + (size_t) c * LMAXD, c);
         loud |= (w.parity | w.flipped) >> 31;
     }
-#undef ACG_SL_TAIL
-};
 
-// grid <= the slabs behind ws
-template <int ALGO>
-__global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLTables t, const DecodeArgs a, unsigned char *__restrict__ ws) {
-    constexpr int T = SL_T;
-    constexpr int XV = 32;      // variables of a trip through the transposing buffer
-    constexpr int XS = T + 1;   // words per row of it: rows an odd number of words apart
-    __shared__ float X[XV * XS];
-    const int l = threadIdx.x;
-    float *const slab = reinterpret_cast<float *>(ws + (size_t) blockIdx.x * (size_t) t.slab_bytes);
-    SlTile<ALGO> tl;
-    tl.P = slab + l;
-    tl.R = tl.P + (size_t) t.n * T;
-    tl.M = tl.R + (size_t) t.E * T;
-    tl.B = SL_STORE_MAG ? tl.M + (size_t) t.max_deg * T : tl.M;
-    tl.ev = t.edge_var;
-    tl.scale = a.ms_scale;
-    const int n = t.n;
+    __device__ __forceinline__ uint32_t sign(const int v) const { return sl_bits(P[(size_t) v * TILE_T]); }
 
-    for (;;) {
-        unsigned long long tv = 0;
-        if (l == 0) tv = atomicAdd(a.work_counter, 1ull);
-        const int64_t tile = (int64_t) (((unsigned long long) (uint32_t) __builtin_amdgcn_readfirstlane((int) (tv >> 32)) << 32) |
-                                        (uint32_t) __builtin_amdgcn_readfirstlane((int) tv));
-        const int64_t frame0 = tile * T;
-        if (frame0 >= a.frames) break;
-        const int nf = (int) (a.frames - frame0 < T ? a.frames - frame0 : T);   // frames of this tile (wave-uniform)
-        const bool exists = l < nf;
-        const size_t frame = (size_t) frame0 + l;
-
-        // ---- start of the tile: P = channel LLR (channel.h:14-16), [frame][n] -> [n][T] through LDS, 32 variables at a time; a
-        // lane takes one variable of every second frame -------------------------------------------------------------------------------
+    // start of the tile: P = channel LLR (channel.h:14-16), [frame][n] -> [n][T] through LDS, 32 variables at a time; a lane takes
+    // one variable of every second frame
+    __device__ __forceinline__ void fill(const int64_t frame0, const int nf) {
+        constexpr int T = TILE_T;
+        const int l = threadIdx.x;
         for (int v0 = 0; v0 < n; v0 += XV) {
             const int vl = l & (XV - 1), h = l / XV;
             const bool mine = v0 + vl < n;
@@ -249,68 +209,39 @@ __global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLTa
                 float x = 0.0f;
                 if (fr < nf && mine) {
                     float llr;
-                    if (a.y_is_f64) llr = (float) (2 * reinterpret_cast<const double *>(a.y)[y0 + (size_t) fr * n] / a.var);
-                    else llr = (float) ((double) reinterpret_cast<const float *>(a.y)[y0 + (size_t) fr * n] * a.inv_var2);
+                    if (a->y_is_f64) llr = (float) (2 * reinterpret_cast<const double *>(a->y)[y0 + (size_t) fr * n] / a->var);
+                    else llr = (float) ((double) reinterpret_cast<const float *>(a->y)[y0 + (size_t) fr * n] * a->inv_var2);
                     x = (ALGO == 0) ? llr * (float) Dom<float>::scale : llr;
                 }
                 X[vl * XS + fr] = x;
             }
             __syncthreads();
             const int nv = n - v0 < XV ? n - v0 : XV;
-            for (int vv = 0; vv < nv; ++vv) tl.P[(size_t) (v0 + vv) * T] = X[vv * XS + l];
+            for (int vv = 0; vv < nv; ++vv) P[(size_t) (v0 + vv) * T] = X[vv * XS + l];
             __syncthreads();
         }
-
-        bool latched = false;
-        int iters = a.max_iter;
-        tl.live = exists;
-        // ---- the iterations ------------------------------------------------------------------------------------------------------
-        for (int it = 1; it <= a.max_iter; ++it) {
-            if (a.early_exit && __ballot(tl.live) == 0ull) break;
-            tl.loud = 0;
-            tl.first = it == 1;
-            size_t e0 = (size_t) sl_sload(t.row_ptr, 0);
-            for (int i = 0; i < t.m; ++i) {
-                const size_t e1 = (size_t) sl_sload(t.row_ptr, (size_t) i + 1);
-                tl.check(e0, e1);
-                e0 = e1;
-            }
-            if (tl.live && (tl.loud & 1u) == 0u) {
-                latched = true;
-                iters = it;
-                tl.live = false;
-            }
-        }
-        // ---- frames out of iterations: one syndrome pass over the posteriors' signs ---------------------------------------------
-        bool good = latched;
-        if (a.max_iter > 0 && __ballot(tl.live) != 0ull) {
-            uint32_t bad = 0;
-            size_t e0 = (size_t) sl_sload(t.row_ptr, 0);
-            for (int i = 0; i < t.m; ++i) {
-                const size_t e1 = (size_t) sl_sload(t.row_ptr, (size_t) i + 1);
-                uint32_t S = 0;
-#pragma unroll 4
-                for (size_t e = e0; e < e1; ++e) S ^= sl_bits(tl.P[(size_t) sl_sload(t.edge_var, e) * T]);
-                bad |= S;
-                e0 = e1;
-            }
-            if (tl.live) good = (bad >> 31) == 0u;
-        }
-        // ---- the tile's outputs: packed words (zeros for a failed frame), flags, iterations -------------------------------------
-        if (exists) {
-            if (a.out_ok) a.out_ok[frame] = good ? 1 : 0;
-            if (a.out_iters) a.out_iters[frame] = iters;
-        }
-        if (a.out_bits) {
-            for (int w = 0; w < t.nwords; ++w) {
-                uint32_t word = 0;
-                const int nb = n - 32 * w < 32 ? n - 32 * w : 32;
-#pragma unroll 8
-                for (int b = 0; b < nb; ++b) word |= (sl_bits(tl.P[(size_t) (32 * w + b) * T]) >> 31) << b;
-                if (exists) a.out_bits[frame * t.nwords + w] = good ? word : 0u;
-            }
-        }
     }
+    __device__ __forceinline__ void drain(const int64_t, const int) {}   // (hard outputs only)
+};
+
+// grid <= the slabs behind ws
+template <int ALGO>
+__global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLayTables t, const DecodeArgs a, unsigned char *__restrict__ ws) {
+    constexpr int T = TILE_T;
+    __shared__ float X[SlTile<ALGO>::XV * SlTile<ALGO>::XS];
+    const int l = threadIdx.x;
+    float *const slab = reinterpret_cast<float *>(ws + (size_t) blockIdx.x * (size_t) t.slab_bytes);
+    SlTile<ALGO> tl;
+    tl.P = slab + l;
+    tl.R = tl.P + (size_t) t.n * T;
+    tl.M = tl.R + (size_t) t.E * T;
+    tl.B = SL_STORE_MAG ? tl.M + (size_t) t.max_deg * T : tl.M;
+    tl.ev = t.edge_var;
+    tl.X = X;
+    tl.a = &a;
+    tl.n = t.n;
+    tl.scale = a.ms_scale;
+    streamed_tile_loop(t, a, tl);
 }
 
 // algo: 0 sum-product, 1 min-sum
@@ -325,8 +256,14 @@ size_t bp_streamed_layered_scratch_words(int algo, int max_deg) {
 }
 bool bp_streamed_layered_stores_mag() { return SL_STORE_MAG; }
 
-hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLTables &t, const DecodeArgs &a, unsigned char *ws, int grid, hipStream_t s) {
-    void *args[] = {(void *) &t, (void *) &a, (void *) &ws};
+hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLayTables &t, const DecodeArgs &a, const QuantArgs *q, unsigned char *ws,
+                                      int grid, hipStream_t s) {
+    void *args[4];
+    int k = 0;
+    args[k++] = (void *) &t;
+    args[k++] = (void *) &a;
+    if (q) args[k++] = (void *) q;
+    args[k++] = (void *) &ws;
     return hipLaunchKernel(kernel, dim3((unsigned) grid), dim3(64), args, 0, s);
 }
 

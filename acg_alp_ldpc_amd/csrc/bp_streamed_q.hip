@@ -17,55 +17,50 @@
 // XOR of the signs and the parity and writes nothing; pass 2 reads P and R again and writes R' and P' (9 bytes per edge).  The
 // loads of a chunk are issued together.  Both forms are the four functions of quant_arith.hpp.
 //
-// Control: layered_ref._run_layered.  A frame latches after the first iteration in which every check was quiet; from then on
-// its lane computes on but writes nothing, so its P stays the latched posterior.  Frames out of iterations get one
-// syndrome pass.  early_exit = 1 ends the tile when every frame of it has latched; early_exit = 0 runs max_iter rounds; the
-// outputs are the same.
-//
-// No stale state: a tile writes every P cell of its slab at its start (tail frames: 0), and in its first iteration takes every
-// message as 0 WITHOUT reading R and writes it, so every R cell a live frame reads later was written by that frame in this
-// tile.  (A frame that is not live — the tail of the last tile — reads whatever the slab holds; nothing of it is written or
-// leaves.)
+// The tile loop — the claim of a tile, the iterations and the latch, the syndrome pass, the outputs — is streamed_tile_loop of
+// bp_streamed_tile.inc, shared with bp_streamed_layered.hip; "Control" and "No stale state" are written there.
 #include <hip/hip_runtime.h>
 
 #include "launchers.hpp"
 #include "quant_arith.hpp"
 
 namespace acg {
+#include "bp_core.inc"         // (what bp_layer_math.inc stands behind; none of its float arithmetic is used here)
+#include "bp_layer_math.inc"   // lsload, LMAXD, ACG_LAYER_SWITCH
+#include "bp_streamed_tile.inc"
 
-typedef const int32_t __attribute__((address_space(4))) *sqconst_i32;
-__device__ __forceinline__ int sq_sload(const int32_t *p, size_t i) { return ((sqconst_i32) (p))[i]; }
-
-constexpr int Q_SMALL = 8;
-constexpr int SQ_T = 64;   // frames of a tile: one per lane
+constexpr int Q_SMALL = LMAXD;   // edges of a chunk: the cells of a check a lane holds in registers
 
 struct SqTile {
-    short *P;            // this lane's posterior of variable v: P[(size_t) v * SQ_T]
-    signed char *R;      // this lane's message of edge e: R[(size_t) e * SQ_T]
+    short *P;            // this lane's posterior of variable v: P[(size_t) v * TILE_T]
+    signed char *R;      // this lane's message of edge e: R[(size_t) e * TILE_T]
     const int32_t *ev;
+    short *X;            // the workgroup's transposing buffer: 64 variables x T frames, rows of XS shorts
+    int n;
+    QuantArgs qa;        // c_in: frames * n channel values; post_out: frames * n posteriors or null
     bool first;      // the tile's first iteration: every message is 0 and R is not read
     bool live;       // the frame is updated: it exists and has not latched
-    uint32_t loud;
+    uint32_t loud;   // bit 0: some check of the iteration was not quiet for this frame
+    static constexpr int XS = TILE_T + 2;   // rows an odd number of words apart
 
     // N edges from e: the variables, and this lane's cells
     template <int N>
     __device__ __forceinline__ void load(const size_t e, int (&v)[N], int (&p)[N], int (&r)[N]) const {
 #pragma unroll
-        for (int j = 0; j < N; ++j) v[j] = sq_sload(ev, e + j);
+        for (int j = 0; j < N; ++j) v[j] = lsload(ev, e + j);
 #pragma unroll
-        for (int j = 0; j < N; ++j) p[j] = P[(size_t) v[j] * SQ_T];
+        for (int j = 0; j < N; ++j) p[j] = P[(size_t) v[j] * TILE_T];
 #pragma unroll
-        for (int j = 0; j < N; ++j) r[j] = first ? 0 : (int) R[(e + j) * SQ_T];
+        for (int j = 0; j < N; ++j) r[j] = first ? 0 : (int) R[(e + j) * TILE_T];
     }
     template <int N>
-    __device__ __forceinline__ void reduce(QCheck &ck, const int (&p)[N], const int (&r)[N], const QuantArgs &qa) const {
+    __device__ __forceinline__ void reduce(QCheck &ck, const int (&p)[N], const int (&r)[N]) const {
 #pragma unroll
         for (int j = 0; j < N; ++j) q_reduce(ck, p[j], p[j] - r[j], qa);
     }
     // new cells of N edges from e; a frame that is not live writes nothing
     template <int N>
-    __device__ __forceinline__ void update(const QCheck &ck, const size_t e, const int (&v)[N], const int (&p)[N], const int (&r)[N],
-                                           const QuantArgs &qa) {
+    __device__ __forceinline__ void update(const QCheck &ck, const size_t e, const int (&v)[N], const int (&p)[N], const int (&r)[N]) {
         int rn[N], pn[N];
         uint32_t flipped = 0;
 #pragma unroll
@@ -77,106 +72,64 @@ struct SqTile {
         if (live) {
 #pragma unroll
             for (int j = 0; j < N; ++j) {
-                P[(size_t) v[j] * SQ_T] = (short) pn[j];
-                R[(e + j) * SQ_T] = (signed char) rn[j];
+                P[(size_t) v[j] * TILE_T] = (short) pn[j];
+                R[(e + j) * TILE_T] = (signed char) rn[j];
             }
         }
     }
 
     template <int N>
-    __device__ __forceinline__ void small_check(const size_t e, const QuantArgs &qa) {
+    __device__ __forceinline__ void small_check(const size_t e) {
         int v[N], p[N], r[N];
         load<N>(e, v, p, r);
         QCheck ck;
         q_open(ck, qa);
-        reduce<N>(ck, p, r, qa);
+        reduce<N>(ck, p, r);
         q_close(ck, qa);
-        update<N>(ck, e, v, p, r, qa);
+        update<N>(ck, e, v, p, r);
     }
     template <int N>
-    __device__ __forceinline__ void pass1(QCheck &ck, const size_t e, const QuantArgs &qa) const {
+    __device__ __forceinline__ void pass1(QCheck &ck, const size_t e) const {
         int v[N], p[N], r[N];
         load<N>(e, v, p, r);
-        reduce<N>(ck, p, r, qa);
+        reduce<N>(ck, p, r);
     }
     template <int N>
-    __device__ __forceinline__ void pass2(const QCheck &ck, const size_t e, const QuantArgs &qa) {
+    __device__ __forceinline__ void pass2(const QCheck &ck, const size_t e) {
         int v[N], p[N], r[N];
         load<N>(e, v, p, r);
-        update<N>(ck, e, v, p, r, qa);
+        update<N>(ck, e, v, p, r);
     }
 
     // the check of the edges [e0, e1), e1 > e0 (wave-uniform)
-    __device__ __forceinline__ void check(const size_t e0, const size_t e1, const QuantArgs &qa) {
+    __device__ __forceinline__ void check(const size_t e0, const size_t e1) {
         const int D = (int) (e1 - e0);
         if (D <= Q_SMALL) {
-            switch (D) {
-                case 1: small_check<1>(e0, qa); break;
-                case 2: small_check<2>(e0, qa); break;
-                case 3: small_check<3>(e0, qa); break;
-                case 4: small_check<4>(e0, qa); break;
-                case 5: small_check<5>(e0, qa); break;
-                case 6: small_check<6>(e0, qa); break;
-                case 7: small_check<7>(e0, qa); break;
-                case 8: small_check<8>(e0, qa); break;
-                default: break;
-            }
+#define ACG_CALL(N) small_check<N>(e0)
+            ACG_LAYER_SWITCH(D, ACG_CALL)
+#undef ACG_CALL
             return;
         }
         QCheck ck;
         q_open(ck, qa);
         size_t e = e0;
-        for (; e + Q_SMALL <= e1; e += Q_SMALL) pass1<Q_SMALL>(ck, e, qa);
-        switch ((int) (e1 - e)) {
-            case 1: pass1<1>(ck, e, qa); break;
-            case 2: pass1<2>(ck, e, qa); break;
-            case 3: pass1<3>(ck, e, qa); break;
-            case 4: pass1<4>(ck, e, qa); break;
-            case 5: pass1<5>(ck, e, qa); break;
-            case 6: pass1<6>(ck, e, qa); break;
-            case 7: pass1<7>(ck, e, qa); break;
-            default: break;
-        }
+        for (; e + Q_SMALL <= e1; e += Q_SMALL) pass1<Q_SMALL>(ck, e);
+#define ACG_CALL(N) pass1<N>(ck, e)
+        ACG_TILE_TAIL((int) (e1 - e), ACG_CALL)
+#undef ACG_CALL
         q_close(ck, qa);
-        for (e = e0; e + Q_SMALL <= e1; e += Q_SMALL) pass2<Q_SMALL>(ck, e, qa);
-        switch ((int) (e1 - e)) {
-            case 1: pass2<1>(ck, e, qa); break;
-            case 2: pass2<2>(ck, e, qa); break;
-            case 3: pass2<3>(ck, e, qa); break;
-            case 4: pass2<4>(ck, e, qa); break;
-            case 5: pass2<5>(ck, e, qa); break;
-            case 6: pass2<6>(ck, e, qa); break;
-            case 7: pass2<7>(ck, e, qa); break;
-            default: break;
-        }
+        for (e = e0; e + Q_SMALL <= e1; e += Q_SMALL) pass2<Q_SMALL>(ck, e);
+#define ACG_CALL(N) pass2<N>(ck, e)
+        ACG_TILE_TAIL((int) (e1 - e), ACG_CALL)
+#undef ACG_CALL
     }
-};
 
-// grid <= the slabs behind ws.  qa.c_in: frames * n channel values; qa.post_out: frames * n posteriors or null.
-__global__ void __launch_bounds__(64) bp_streamed_q_kernel(const StreamQTables t, const DecodeArgs a, const QuantArgs qa, unsigned char *__restrict__ ws) {
-    constexpr int T = SQ_T;
-    constexpr int XS = T + 2;   // shorts per row of the transposing buffer: rows an odd number of words apart
-    __shared__ short X[64 * XS];   // 64 variables x T frames
-    const int l = threadIdx.x;
-    unsigned char *const slab = ws + (size_t) blockIdx.x * (size_t) t.slab_bytes;
-    SqTile tl;
-    tl.P = reinterpret_cast<short *>(slab) + l;
-    tl.R = reinterpret_cast<signed char *>(slab + (size_t) t.n * T * 2) + l;
-    tl.ev = t.edge_var;
-    const int n = t.n;
+    __device__ __forceinline__ uint32_t sign(const int v) const { return (uint32_t) (int) P[(size_t) v * TILE_T]; }
 
-    for (;;) {
-        unsigned long long tv = 0;
-        if (l == 0) tv = atomicAdd(a.work_counter, 1ull);
-        const int64_t tile = (int64_t) (((unsigned long long) (uint32_t) __builtin_amdgcn_readfirstlane((int) (tv >> 32)) << 32) |
-                                        (uint32_t) __builtin_amdgcn_readfirstlane((int) tv));
-        const int64_t frame0 = tile * T;
-        if (frame0 >= a.frames) break;
-        const int nf = (int) (a.frames - frame0 < T ? a.frames - frame0 : T);   // frames of this tile (wave-uniform)
-        const bool exists = l < nf;
-        const size_t frame = (size_t) frame0 + l;
-
-        // ---- start of the tile: P = clamped channel values, [frame][n] -> [n][T] through LDS, 64 variables at a time ---------
+    // start of the tile: P = clamped channel values, [frame][n] -> [n][T] through LDS, 64 variables at a time
+    __device__ __forceinline__ void fill(const int64_t frame0, const int nf) {
+        constexpr int T = TILE_T;
+        const int l = threadIdx.x;
         for (int v0 = 0; v0 < n; v0 += 64) {
             const bool mine = v0 + l < n;
             const int16_t *const c = qa.c_in + (size_t) frame0 * n + v0 + l;
@@ -188,64 +141,18 @@ __global__ void __launch_bounds__(64) bp_streamed_q_kernel(const StreamQTables t
             }
             __syncthreads();
             const int nv = n - v0 < 64 ? n - v0 : 64;
-            for (int vv = 0; vv < nv; ++vv) tl.P[(size_t) (v0 + vv) * T] = X[vv * XS + l];
+            for (int vv = 0; vv < nv; ++vv) P[(size_t) (v0 + vv) * T] = X[vv * XS + l];
             __syncthreads();
         }
-
-        bool latched = false;
-        int iters = a.max_iter;
-        tl.live = exists;
-        // ---- the iterations ------------------------------------------------------------------------------------------------------
-        for (int it = 1; it <= a.max_iter; ++it) {
-            if (a.early_exit && __ballot(tl.live) == 0ull) break;
-            tl.loud = 0;
-            tl.first = it == 1;
-            size_t e0 = (size_t) sq_sload(t.row_ptr, 0);
-            for (int i = 0; i < t.m; ++i) {
-                const size_t e1 = (size_t) sq_sload(t.row_ptr, (size_t) i + 1);
-                tl.check(e0, e1, qa);
-                e0 = e1;
-            }
-            if (tl.live && tl.loud == 0u) {
-                latched = true;
-                iters = it;
-                tl.live = false;
-            }
-        }
-        // ---- frames out of iterations: one syndrome pass over the posteriors' signs ---------------------------------------------
-        bool good = latched;
-        if (a.max_iter > 0 && __ballot(tl.live) != 0ull) {
-            int bad = 0;
-            size_t e0 = (size_t) sq_sload(t.row_ptr, 0);
-            for (int i = 0; i < t.m; ++i) {
-                const size_t e1 = (size_t) sq_sload(t.row_ptr, (size_t) i + 1);
-                int S = 0;
-#pragma unroll 4
-                for (size_t e = e0; e < e1; ++e) S ^= (int) tl.P[(size_t) sq_sload(t.edge_var, e) * T];
-                bad |= S;
-                e0 = e1;
-            }
-            if (tl.live) good = bad >= 0;
-        }
-        // ---- the tile's outputs: packed words (zeros for a failed frame), flags, iterations -------------------------------------
-        if (exists) {
-            if (a.out_ok) a.out_ok[frame] = good ? 1 : 0;
-            if (a.out_iters) a.out_iters[frame] = iters;
-        }
-        if (a.out_bits) {
-            for (int w = 0; w < t.nwords; ++w) {
-                uint32_t word = 0;
-                const int nb = n - 32 * w < 32 ? n - 32 * w : 32;
-#pragma unroll 8
-                for (int b = 0; b < nb; ++b) word |= ((uint32_t) (int) tl.P[(size_t) (32 * w + b) * T] >> 31) << b;
-                if (exists) a.out_bits[frame * t.nwords + w] = good ? word : 0u;
-            }
-        }
-        // ---- and its posteriors, [n][T] -> [frame][n] through LDS -------------------------------------------------------------------
+    }
+    // end of the tile: its posteriors, [n][T] -> [frame][n] through LDS
+    __device__ __forceinline__ void drain(const int64_t frame0, const int nf) {
+        constexpr int T = TILE_T;
+        const int l = threadIdx.x;
         if (qa.post_out) {
             for (int v0 = 0; v0 < n; v0 += 64) {
                 const int nv = n - v0 < 64 ? n - v0 : 64;
-                for (int vv = 0; vv < nv; ++vv) X[vv * XS + l] = tl.P[(size_t) (v0 + vv) * T];
+                for (int vv = 0; vv < nv; ++vv) X[vv * XS + l] = P[(size_t) (v0 + vv) * T];
                 __syncthreads();
                 if (v0 + l < n) {
                     int16_t *const po = qa.post_out + (size_t) frame0 * n + v0 + l;
@@ -255,14 +162,24 @@ __global__ void __launch_bounds__(64) bp_streamed_q_kernel(const StreamQTables t
             }
         }
     }
+};
+
+// grid <= the slabs behind ws.  qa.c_in: frames * n channel values; qa.post_out: frames * n posteriors or null.
+__global__ void __launch_bounds__(64) bp_streamed_q_kernel(const StreamLayTables t, const DecodeArgs a, const QuantArgs qa, unsigned char *__restrict__ ws) {
+    constexpr int T = TILE_T;
+    __shared__ short X[64 * SqTile::XS];
+    const int l = threadIdx.x;
+    unsigned char *const slab = ws + (size_t) blockIdx.x * (size_t) t.slab_bytes;
+    SqTile tl;
+    tl.P = reinterpret_cast<short *>(slab) + l;
+    tl.R = reinterpret_cast<signed char *>(slab + (size_t) t.n * T * 2) + l;
+    tl.ev = t.edge_var;
+    tl.X = X;
+    tl.n = t.n;
+    tl.qa = qa;
+    streamed_tile_loop(t, a, tl);
 }
 
 const void *bp_streamed_q_kernel_ptr() { return (const void *) bp_streamed_q_kernel; }
-
-hipError_t bp_streamed_q_launch(const void *kernel, const StreamQTables &t, const DecodeArgs &a, const QuantArgs &q, unsigned char *ws,
-                                int grid, hipStream_t s) {
-    void *args[] = {(void *) &t, (void *) &a, (void *) &q, (void *) &ws};
-    return hipLaunchKernel(kernel, dim3((unsigned) grid), dim3(64), args, 0, s);
-}
 
 }  // namespace acg

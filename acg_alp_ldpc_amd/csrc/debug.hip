@@ -386,9 +386,9 @@ static int acg_ldpc_debug_streamed_slab_impl(acg_ldpc_decoder *d, int32_t slab, 
         return 3;
     }
     std::lock_guard<std::recursive_mutex> lk(d->mu);
-    const int tiles = d->streaml ? d->sl_tiles : d->sq_tiles;
-    const int64_t bytes = d->streaml ? d->sltab.slab_bytes : d->sqtab.slab_bytes;
-    const unsigned char *ws = d->streaml ? d->sl_ws.as<unsigned char>() : d->sq_ws.as<unsigned char>();
+    const int tiles = d->sl_tiles;
+    const int64_t bytes = d->sltab.slab_bytes;
+    const unsigned char *ws = d->sl_ws.as<unsigned char>();
     *slab_bytes = bytes;
     if (slab < 0 || slab >= tiles) {
         set_error("slab " + std::to_string(slab) + " is outside 0 ... " + std::to_string(tiles - 1) + " (the handle's tiles)");

@@ -95,6 +95,14 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
     a.sigma = (float) std::sqrt(var);
 }
 
+// one launch of a streamed layered engine (q: the integer engine's quantiser, or null): a wavefront per tile of the frames, no more
+// than the handle has slabs
+static hipError_t launch_streamed_layered(acg_ldpc_decoder *d, const DecodeArgs &a, const QuantArgs *q, hipStream_t s) {
+    const int T = d->frames_per_block;
+    const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sl_tiles);
+    return bp_streamed_layered_launch(d->kernel[0], d->sltab, a, q, d->sl_ws.as<unsigned char>(), grid, s);
+}
+
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
 int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid) {
     if (qio && d->osd ? qio->post_out != nullptr : qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || (!d->kernel_qio && !d->streamq))) {
@@ -166,11 +174,10 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
         if (qio) {
             q.c_in = qio->c_in;
             q.post_out = qio->post_out;
-            const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sq_tiles);
-            HIP_OK(bp_streamed_q_launch(d->kernel[0], d->sqtab, a, q, d->sq_ws.as<unsigned char>(), grid, s));
+            HIP_OK(launch_streamed_layered(d, a, &q, s));
         } else {
             // the symbol entrance: the handle's quantiser into its staging buffer, then the integer path, a residency of tiles at a time
-            const int64_t chunk = std::min<int64_t>(a.frames, (int64_t) d->sq_tiles * T);
+            const int64_t chunk = std::min<int64_t>(a.frames, (int64_t) d->sl_tiles * T);
             const size_t n = (size_t) d->c.n, nwords = (n + 31) / 32;
             if (int rc = d->sq_stage.reserve((size_t) chunk * n * sizeof(int16_t))) return rc;
             q.c_in = d->sq_stage.as<int16_t>();
@@ -184,8 +191,7 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
                 if (a.out_iters) ac.out_iters = a.out_iters + f0;
                 if (f0 > 0) HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), s));   // (the chunks share the launch's counter)
                 HIP_OK(quantize_debug_launch(ac, q, ac.frames * (int64_t) n, d->sq_stage.as<int16_t>(), s));
-                const int grid = (int) std::min<int64_t>((ac.frames + T - 1) / T, d->sq_tiles);
-                HIP_OK(bp_streamed_q_launch(d->kernel[0], d->sqtab, ac, q, d->sq_ws.as<unsigned char>(), grid, s));
+                HIP_OK(launch_streamed_layered(d, ac, &q, s));
             }
         }
     } else if (d->streaml) {
@@ -193,9 +199,7 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
             set_error("internal: the streamed layered engine has no in-kernel generator");
             return 11;
         }
-        const int T = d->frames_per_block;
-        const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sl_tiles);
-        HIP_OK(bp_streamed_layered_launch(d->kernel[0], d->sltab, a, d->sl_ws.as<unsigned char>(), grid, s));
+        HIP_OK(launch_streamed_layered(d, a, nullptr, s));
     } else if (d->osd) {
         if (a.mc) {
             set_error("internal: the OSD engine has no in-kernel generator");

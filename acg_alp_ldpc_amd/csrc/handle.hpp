@@ -178,18 +178,17 @@ struct acg_ldpc_decoder {
     acg::LayerBlockTables lbtab{};
     acg::DeviceBuf lb_step, lb_pos;
     // streamed fixed-point layered min-sum (bp_streamed_q.hip; handles of acg_ldpc_decoder_create_quantized_streamed only): a
-    // quantized handle (layered_wg == q, quant, qargs, the sets in lblay) whose frames live in the slabs of sq_ws, one per resident
+    // quantized handle (layered_wg == q, quant, qargs, the sets in lblay) whose frames live in the slabs of sl_ws, one per resident
     // tile of 64 frames.  sq_stage: the symbol entrance's int16 channel values of the frames in flight.
     bool streamq = false;
-    acg::StreamQTables sqtab{};
-    int sq_tiles = 0;
-    acg::DeviceBuf sq_ws, sq_stage;
+    acg::DeviceBuf sq_stage;
     // streamed float layered BP (bp_streamed_layered.hip; handles of acg_ldpc_decoder_create_layered_streamed only): sum-product
     // or min-sum with fp32 posteriors and messages, a frame in the slabs of sl_ws, one per resident tile of 64 frames; the sets in
     // lblay.  NOT a quantized handle (layered_wg stays none): the integer entrances refuse it.  Decode only: Monte-Carlo runs take
     // the unfused route.
     bool streaml = false;
-    acg::StreamLTables sltab{};
+    // what either of the two has (a handle is at most one of them): the CSR and slab size, the resident tiles, their slabs
+    acg::StreamLayTables sltab{};
     int sl_tiles = 0;
     acg::DeviceBuf sl_ws;
     // ordered-statistics decoding (osd.hip; algo = ACG_LDPC_OSD): the packed column table, and what the kernel reads.  One kernel

@@ -154,22 +154,14 @@ struct QuantIo {
     int16_t *post_out;
 };
 
-// Streamed fixed-point layered min-sum (bp_streamed_q.hip): the checks in processing order as a plain CSR, read through
-// scalar loads, and the slab of a tile
-struct StreamQTables {
+// The streamed layered engines (bp_streamed_q.hip: fixed-point min-sum; bp_streamed_layered.hip: float sum-product and min-sum):
+// the checks in processing order as a plain CSR, read through scalar loads, and the slab of a tile
+struct StreamLayTables {
     const int32_t *row_ptr;    // [m + 1] first edge of the i-th check processed (the sets of bp_layered_block_build, set by set)
     const int32_t *edge_var;   // [E] variables of those edges, ascending inside a check
     int32_t m, n, E, nwords;   // m: checks with at least one variable
-    int64_t slab_bytes;        // bytes of a tile's slab: P[n][T] int16 | R[E][T] int8, rounded up to 256
-};
-
-// Streamed float layered BP (bp_streamed_layered.hip): the same CSR, and the slab of a tile
-struct StreamLTables {
-    const int32_t *row_ptr;    // [m + 1] first edge of the i-th check processed (the sets of bp_layered_block_build, set by set)
-    const int32_t *edge_var;   // [E] variables of those edges, ascending inside a check
-    int32_t m, n, E, nwords;   // m: checks with at least one variable
-    int32_t max_deg;           // largest check degree: rows of the wide-check scratch
-    int64_t slab_bytes;        // bytes of a tile's slab: P[n][T] | R[E][T] | scratch, fp32, rounded up to 256
+    int32_t max_deg;           // largest check degree: rows of the float engine's wide-check scratch
+    int64_t slab_bytes;        // bytes of a tile's slab, rounded up to 256: P[n][T] int16 | R[E][T] int8, or P[n][T] | R[E][T] | scratch in fp32
 };
 
 // Ordered-statistics decoding (osd.hip): what the kernel reads next to DecodeArgs

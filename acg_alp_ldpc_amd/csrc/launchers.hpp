@@ -95,17 +95,16 @@ hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_
 
 // ---- bp_streamed_q.hip: streamed fixed-point layered min-sum, a wavefront per tile of 64 frames ----
 const void *bp_streamed_q_kernel_ptr();
-// q: the quantiser with c_in set (and post_out, or null); ws: grid slabs of t.slab_bytes
-hipError_t bp_streamed_q_launch(const void *kernel, const StreamQTables &t, const DecodeArgs &a, const QuantArgs &q, unsigned char *ws,
-                                int grid, hipStream_t s);
 
 // ---- bp_streamed_layered.hip: streamed float layered BP, a wavefront per tile of 64 frames ----
 const void *bp_streamed_layered_kernel_ptr(int algo);   // algo: 0 sum-product, 1 min-sum
 // fp32 words per frame behind P and R: the scratch of a wide sum-product check (0: max_deg <= 8, or min-sum)
 size_t bp_streamed_layered_scratch_words(int algo, int max_deg);
 bool bp_streamed_layered_stores_mag();   // pass 2 of a wide sum-product check reads mag back (or forms it again)
-// ws: grid slabs of t.slab_bytes
-hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLTables &t, const DecodeArgs &a, unsigned char *ws, int grid, hipStream_t s);
+// either engine.  q: the quantiser of bp_streamed_q_kernel with c_in set (and post_out, or null), null for the float kernels; ws:
+// grid slabs of t.slab_bytes
+hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLayTables &t, const DecodeArgs &a, const QuantArgs *q, unsigned char *ws,
+                                      int grid, hipStream_t s);
 
 // ---- osd.hip: ordered-statistics decoding, one workgroup of L = 64, 128 or 256 threads per frame ----
 const void *osd_kernel_ptr(int L);
