@@ -93,6 +93,8 @@ SYMBOLS = {
     "acg_ldpc_decoder_create_quantized_streamed": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(Quant), C.POINTER(_vp)]),
     "acg_ldpc_decoder_create_layered_streamed": (C.c_int, [_vp, C.POINTER(Params), C.POINTER(_vp)]),
     "acg_ldpc_decode_batch_q": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_decode_batch_llr_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "acg_ldpc_decode_batch_llr": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "acg_ldpc_osd_decode_batch_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "acg_ldpc_osd_decode_batch": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "acg_ldpc_debug_osd_soft": (C.c_int, [_vp, _i32, _i64, _vp]),

@@ -716,6 +716,7 @@ static int decoder_setup_streaml(acg_ldpc_decoder *d) {
     if (int rc = decoder_setup_streamed_layered(d, bp_streamed_layered_kernel_ptr(algo), per_frame, "streamed layered BP: ", "ACG_STREAML_TILES", "ACG_STREAML_PER_CU"))
         return rc;
     d->streaml = true;
+    for (int k = 0; k < 2; k++) d->kernel_lio[k] = bp_streamed_layered_kernel_ptr(k, true);
     return 0;
 }
 
@@ -1283,7 +1284,7 @@ static std::string describe(const acg_ldpc_decoder *d) {
         const size_t scratch = bp_streamed_layered_scratch_words(d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1, d->sltab.max_deg);
         snprintf(b, sizeof b, "%s engine=streamed kernel=bp_streamed_layered_kernel<%s> schedule=layered messages=fp32 posteriors=fp32 T=%d tiles=%d "
                                "state_bytes_per_frame=%zu scratch_bytes_per_frame=%zu wide_mag=%s slab_bytes=%lld workspace_bytes=%zu "
-                               "workspace=hipMalloc sets=%d checks=%d max_check_degree=%d",
+                               "workspace=hipMalloc sets=%d checks=%d max_check_degree=%d io=llr,post",
                  algo, algo, d->frames_per_block, d->sl_tiles, 4 * ((size_t) d->c.n + (size_t) d->sltab.E), 4 * scratch,
                  scratch == 0 ? "none" : (bp_streamed_layered_stores_mag() ? "stored" : "recomputed"), (long long) d->sltab.slab_bytes,
                  (size_t) d->sl_tiles * (size_t) d->sltab.slab_bytes, d->lblay.n_sets, d->sltab.m, d->sltab.max_deg);

@@ -28,7 +28,21 @@
 // The tile loop — the claim of a tile, the iterations and the latch, the syndrome pass, the outputs — is streamed_tile_loop of
 // bp_streamed_tile.inc, shared with bp_streamed_q.hip; "Control" and "No stale state" are written there.  Of this engine's own:
 // a scratch cell is written by pass 1 of the check whose pass 2 reads it.
+//
+// The IO instances (acg_ldpc_decode_batch_llr*; StreamLayIo behind ws) differ in the two ends of a tile and in nothing between:
+//   fill   a frame is n fp32 LLRs, positive = bit 0.  Per value: NaN -> +0; clamp to +-2^20 (exact in fp32, and +-inf stays out of
+//          p - r); min-sum takes that, sum-product multiplies it ONCE by (float) Dom<float>::scale — the multiply the symbol
+//          entrance applies to the LLR it forms.  So an LLR of at most 2^20 that the symbol entrance would have formed itself gives
+//          the same slab, bit for bit, and with it the same word, flag and iteration.
+//   drain  where post_out is set, the slab's P of the frames that exist, [n][T] -> [frame][n] through X: min-sum as it is,
+//          sum-product times (float) ln 2 in ONE multiply, back to natural-log units.  The sign bit survives, -0 included.  A latched
+//          lane writes nothing of P (the tile loop), so a frame that latched hands out the posteriors of the round boundary at which
+//          its word was formed, whatever early_exit says; one that failed, those after max_iter iterations; max_iter = 0, the clamped
+//          LLR (sum-product: scaled and scaled back, which need not be the input's bits).
+// The symbol entrance's instances read no StreamLayIo and compile to what they compiled to without it.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "launchers.hpp"
 
@@ -47,8 +61,11 @@ constexpr bool SL_STORE_MAG = ACG_SL_STORE_MAG != 0;
 __device__ __forceinline__ uint32_t sl_bits(const float x) { return __float_as_uint(x); }
 __device__ __forceinline__ float sl_abs(const float x) { return __uint_as_float(__float_as_uint(x) & 0x7FFFFFFFu); }
 
-// ALGO: 1 = normalised min-sum, 0 = sum-product
-template <int ALGO>
+constexpr uint32_t SL_LLR_CLAMP = 0x49800000u;   // 2^20 as fp32 bits: the largest magnitude of an LLR of the IO instances
+
+// ALGO: 1 = normalised min-sum, 0 = sum-product.  IO: the LLR entrance (io.llr_in in, io.post_out out) instead of the symbol
+// entrance (a->y in, hard outputs only)
+template <int ALGO, bool IO = false>
 struct SlTile {
     float *P;            // this lane's posterior of variable v: P[(size_t) v * TILE_T]
     float *R;            // this lane's message of edge e: R[(size_t) e * TILE_T]
@@ -57,6 +74,7 @@ struct SlTile {
     const int32_t *ev;
     float *X;            // the workgroup's transposing buffer: XV variables x T frames, rows of XS words
     const DecodeArgs *a; // the channel values and terms of fill()
+    StreamLayIo io;      // IO: the LLRs of fill() and the posteriors of drain(); neither set nor read otherwise
     int n;
     float scale;
     static constexpr int XV = 32;           // variables of a trip through the transposing buffer
@@ -209,7 +227,11 @@ struct SlTile {
                 float x = 0.0f;
                 if (fr < nf && mine) {
                     float llr;
-                    if (a->y_is_f64) llr = (float) (2 * reinterpret_cast<const double *>(a->y)[y0 + (size_t) fr * n] / a->var);
+                    if constexpr (IO) {
+                        // NaN -> +0, then clamp to +-2^20, both on the bits: no rounding and no floating-point mode takes part
+                        const uint32_t u = sl_bits(io.llr_in[y0 + (size_t) fr * n]), m = u & 0x7FFFFFFFu;
+                        llr = __uint_as_float(m > 0x7F800000u ? 0u : (m > SL_LLR_CLAMP ? (u & 0x80000000u) | SL_LLR_CLAMP : u));
+                    } else if (a->y_is_f64) llr = (float) (2 * reinterpret_cast<const double *>(a->y)[y0 + (size_t) fr * n] / a->var);
                     else llr = (float) ((double) reinterpret_cast<const float *>(a->y)[y0 + (size_t) fr * n] * a->inv_var2);
                     x = (ALGO == 0) ? llr * (float) Dom<float>::scale : llr;
                 }
@@ -221,17 +243,46 @@ struct SlTile {
             __syncthreads();
         }
     }
-    __device__ __forceinline__ void drain(const int64_t, const int) {}   // (hard outputs only)
+    // end of the tile.  IO: its posteriors, [n][T] -> [frame][n] through LDS, the mirror image of fill(): the same cells of X
+    // written by rows and read by columns, so neither side meets a bank conflict; frames that exist and variables below n only
+    __device__ __forceinline__ void drain(const int64_t frame0, const int nf) {
+        if constexpr (IO) {
+            constexpr int T = TILE_T;
+            const int l = threadIdx.x;
+            if (!io.post_out) return;
+            for (int v0 = 0; v0 < n; v0 += XV) {
+                const int nv = n - v0 < XV ? n - v0 : XV;
+                for (int vv = 0; vv < nv; ++vv) X[vv * XS + l] = P[(size_t) (v0 + vv) * T];
+                __syncthreads();
+                const int vl = l & (XV - 1), h = l / XV;
+                const bool mine = v0 + vl < n;
+                const size_t y0 = (size_t) frame0 * n + v0 + vl;
+#pragma unroll 8
+                for (int k = 0; k < T / 2; ++k) {
+                    const int fr = 2 * k + h;
+                    if (fr < nf && mine) {
+                        const float p = X[vl * XS + fr];
+                        io.post_out[y0 + (size_t) fr * n] = (ALGO == 0) ? p * (float) 0.6931471805599453 : p;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        // (otherwise: hard outputs only)
+    }
 };
 
-// grid <= the slabs behind ws
-template <int ALGO>
-__global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLayTables t, const DecodeArgs a, unsigned char *__restrict__ ws) {
+// grid <= the slabs behind ws.  Io: nothing (the symbol entrance's instances), or one StreamLayIo (the IO instances)
+template <int ALGO, typename... Io>
+__global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLayTables t, const DecodeArgs a, unsigned char *__restrict__ ws, const Io... io) {
     constexpr int T = TILE_T;
-    __shared__ float X[SlTile<ALGO>::XV * SlTile<ALGO>::XS];
+    constexpr bool IO = sizeof...(Io) != 0;
+    static_assert(!IO || (sizeof...(Io) == 1 && (std::is_same<Io, StreamLayIo>::value && ...)), "the IO instances: one StreamLayIo behind ws");
+    using Tile = SlTile<ALGO, IO>;
+    __shared__ float X[Tile::XV * Tile::XS];
     const int l = threadIdx.x;
     float *const slab = reinterpret_cast<float *>(ws + (size_t) blockIdx.x * (size_t) t.slab_bytes);
-    SlTile<ALGO> tl;
+    Tile tl;
     tl.P = slab + l;
     tl.R = tl.P + (size_t) t.n * T;
     tl.M = tl.R + (size_t) t.E * T;
@@ -241,11 +292,13 @@ __global__ void __launch_bounds__(64) bp_streamed_layered_kernel(const StreamLay
     tl.a = &a;
     tl.n = t.n;
     tl.scale = a.ms_scale;
+    if constexpr (IO) tl.io = (io, ...);
     streamed_tile_loop(t, a, tl);
 }
 
 // algo: 0 sum-product, 1 min-sum
-const void *bp_streamed_layered_kernel_ptr(int algo) {
+const void *bp_streamed_layered_kernel_ptr(int algo, bool io) {
+    if (io) return algo == 0 ? (const void *) bp_streamed_layered_kernel<0, StreamLayIo> : (const void *) bp_streamed_layered_kernel<1, StreamLayIo>;
     return algo == 0 ? (const void *) bp_streamed_layered_kernel<0> : (const void *) bp_streamed_layered_kernel<1>;
 }
 
@@ -257,13 +310,14 @@ size_t bp_streamed_layered_scratch_words(int algo, int max_deg) {
 bool bp_streamed_layered_stores_mag() { return SL_STORE_MAG; }
 
 hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLayTables &t, const DecodeArgs &a, const QuantArgs *q, unsigned char *ws,
-                                      int grid, hipStream_t s) {
-    void *args[4];
+                                      int grid, hipStream_t s, const StreamLayIo *io) {
+    void *args[5];
     int k = 0;
     args[k++] = (void *) &t;
     args[k++] = (void *) &a;
     if (q) args[k++] = (void *) q;
     args[k++] = (void *) &ws;
+    if (io) args[k++] = (void *) io;
     return hipLaunchKernel(kernel, dim3((unsigned) grid), dim3(64), args, 0, s);
 }
 

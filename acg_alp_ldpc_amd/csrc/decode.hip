@@ -95,16 +95,21 @@ void acg::fill_channel(DecodeArgs &a, double snr) {
     a.sigma = (float) std::sqrt(var);
 }
 
-// one launch of a streamed layered engine (q: the integer engine's quantiser, or null): a wavefront per tile of the frames, no more
-// than the handle has slabs
-static hipError_t launch_streamed_layered(acg_ldpc_decoder *d, const DecodeArgs &a, const QuantArgs *q, hipStream_t s) {
+// one launch of a streamed layered engine (q: the integer engine's quantiser, or null; lio: the float engine's LLR entrance and
+// its IO instance, or null): a wavefront per tile of the frames, no more than the handle has slabs
+static hipError_t launch_streamed_layered(acg_ldpc_decoder *d, const DecodeArgs &a, const QuantArgs *q, hipStream_t s, const StreamLayIo *lio = nullptr) {
     const int T = d->frames_per_block;
     const int grid = (int) std::min<int64_t>((a.frames + T - 1) / T, d->sl_tiles);
-    return bp_streamed_layered_launch(d->kernel[0], d->sltab, a, q, d->sl_ws.as<unsigned char>(), grid, s);
+    const void *kernel = lio ? d->kernel_lio[d->p.algo == ACG_LDPC_BP_SUMPRODUCT ? 0 : 1] : d->kernel[0];
+    return bp_streamed_layered_launch(kernel, d->sltab, a, q, d->sl_ws.as<unsigned char>(), grid, s, lio);
 }
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
-int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid) {
+int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid, const StreamLayIo *lio) {
+    if (lio && (qio || qgrid || !d->streaml || !lio->llr_in)) {
+        set_error("internal: LLRs handed to a launch that cannot take them");
+        return 11;
+    }
     if (qio && d->osd ? qio->post_out != nullptr : qio && (d->layered_wg != acg_ldpc_decoder::LayeredWg::q || (!d->kernel_qio && !d->streamq))) {
         set_error("internal: channel values handed to a decoder that is not quantized");
         return 11;
@@ -199,7 +204,7 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
             set_error("internal: the streamed layered engine has no in-kernel generator");
             return 11;
         }
-        HIP_OK(launch_streamed_layered(d, a, nullptr, s));
+        HIP_OK(launch_streamed_layered(d, a, nullptr, s, lio));
     } else if (d->osd) {
         if (a.mc) {
             set_error("internal: the OSD engine has no in-kernel generator");
@@ -407,16 +412,18 @@ static void unpack_bits(const uint32_t *words, int nwords, int n, int64_t frames
 // stream -> host threads expand the words into one byte per bit.  Chunk c + 1 is packed and chunk c - 1 unpacked while
 // the GPU works on chunk c.  elem = 8 (double symbols: exact LLRs, channel.h:14-16) or 4 (float symbols); elem = 2: int16
 // channel values of a quantized handle (acg_ldpc_decode_batch_q; snr unused), whose int16 posteriors come back behind the
-// flags of the chunk where post is given, or int16 soft values of an OSD handle (acg_ldpc_osd_decode_batch).
+// flags of the chunk where post is given, or int16 soft values of an OSD handle (acg_ldpc_osd_decode_batch).  llr (elem = 4):
+// fp32 LLRs of a streamed float layered handle (acg_ldpc_decode_batch_llr; snr unused), whose fp32 posteriors come back the same way.
 static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64_t frames, double snr, uint8_t *bits, uint8_t *ok,
-                             int32_t *iters, int16_t *post = nullptr) {
+                             int32_t *iters, void *post = nullptr, bool llr = false) {
     const int n = d->c.n, nwords = (n + 31) / 32;
     const size_t y_bytes = (size_t) n * elem;
+    const size_t post_bytes = (size_t) n * (llr ? 4 : 2);   // of a frame's posteriors
     const size_t row = (size_t) nwords * 4 + 5;   // words, sweep count and flag of a frame
     auto post_off = [&](int64_t fc) { return ((size_t) fc * row + 15) & ~(size_t) 15; };
     // small batches (single frames: the reference's decode()) take one chunk; large ones <= 64k frames / 256 MiB per chunk
     const int64_t chunk = host_chunk_frames(frames, y_bytes);
-    if (int rc = ensure_pipe(d, chunk, y_bytes, row + (post ? (size_t) n * 2 : 0))) return rc;
+    if (int rc = ensure_pipe(d, chunk, y_bytes, row + (post ? post_bytes : 0))) return rc;
     HostPipe &P = *d->pipe;
     const int64_t nchunks = (frames + chunk - 1) / chunk;
     const bool threads = frames >= 4096;  // tiny batches: the hand-off to the pool costs more than the copy
@@ -443,13 +450,14 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         hipStream_t s = P.stream[b];
         unsigned char *dev_out = P.dev_out[b].as<unsigned char>();
         HIP_OK(hipMemcpyAsync(P.dev_y[b].p, P.pin_y[b].p, (size_t) fc * y_bytes, hipMemcpyHostToDevice, s));
-        DecodeArgs a = decode_args(elem == 2 ? nullptr : P.dev_y[b].p, (elem == 8) ? 1 : 0, fc, snr);
+        DecodeArgs a = decode_args(elem == 2 || llr ? nullptr : P.dev_y[b].p, (elem == 8) ? 1 : 0, fc, snr);
         const QuantIo io{P.dev_y[b].as<int16_t>(), post ? reinterpret_cast<int16_t *>(dev_out + post_off(fc)) : nullptr};
+        const StreamLayIo lio{P.dev_y[b].as<float>(), post ? reinterpret_cast<float *>(dev_out + post_off(fc)) : nullptr};
         a.out_bits = reinterpret_cast<uint32_t *>(dev_out);
         a.out_iters = reinterpret_cast<int32_t *>(dev_out + (size_t) fc * nwords * 4);
         a.out_ok = dev_out + (size_t) fc * (nwords * 4 + 4);
-        if (int rc = launch_decode(d, a, s, elem == 2 ? &io : nullptr)) return rc;
-        HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, post ? post_off(fc) + (size_t) fc * n * 2 : (size_t) fc * row, hipMemcpyDeviceToHost, s));
+        if (int rc = launch_decode(d, a, s, elem == 2 ? &io : nullptr, nullptr, llr ? &lio : nullptr)) return rc;
+        HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, post ? post_off(fc) + (size_t) fc * post_bytes : (size_t) fc * row, hipMemcpyDeviceToHost, s));
         HIP_OK(hipEventRecord(P.done[b], s));
         return 0;
     };
@@ -461,16 +469,17 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         const uint32_t *pbits = reinterpret_cast<const uint32_t *>(out);
         std::memcpy(ok + f0, out + (size_t) fc * (nwords * 4 + 4), (size_t) fc);
         if (iters) std::memcpy(iters + f0, out + (size_t) fc * nwords * 4, (size_t) fc * 4);
-        const int16_t *ppost = reinterpret_cast<const int16_t *>(out + post_off(fc));
+        const unsigned char *ppost = out + post_off(fc);
+        unsigned char *const upost = static_cast<unsigned char *>(post);
         if (!threads) {
             unpack_bits(pbits, nwords, n, fc, bits + (size_t) f0 * n);
-            if (post) std::memcpy(post + (size_t) f0 * n, ppost, (size_t) fc * n * 2);
+            if (post) std::memcpy(upost + (size_t) f0 * post_bytes, ppost, (size_t) fc * post_bytes);
             return 0;
         }
         pool->run_all([&](int part, int parts) {
             const int64_t lo = fc * part / parts, hi = fc * (part + 1) / parts;
             unpack_bits(pbits + (size_t) lo * nwords, nwords, n, hi - lo, bits + (size_t) (f0 + lo) * n);
-            if (post) std::memcpy(post + (size_t) (f0 + lo) * n, ppost + (size_t) lo * n, (size_t) (hi - lo) * n * 2);
+            if (post) std::memcpy(upost + (size_t) (f0 + lo) * post_bytes, ppost + (size_t) lo * post_bytes, (size_t) (hi - lo) * post_bytes);
         });
         return 0;
     };
@@ -590,6 +599,65 @@ int acg_ldpc_decode_batch_q_dev(acg_ldpc_decoder *d, const int16_t *c_dev, int64
 int acg_ldpc_decode_batch_q(acg_ldpc_decoder *d, const int16_t *c, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
                             int16_t *post) {
     return guarded([&] { return decode_batch_q_impl(d, c, frames, bits, ok, iters, post); });
+}
+
+// ---- the LLR entrance of the streamed float layered engine: fp32 LLRs in, fp32 posterior LLRs out ----
+
+// what the two entry points refuse that is not a null or a negative argument
+static int streaml_handle(const acg_ldpc_decoder *d) {
+    if (!d->streaml) {
+        set_error("LLRs need a decoder of acg_ldpc_decoder_create_layered_streamed");
+        return 3;
+    }
+    return 0;
+}
+
+static int decode_batch_llr_dev_impl(acg_ldpc_decoder *d, const float *llr_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                     int32_t *iters_dev, float *post_dev, void *stream) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    if (frames < 0 || (frames > 0 && !llr_dev)) {
+        set_error("bad frames / llr");
+        return 1;
+    }
+    if (int rc = streaml_handle(d)) return rc;
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    DecodeArgs a = decode_args(nullptr, 0, frames, 0.0);   // (no symbols, no channel: the IO instances read neither)
+    a.out_bits = bits_dev;
+    a.out_ok = ok_dev;
+    a.out_iters = iters_dev;
+    const StreamLayIo io{llr_dev, post_dev};
+    return launch_decode(d, a, stream ? (hipStream_t) stream : d->stream, nullptr, nullptr, &io);
+}
+
+static int decode_batch_llr_impl(acg_ldpc_decoder *d, const float *llr, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters, float *post) {
+    if (!d) {
+        set_error("null decoder");
+        return 1;
+    }
+    if (frames < 0 || (frames > 0 && (!llr || !bits || !ok))) {
+        set_error("null buffer");
+        return 1;
+    }
+    if (int rc = streaml_handle(d)) return rc;
+    if (frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    return decode_batch_host(d, llr, 4, frames, 0.0, bits, ok, iters, post, true);
+}
+
+int acg_ldpc_decode_batch_llr_dev(acg_ldpc_decoder *d, const float *llr_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                  int32_t *iters_dev, float *post_dev, void *stream) {
+    return guarded([&] { return decode_batch_llr_dev_impl(d, llr_dev, frames, bits_dev, ok_dev, iters_dev, post_dev, stream); });
+}
+
+int acg_ldpc_decode_batch_llr(acg_ldpc_decoder *d, const float *llr, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
+                              float *post) {
+    return guarded([&] { return decode_batch_llr_impl(d, llr, frames, bits, ok, iters, post); });
 }
 
 // ---- the integer entrance of the OSD engine: soft values in ----

@@ -53,9 +53,9 @@ struct HostPipe {
     size_t y_bytes = 0;      // bytes per frame of the symbol buffers
     size_t out_bytes = 0;    // bytes per frame of the output buffers (+ 16 per buffer for the alignment of the posteriors)
     PinnedBuf pin_y[NBUF], pin_out[NBUF];  // out: [frames][nwords] words | [frames] sweep counts | [frames] flags of the chunk in
-    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight (| [frames][n] int16 posteriors from a 16-byte boundary, where
-                                           // acg_ldpc_decode_batch_q is asked for them): one region, so the results come back in
-                                           // ONE device-to-host copy
+    DeviceBuf dev_y[NBUF], dev_out[NBUF];  // flight (| [frames][n] posteriors from a 16-byte boundary, int16 where
+                                           // acg_ldpc_decode_batch_q, fp32 where acg_ldpc_decode_batch_llr is asked for them):
+                                           // one region, so the results come back in ONE device-to-host copy
     hipStream_t stream[NBUF] = {};
     hipEvent_t done[NBUF] = {};
     void release() {
@@ -187,6 +187,10 @@ struct acg_ldpc_decoder {
     // lblay.  NOT a quantized handle (layered_wg stays none): the integer entrances refuse it.  Decode only: Monte-Carlo runs take
     // the unfused route.
     bool streaml = false;
+    // its IO instances (the LLR entrance, acg_ldpc_decode_batch_llr*): sum-product's and min-sum's, of which launch_decode takes
+    // the one of the handle's algorithm; kernel[0] stays the symbol entrance's.  The same slabs and tiles: a grid of the IO
+    // instance is bounded by sl_tiles too
+    const void *kernel_lio[2] = {nullptr, nullptr};
     // what either of the two has (a handle is at most one of them): the CSR and slab size, the resident tiles, their slabs
     acg::StreamLayTables sltab{};
     int sl_tiles = 0;
@@ -305,7 +309,9 @@ void fill_channel(DecodeArgs &a, double snr);
 // qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for; of an
 // OSD handle — soft values instead of a.y (post_out null)
 // qgrid != null: the grid form of a quantized handle — a.frames virtual frames, a quantiser per point instead of the handle's
-int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr, const QuantGridArgs *qgrid = nullptr);
+// lio != null: the LLR entrance of a streamed float layered handle — LLRs instead of a.y, posteriors where asked for
+int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr, const QuantGridArgs *qgrid = nullptr,
+                  const StreamLayIo *lio = nullptr);
 int ensure_staging(acg_ldpc_decoder *d, int64_t frames);
 void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a);
 DecodeArgs decode_args(const void *y, int y_is_f64, int64_t frames, double snr);

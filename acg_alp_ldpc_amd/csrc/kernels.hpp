@@ -164,6 +164,13 @@ struct StreamLayTables {
     int64_t slab_bytes;        // bytes of a tile's slab, rounded up to 256: P[n][T] int16 | R[E][T] int8, or P[n][T] | R[E][T] | scratch in fp32
 };
 
+// The LLR entrance of the streamed float layered engine (acg_ldpc_decode_batch_llr*): what the IO instances of
+// bp_streamed_layered_kernel read, an argument block of their own behind ws, so no argument of the other instances moves
+struct StreamLayIo {
+    const float *llr_in;   // frames * n LLRs, positive = bit 0; the kernel takes NaN as +0 and clamps to +-2^20
+    float *post_out;       // frames * n posterior LLRs in natural-log units, written with the frame's word; null = off
+};
+
 // Ordered-statistics decoding (osd.hip): what the kernel reads next to DecodeArgs
 struct OsdArgs {
     const uint32_t *cols;   // [n][stride] H column-major, bit r % 32 of word r / 32 of column v = H[r][v]

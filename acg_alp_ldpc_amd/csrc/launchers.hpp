@@ -97,14 +97,15 @@ hipError_t quantize_debug_launch(const DecodeArgs &a, const QuantArgs &q, int64_
 const void *bp_streamed_q_kernel_ptr();
 
 // ---- bp_streamed_layered.hip: streamed float layered BP, a wavefront per tile of 64 frames ----
-const void *bp_streamed_layered_kernel_ptr(int algo);   // algo: 0 sum-product, 1 min-sum
+// algo: 0 sum-product, 1 min-sum; io: the instance of the LLR entrance (StreamLayIo: LLRs in, posteriors out) instead of the symbol entrance's
+const void *bp_streamed_layered_kernel_ptr(int algo, bool io = false);
 // fp32 words per frame behind P and R: the scratch of a wide sum-product check (0: max_deg <= 8, or min-sum)
 size_t bp_streamed_layered_scratch_words(int algo, int max_deg);
 bool bp_streamed_layered_stores_mag();   // pass 2 of a wide sum-product check reads mag back (or forms it again)
 // either engine.  q: the quantiser of bp_streamed_q_kernel with c_in set (and post_out, or null), null for the float kernels; ws:
-// grid slabs of t.slab_bytes
+// grid slabs of t.slab_bytes; io: the last argument of the float kernels' IO instances, null for every other kernel
 hipError_t bp_streamed_layered_launch(const void *kernel, const StreamLayTables &t, const DecodeArgs &a, const QuantArgs *q, unsigned char *ws,
-                                      int grid, hipStream_t s);
+                                      int grid, hipStream_t s, const StreamLayIo *io = nullptr);
 
 // ---- osd.hip: ordered-statistics decoding, one workgroup of L = 64, 128 or 256 threads per frame ----
 const void *osd_kernel_ptr(int L);

@@ -424,13 +424,52 @@ class StreamedQuantizedMinSumDecoder(QuantizedMinSumDecoder):
 
 
 class _StreamedLayered:
-    """the create call and handle key of the streamed float layered engine (acg_ldpc_decoder_create_layered_streamed)"""
+    """the create call and handle key of the streamed float layered engine (acg_ldpc_decoder_create_layered_streamed), and its
+    LLR entrance: decode_llr_batch / decode_llr_batch_dev, fp32 LLRs in (punctured and shortened positions among them), fp32
+    posterior LLRs out.  tests/streamed_layered_io_ref.py restates it."""
 
     def _key(self, H):
         return super()._key(H) + ("layered-streamed",)
 
     def _create(self, code, p, h):
         return lib().acg_ldpc_decoder_create_layered_streamed(code._h, C.byref(p), C.byref(h))
+
+    # -- the LLR entrance: LLRs in, posterior LLRs out (acg_ldpc_decode_batch_llr*) -----------------
+    def decode_llr_batch(self, H, L, posteriors=True, out=None):
+        """L: frames x n LLRs, positive = bit 0 (any real array; converted to float32).  NaN counts as 0 and every value is
+        clamped to +-2^20.  A punctured position is 0, a shortened one +2^20 (known 0) or -2^20 (known 1).
+        out = (bits, ok, iters[, post]) reuses caller arrays.  -> (bits[F,n], ok[F], iters[F][, post[F,n] float32]): post is the
+        posterior LLR in natural-log units, and (post < 0, -0 included: np.signbit) is the word of every frame with ok = 1."""
+        a = np.asarray(L)
+        if a.dtype.kind not in "fiub":
+            raise TypeError("decode_llr_batch takes real LLRs, not %s" % a.dtype)
+        if a.ndim != 2:
+            raise ValueError("L must be frames x n")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        with self._lease(H) as (h, code):
+            if a.shape[1] != code.n:
+                raise ValueError("L must be frames x n")
+            F = a.shape[0]
+            if out is not None:
+                bits, ok, iters = out[:3]
+                post = out[3] if posteriors else None
+                assert bits.shape == (F, code.n) and bits.dtype == np.uint8 and bits.flags.c_contiguous
+                assert ok.shape == (F,) and ok.dtype == np.uint8 and iters.shape == (F,) and iters.dtype == np.int32
+                assert post is None or (post.shape == (F, code.n) and post.dtype == np.float32 and post.flags.c_contiguous)
+            else:
+                bits = np.empty((F, code.n), dtype=np.uint8)
+                ok = np.empty(F, dtype=np.uint8)
+                iters = np.empty(F, dtype=np.int32)
+                post = np.empty((F, code.n), dtype=np.float32) if posteriors else None
+            check(lib().acg_ldpc_decode_batch_llr(h, a.ctypes.data, F, bits.ctypes.data, ok.ctypes.data, iters.ctypes.data,
+                                                  post.ctypes.data if post is not None else None))
+        return (bits, ok, iters, post) if posteriors else (bits, ok, iters)
+
+    def decode_llr_batch_dev(self, H, llr_ptr, frames, bits_ptr, ok_ptr, iters_ptr=None, post_ptr=None, stream=None):
+        """device pointers (ints): frames*n float32 LLRs in; packed words, flags, iterations and, where post_ptr is given,
+        frames*n float32 posteriors out; asynchronous on `stream` (None = the decoder's own stream)"""
+        with self._lease(H) as (h, _):
+            check(lib().acg_ldpc_decode_batch_llr_dev(h, llr_ptr, int(frames), bits_ptr, ok_ptr, iters_ptr, post_ptr, stream))
 
 
 class StreamedLayeredBPDecoder(_StreamedLayered, BeliefPropagationDecoder):

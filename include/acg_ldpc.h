@@ -302,12 +302,45 @@ int acg_ldpc_decoder_create_quantized_streamed(const acg_ldpc_code *code, const 
  * quantized.  The workspace belongs to the handle, so launches of one handle on different streams are ordered on the device.
  * acg_ldpc_decoder_name returns "BP" or "MS"; acg_ldpc_decoder_layout reports as for the streamed engines (no LDS bytes, one
  * lane per frame, T frames per block, tiles); acg_ldpc_decoder_describe names the kernel, the algorithm, T, the tiles, the bytes
- * of state per frame and the sets.
+ * of state per frame and the sets, and ends in io=llr,post (the LLR entrance below).
  * A code whose frame fits in LDS is decoded faster by acg_ldpc_decoder_create: use this call for the codes that one refuses
  * (check degree above 32, a frame beyond 160 KiB).
  * Not provided: a cascade stage of this engine (acg_ldpc_cascade_create keeps building its stages with the create calls it uses
- * today), LLR input, posterior output, fp16 messages, fp64, a fused Monte-Carlo kernel. */
+ * today), fp16 messages, fp64, a fused Monte-Carlo kernel. */
 int acg_ldpc_decoder_create_layered_streamed(const acg_ldpc_code *code, const acg_ldpc_params *params, acg_ldpc_decoder **out);
+
+/* The LLR entrance of the engine: LLRs in, posterior LLRs out.  For punctured and shortened codes, for LLRs from one's own
+ * demapper, for channels that symbols + snr cannot express, and for whatever wants soft output behind the decoder.
+ *   LLR in          a frame is n float values L_v in natural-log units with the sign convention of the symbol entrance
+ *                   (positive = bit 0).  Per value, in this order: NaN becomes +0; the value is clamped to +-1048576 (2^20: far
+ *                   beyond any useful LLR, and +-inf never meets the arithmetic); min-sum starts from that, sum-product from
+ *                   that times (float) log2(e) in one fp32 multiply — the multiply the symbol entrance applies to the LLR it
+ *                   forms.  Every message starts from 0.  So for LLRs of at most 2^20 that the symbol entrance would have formed
+ *                   itself (float symbols: (float) ((double) y * (2 / sigma^2))) word, flag and iteration are those of the symbol
+ *                   entrance.  There is no snr.
+ *                   A punctured position is L = 0; a shortened one +1048576 (known 0) or -1048576 (known 1) — or +-inf, which
+ *                   is clamped to that.  Nothing special is done for them: they are LLRs like any other.
+ *   posterior out   a frame's posterior is n float values in natural-log units, read at the moment the frame's word, flag and
+ *                   iteration are written: min-sum hands out its posterior P_v as it is, sum-product P_v times (float) ln 2 in
+ *                   one fp32 multiply.  For a frame that latches, the posteriors of the round boundary at which its word is
+ *                   formed — with early_exit = 0 the frame is swept on, the posterior written is still the latched one; for a
+ *                   frame that fails, the posteriors after max_iter iterations (its word is zeros as everywhere); for
+ *                   max_iter = 0 the clamped input (sum-product: scaled and scaled back, two roundings, so not always the
+ *                   input's bits).  The sign bit is the hard decision, -0 included: signbit(post) is the word of every frame
+ *                   with ok = 1.
+ * Both take a handle of acg_ldpc_decoder_create_layered_streamed only.  Each returns non-zero, leaves a message in
+ * acg_ldpc_last_error and launches nothing for a null handle, frames < 0, frames > 0 with a null input (the host call: also null
+ * bits or ok) — all three before a device is looked for — and for any other handle (the message names the create call).
+ * frames == 0 is a no-op that returns 0.  iters* and post* may be NULL. */
+
+/* acg_ldpc_decode_batch_dev with LLRs in and, if post_dev != NULL, frames*n float posteriors out: the same launch path, so the
+ * work-counter ring, the event pair and the stream rules at the top of this header hold for it */
+int acg_ldpc_decode_batch_llr_dev(acg_ldpc_decoder *dec, const float *llr_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                                  int32_t *iters_dev, float *post_dev, void *stream);
+/* host buffers, through the pipelined two-set staging path of acg_ldpc_decode_batch_f32 (4 bytes in per value; 4 more out per
+ * value when post is given) */
+int acg_ldpc_decode_batch_llr(acg_ldpc_decoder *dec, const float *llr, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters,
+                              float *post);
 
 /* ---- OSD: ordered-statistics decoding (Fossorier-Lin) of order 0 and 1 (build-added) ------ */
 

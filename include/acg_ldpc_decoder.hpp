@@ -340,9 +340,39 @@ private:
 // (acg_ldpc_decoder_create_layered_streamed): any code size, any check degree; word and flag of every frame equal those of
 // BeliefPropagationDecoder(max_iter, true, 256) / MinSumDecoder(max_iter, scale, true, 256) on every code both accept.  A code
 // whose frame fits in LDS is decoded faster by those.
-class StreamedLayeredBPDecoder : public BeliefPropagationDecoder {
+
+// what the two classes below add to their flooding-or-layered base: the create call, and the LLR entrance (acg_ldpc.h:
+// acg_ldpc_decode_batch_llr*) — LLRs in, posterior LLRs out
+template <class Base>
+class StreamedLayeredIo : public Base {
 public:
-    explicit StreamedLayeredBPDecoder(int max_iter) : BeliefPropagationDecoder(max_iter, true, 0) {}
+    using Base::Base;
+    struct LlrResult {
+        std::vector<uint8_t> bits, ok;   // frames*n bytes (zeros for a failed frame), frames flags
+        std::vector<int32_t> iters;      // frames
+        std::vector<float> post;         // frames*n posterior LLRs (natural-log units; the sign bit is the bit); empty when not asked for
+    };
+    // L: frames*n LLRs, positive = bit 0 (NaN counts as 0, every value is clamped to +-2^20; punctured = 0, shortened = +-2^20)
+    LlrResult decode_llr_batch(const TMatrix &H, const std::vector<float> &L, bool posteriors = true) {
+        const size_t n = H[0].size(), frames = L.size() / n;
+        LlrResult r;
+        r.bits.resize(frames * n);
+        r.ok.resize(frames);
+        r.iters.resize(frames);
+        if (posteriors) r.post.resize(frames * n);
+        this->with_handle(H, [&](acg_ldpc_decoder *d) {
+            Base::check(acg_ldpc_decode_batch_llr(d, L.data(), (int64_t) frames, r.bits.data(), r.ok.data(), r.iters.data(),
+                                                  posteriors ? r.post.data() : nullptr));
+        });
+        return r;
+    }
+    // device buffers, asynchronous on `stream` (null: the handle's own)
+    void decode_llr_batch_dev(const TMatrix &H, const float *llr_dev, int64_t frames, uint32_t *bits_dev, uint8_t *ok_dev,
+                              int32_t *iters_dev = nullptr, float *post_dev = nullptr, void *stream = nullptr) {
+        this->with_handle(H, [&](acg_ldpc_decoder *d) {
+            Base::check(acg_ldpc_decode_batch_llr_dev(d, llr_dev, frames, bits_dev, ok_dev, iters_dev, post_dev, stream));
+        });
+    }
 
 protected:
     int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
@@ -350,14 +380,14 @@ protected:
     }
 };
 
-class StreamedLayeredMinSumDecoder : public MinSumDecoder {
+class StreamedLayeredBPDecoder : public StreamedLayeredIo<BeliefPropagationDecoder> {
 public:
-    explicit StreamedLayeredMinSumDecoder(int max_iter, double scale = 1.0) : MinSumDecoder(max_iter, scale, true, 0) {}
+    explicit StreamedLayeredBPDecoder(int max_iter) : StreamedLayeredIo<BeliefPropagationDecoder>(max_iter, true, 0) {}
+};
 
-protected:
-    int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
-        return acg_ldpc_decoder_create_layered_streamed(code, &p, out);
-    }
+class StreamedLayeredMinSumDecoder : public StreamedLayeredIo<MinSumDecoder> {
+public:
+    explicit StreamedLayeredMinSumDecoder(int max_iter, double scale = 1.0) : StreamedLayeredIo<MinSumDecoder>(max_iter, scale, true, 0) {}
 };
 
 // build-added; not in the reference.  Fixed-point layered min-sum (acg_ldpc_decoder_create_quantized): integer channel values,
