@@ -12,9 +12,9 @@ from .codes import regular_ldpc  # noqa: F401
 from .decoder import (BeliefPropagationDecoder, CascadeDecoder, Decoder, MinSumDecoder, OSDDecoder, QPADMMDecoder, QuantConfig,  # noqa: F401
                       QuantizedMinSumDecoder, StreamedLayeredBPDecoder, StreamedLayeredMinSumDecoder, StreamedQuantizedMinSumDecoder)
 from .experiment import (CodesEvaluator, ExperimentDetail, ExperimentResult, merge_cascade_results, merge_exp_details,  # noqa: F401
-                         merge_exp_results, quant_structs, run_experiment, run_experiment_cascade, run_experiment_codes,
-                         run_experiment_detail, run_experiment_grid, run_experiment_inproc, run_experiment_quants,
-                         run_experiment_sharded, shard_range)
+                         merge_exp_results, quant_structs, rate_match_pattern, run_experiment, run_experiment_cascade,
+                         run_experiment_codes, run_experiment_detail, run_experiment_grid, run_experiment_inproc,
+                         run_experiment_quants, run_experiment_rm, run_experiment_sharded, shard_range)
 
 
 def read_pcm(path):

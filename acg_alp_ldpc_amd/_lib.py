@@ -64,6 +64,7 @@ ALGO_BP, ALGO_MINSUM, ALGO_QPADMM, ALGO_OSD = 0, 1, 2, 3
 EVENT_PSEUDO, EVENT_NO_WORD, EVENT_NONCODEWORD = 1, 2, 3
 PREC_DEFAULT, PREC_F64, PREC_F32, PREC_F16 = 0, 1, 2, 3
 NOISE_DEVICE_PHILOX, NOISE_HOST_MT19937 = 0, 1
+RM_SENT, RM_PUNCTURED, RM_SHORTENED = 0, 1, 2
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_STREAMED = 0, 1, 2
 SCHEDULE_FLOODING, SCHEDULE_LAYERED = 0, 1
 
@@ -133,6 +134,8 @@ SYMBOLS = {
     "acg_ldpc_transmit_host": (C.c_int, [_vp, _i64, _i32, _i64, _i64, _f64, _vp]),
     "acg_ldpc_llr_variance": (_f64, [_f64]),
     "acg_ldpc_awgn_dev": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _vp]),
+    "acg_ldpc_mc_run_rm": (C.c_int, [_vp, C.POINTER(McCfg), _vp, C.POINTER(McResult)]),
+    "acg_ldpc_rm_channel_dev": (C.c_int, [_vp, C.POINTER(McCfg), _vp, _vp, _vp, _vp]),
     "acg_ldpc_debug_ring_tasks": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _i64, _vp]),
     "acg_ldpc_debug_layers": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),
     "acg_ldpc_debug_layers_block": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _i64]),

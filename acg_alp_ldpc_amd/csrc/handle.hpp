@@ -219,6 +219,8 @@ struct acg_ldpc_decoder {
     std::unique_ptr<acg::HostPipe> pipe;  // pipelined staging of the host-buffer entry points (created on first use)
     // MC through engines without an in-kernel generator (streamed): chunk buffers
     acg::DeviceBuf mc_y;
+    // rate-matched runs (acg_ldpc_mc_run_rm): the pattern of the call, the raw-error counts of a chunk (its channel values: mc_y)
+    acg::DeviceBuf rm_pattern, rm_raw;
     // MC
     acg::DeviceBuf cw_dev;
     int64_t cw_count = 0;

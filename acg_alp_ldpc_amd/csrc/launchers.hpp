@@ -61,6 +61,18 @@ hipError_t classify_grid_launch(const void *y, int y_is_f64, const uint32_t *bit
                                 int64_t n_cw, unsigned long long *counters, const int32_t *row_ptr, const int32_t *edge_var, int m,
                                 hipStream_t s);
 
+// ---- mc_rm_kernels.hip: Monte-Carlo for punctured / shortened codes (acg_ldpc_mc_run_rm) ----
+// noise -> symbol -> channel value of frames x n positions in one pass: fp32 LLRs (q == null; inv_var2 = 2 / sigma^2) or q's
+// int16 channel values into out; pattern: n bytes of ACG_LDPC_RM_*, null = all sent; raw (may be null): frames raw-error
+// counts, zeroed here on s
+hipError_t rm_channel_launch(void *out, const QuantArgs *q, int32_t *raw, int64_t frames, int n, int nwords, int64_t first_frame,
+                             uint64_t seed, const uint32_t *cw_packed, int64_t n_cw, float sigma, double inv_var2, const uint8_t *pattern,
+                             hipStream_t s);
+// classify_grid_launch for one decoder, with raw[f] in place of the Hamming count over the symbols
+hipError_t classify_rm_launch(const int32_t *raw, const uint32_t *bits, const uint8_t *ok, const int32_t *iters, int64_t frames, int n,
+                              int nwords, int64_t first_frame, const uint32_t *cw_packed, int64_t n_cw, unsigned long long *counters,
+                              hipStream_t s);
+
 // ---- cascade_kernels.hip: the glue of a two-stage decode, per chunk of frames (an int32 count: at most 65536) ----
 // idx[0 .. *count) = the frames with ok == 0, ascending; stage (may be null) = 1 for every frame.  idx: `frames` entries
 hipError_t cascade_select_launch(const uint8_t *ok, int32_t frames, int32_t *idx, int32_t *count, uint8_t *stage, hipStream_t s);

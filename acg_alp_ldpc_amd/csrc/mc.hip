@@ -1,6 +1,6 @@
 // C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo.  acg_ldpc_mc_run, the detail run, the QP-ADMM
 // parameter grid, the quantiser grid of the fixed-point engine, the run through a cascade (cascade.hip), the evaluator of a batch
-// of codes, and the generators (device AWGN, host codewords and transmit).
+// of codes, the generators (device AWGN, host codewords and transmit), and the run for punctured and shortened codes.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
@@ -1126,6 +1126,132 @@ static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cf
 
 int acg_ldpc_awgn_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
     return guarded([&] { return acg_ldpc_awgn_dev_impl(d, cfg, y_dev, stream); });
+}
+
+// ---------------------------------------------------------------- Monte-Carlo for punctured and shortened codes
+// ACG_MC_RM_CHUNK=<frames>: developer / test switch that lowers the chunk of a rate-matched run (README, developer variables)
+static int64_t mc_rm_chunk(int64_t chunk) {
+    const char *e = getenv("ACG_MC_RM_CHUNK");
+    const int64_t v = e ? atoll(e) : 0;
+    return v > 0 ? std::min(chunk, v) : chunk;
+}
+
+// What the two calls refuse, in the order the header states; `sink` is res or out_dev.  0: the handle takes channel values.
+static int rm_check(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, const void *sink, const char *call) {
+    if (!d || !cfg || !sink) {
+        set_error("null argument");
+        return 1;
+    }
+    if (check_mc_cfg(cfg)) return 1;
+    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
+        set_error(std::string(call) + ": device noise only (ACG_LDPC_NOISE_DEVICE_PHILOX)");
+        return 1;
+    }
+    for (int v = 0; pattern && v < d->c.n; v++)
+        if (pattern[v] > ACG_LDPC_RM_SHORTENED) {
+            set_error(std::string(call) + ": pattern[" + std::to_string(v) + "] = " + std::to_string((int) pattern[v]) +
+                      " is not ACG_LDPC_RM_SENT, _PUNCTURED or _SHORTENED");
+            return 1;
+        }
+    if (!d->streaml && d->layered_wg != acg_ldpc_decoder::LayeredWg::q) {
+        set_error(std::string(call) + " needs a decoder of acg_ldpc_decoder_create_layered_streamed, acg_ldpc_decoder_create_quantized or "
+                  "acg_ldpc_decoder_create_quantized_streamed");
+        return 3;
+    }
+    return 0;
+}
+
+// the pattern of this call into the handle's copy -> its device address, null for an all-sent run.  s: the stream the
+// generator is about to run on — what it still holds may read the previous pattern, so it is waited for first (calls on
+// different streams of the caller's are the caller's to order, as for the codewords).  Caller holds d->mu.
+static int rm_pattern_dev(acg_ldpc_decoder *d, const uint8_t *pattern, hipStream_t s, const uint8_t **out) {
+    *out = nullptr;
+    if (!pattern) return 0;
+    if (d->rm_pattern.p) HIP_OK(hipStreamSynchronize(s));
+    if (int rc = d->rm_pattern.reserve((size_t) (d->c.n + 3) & ~(size_t) 3)) return rc;
+    HIP_OK(hipMemcpy(d->rm_pattern.p, pattern, (size_t) d->c.n, hipMemcpyHostToDevice));
+    *out = d->rm_pattern.as<uint8_t>();
+    return 0;
+}
+
+// the generator launch of frames [first, first + fc) of cfg on stream s
+static int rm_channel(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pat_dev, int64_t first, int64_t fc, void *out,
+                      int32_t *raw, hipStream_t s) {
+    const SentWords cw = sent_words(d, cfg);
+    const double var = acg_ldpc_llr_variance(cfg->snr);
+    HIP_OK(rm_channel_launch(out, d->streaml ? nullptr : &d->qargs, raw, fc, d->c.n, (d->c.n + 31) / 32, first, cfg->seed, cw.dev, cw.n,
+                             (float) channel_sigma(cfg->snr), 2.0 / var, pat_dev, s));
+    return 0;
+}
+
+static int acg_ldpc_rm_channel_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, void *out_dev,
+                                        int32_t *raw_dev, void *stream) {
+    if (int rc = rm_check(d, cfg, pattern, out_dev, "acg_ldpc_rm_channel_dev")) return rc;
+    if (cfg->frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    if (int rc = ensure_codewords(d, cfg)) return rc;
+    const hipStream_t s = stream ? (hipStream_t) stream : d->stream;
+    const uint8_t *pat_dev = nullptr;
+    if (int rc = rm_pattern_dev(d, pattern, s, &pat_dev)) return rc;
+    return rm_channel(d, cfg, pat_dev, cfg->first_frame, cfg->frames, out_dev, raw_dev, s);
+}
+
+int acg_ldpc_rm_channel_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, void *out_dev, int32_t *raw_dev,
+                            void *stream) {
+    return guarded([&] { return acg_ldpc_rm_channel_dev_impl(d, cfg, pattern, out_dev, raw_dev, stream); });
+}
+
+// Per chunk: rm_channel_kernel (channel values into mc_y, raw-error counts) -> the handle's channel-value entrance on its
+// ordinary launch path -> classify_rm_kernel; the chunks, the timing and the counters' read-back of the unfused branch of
+// acg_ldpc_mc_run.
+static int acg_ldpc_mc_run_rm_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res) {
+    if (int rc = rm_check(d, cfg, pattern, res, "acg_ldpc_mc_run_rm")) return rc;
+    std::memset(res, 0, sizeof(*res));
+    if (cfg->frames == 0) return 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    int rc = 0;
+    if ((rc = ensure_codewords(d, cfg))) return rc;
+    const uint8_t *pat_dev = nullptr;
+    if ((rc = rm_pattern_dev(d, pattern, d->stream, &pat_dev))) return rc;
+    const int n = d->c.n, nwords = (n + 31) / 32;
+    const size_t elem = d->streaml ? sizeof(float) : sizeof(int16_t);
+    const int64_t chunk = mc_rm_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4))));
+    const size_t fcap = (size_t) std::min<int64_t>(chunk, cfg->frames);
+    if ((rc = d->mc_y.reserve(fcap * n * elem)) || (rc = d->rm_raw.reserve(fcap * sizeof(int32_t))) ||
+        (rc = d->st_bits.reserve(fcap * nwords * sizeof(uint32_t))) || (rc = d->st_ok.reserve(fcap)) ||
+        (rc = d->st_iters.reserve(fcap * sizeof(int32_t))))
+        return rc;
+    HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+    const SentWords cw = sent_words(d, cfg);
+    int32_t *raw = d->rm_raw.as<int32_t>();
+    float kms = 0;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+        if ((rc = rm_channel(d, cfg, pat_dev, first, fc, d->mc_y.p, raw, d->stream))) return rc;
+        Chunk c;
+        c.a = decode_args(nullptr, 0, fc, 0.0);   // (no symbols, no channel: the channel-value entrances read neither)
+        stage_outputs(d, c.a);
+        const QuantIo qio{d->mc_y.as<int16_t>(), nullptr};
+        const StreamLayIo lio{d->mc_y.as<float>(), nullptr};
+        if ((rc = launch_decode(d, c.a, d->stream, d->streaml ? nullptr : &qio, nullptr, d->streaml ? &lio : nullptr))) return rc;
+        c.slot = d->last_slot;
+        HIP_OK(classify_rm_launch(raw, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, n, nwords, first, cw.dev, cw.n, d->counters_dev(), d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        kms += chunk_ms(d, c);
+    }
+    unsigned long long h[MC_NCOUNTERS];
+    HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
+    counters_to_result(h, res);
+    res->kernel_ms = kms;
+    res->time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+int acg_ldpc_mc_run_rm(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res) {
+    return guarded([&] { return acg_ldpc_mc_run_rm_impl(d, cfg, pattern, res); });
 }
 
 // ---------------------------------------------------------------- host generators

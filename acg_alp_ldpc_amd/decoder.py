@@ -329,7 +329,24 @@ class QuantConfig:
         return _lib.Quant(*self.as_tuple())
 
 
-class QuantizedMinSumDecoder(Decoder):
+class _RmChannel:
+    """acg_ldpc_rm_channel_dev on the classes whose engine has a channel-value entrance"""
+
+    def rm_channel_dev(self, H, cfg, pattern, out_ptr, raw_ptr=None, stream=None):
+        """cfg: a _lib.McCfg (device noise); pattern: uint8 [n] of _lib.RM_* as experiment.rate_match_pattern returns it, or
+        None = all sent.  Device pointers (ints): cfg.frames * n channel values out — float32 LLRs on the streamed layered
+        classes, int16 on the quantized ones — as experiment.run_experiment_rm hands them to the decoder, and, where raw_ptr is
+        given, cfg.frames int32 raw-error counts; asynchronous on `stream` (None = the decoder's own stream)"""
+        with self._lease(H) as (h, code):
+            pat = None
+            if pattern is not None:
+                pat = np.ascontiguousarray(pattern, dtype=np.uint8)
+                if pat.shape != (code.n,):
+                    raise ValueError("pattern must have n = %d entries" % code.n)
+            check(lib().acg_ldpc_rm_channel_dev(h, C.byref(cfg), None if pat is None else pat.ctypes.data, out_ptr, raw_ptr, stream))
+
+
+class QuantizedMinSumDecoder(_RmChannel, Decoder):
     """Build-added fixed-point layered min-sum (acg_ldpc_decoder_create_quantized; not in the reference): integer channel
     values, messages and posteriors, one workgroup per frame, check degree up to 32.  Bit-true: tests/layered_q_ref.py restates it.
     quant: a QuantConfig, a dict of its fields, or None for the defaults.  The schedule is layered and the algorithm min-sum;
@@ -423,7 +440,7 @@ class StreamedQuantizedMinSumDecoder(QuantizedMinSumDecoder):
         return lib().acg_ldpc_decoder_create_quantized_streamed(code._h, C.byref(p), C.byref(q), C.byref(h))
 
 
-class _StreamedLayered:
+class _StreamedLayered(_RmChannel):
     """the create call and handle key of the streamed float layered engine (acg_ldpc_decoder_create_layered_streamed), and its
     LLR entrance: decode_llr_batch / decode_llr_batch_dev, fp32 LLRs in (punctured and shortened positions among them), fp32
     posterior LLRs out.  tests/streamed_layered_io_ref.py restates it."""

@@ -102,6 +102,71 @@ def run_experiment(decoder, codewords, H, snr, frames=None, first_frame=0, noise
                             kernel_ms=res.kernel_ms)
 
 
+def _index_list(n, idx, what):
+    idx = np.asarray(list(idx), dtype=np.int64).ravel()
+    if idx.size and (idx.min() < 0 or idx.max() >= n):
+        raise ValueError("rate_match_pattern: %s index %d is outside 0 ... %d" % (what, int(idx[(idx < 0) | (idx >= n)][0]), n - 1))
+    return idx
+
+
+def rate_match_pattern(n, punctured=(), shortened=()):
+    """The pattern of acg_ldpc_mc_run_rm: uint8 [n], _lib.RM_PUNCTURED at the punctured indices, _lib.RM_SHORTENED at the
+    shortened ones, _lib.RM_SENT elsewhere.  An index in both lists, or outside 0 ... n - 1, is a ValueError."""
+    n = int(n)
+    p, s = _index_list(n, punctured, "punctured"), _index_list(n, shortened, "shortened")
+    both = np.intersect1d(p, s)
+    if both.size:
+        raise ValueError("rate_match_pattern: index %d is both punctured and shortened" % int(both[0]))
+    pat = np.zeros(n, dtype=np.uint8)
+    pat[p] = _lib.RM_PUNCTURED
+    pat[s] = _lib.RM_SHORTENED
+    return pat
+
+
+def _pattern_bytes(pattern, n):
+    """pattern (None = all sent) as the contiguous uint8 [n] the C calls read; values outside a byte are refused here"""
+    if pattern is None:
+        return None
+    a = np.asarray(pattern)
+    if a.shape != (n,):
+        raise ValueError("pattern must have n = %d entries" % n)
+    if a.dtype.kind not in "iub" or (a.size and (a.min() < 0 or a.max() > 255)):
+        raise ValueError("pattern entries are _lib.RM_SENT, RM_PUNCTURED or RM_SHORTENED")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def run_experiment_rm(decoder, codewords, H, snr, pattern=None, frames=None, first_frame=0, seed=1):
+    """acg_ldpc_mc_run_rm: run_experiment with device noise for a punctured / shortened code.  pattern: uint8 [n] as
+    rate_match_pattern returns it (None: every position sent).  A punctured position reaches the decoder as an erasure, a
+    shortened one as a known bit; raw errors are counted over the sent positions; a frame is correct when the word equals the
+    sent one on all n positions.  snr is Es/N0 of a transmitted symbol.  decoder: a StreamedLayeredBPDecoder,
+    StreamedLayeredMinSumDecoder, QuantizedMinSumDecoder or StreamedQuantizedMinSumDecoder (the engines with a channel-value
+    entrance); the library refuses every other.  Other arguments as run_experiment."""
+    from .code import ParityCheckMatrix
+    pat = _pattern_bytes(pattern, H.n if isinstance(H, ParityCheckMatrix) else np.asarray(H).shape[1])   # (before a handle is made)
+    with decoder._lease(H) as (h, code):
+        cfg = McCfg()
+        cw = None
+        if codewords is not None:
+            cw = np.ascontiguousarray(codewords, dtype=np.uint8)
+            assert cw.ndim == 2 and cw.shape[1] == code.n
+            cfg.codewords = cw.ctypes.data
+            cfg.n_codewords = cw.shape[0]
+        if frames is None:
+            if cw is None:
+                raise ValueError("frames required without codewords")
+            frames = cw.shape[0]
+        cfg.frames = int(frames)
+        cfg.first_frame = int(first_frame)
+        cfg.snr = float(snr)
+        cfg.seed = int(seed)
+        cfg.noise = _lib.NOISE_DEVICE_PHILOX
+        res = McResult()
+        check(lib().acg_ldpc_mc_run_rm(h, C.byref(cfg), None if pat is None else pat.ctypes.data, C.byref(res)))
+    return ExperimentResult(**{f: getattr(res, f) for f in ExperimentResult.FIELDS}, time_sec=res.time_sec,
+                            kernel_ms=res.kernel_ms)
+
+
 CASCADE_EXTRAS = ("second_frames", "second_correct", "second_pseudo", "second_sum_iters", "second_kernel_ms")
 
 

@@ -676,6 +676,47 @@ double acg_ldpc_llr_variance(double snr);
  * for global frames [first_frame, first_frame+frames). codewords as in acg_ldpc_mc_cfg (host pointer). */
 int acg_ldpc_awgn_dev(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream);
 
+/* ---- Monte-Carlo runs for punctured and shortened (rate-matched) codes --------------------- */
+
+/* A pattern is n bytes, one per variable (host pointer; NULL = every position sent).  Any other value is refused, and the
+ * message names the first offending index. */
+enum {
+    ACG_LDPC_RM_SENT = 0,      /* transmitted */
+    ACG_LDPC_RM_PUNCTURED = 1, /* not transmitted, unknown to the receiver */
+    ACG_LDPC_RM_SHORTENED = 2  /* not transmitted, known to the receiver */
+};
+
+/* acg_ldpc_mc_run for a rate-matched code, on the handles that have a channel-value entrance: those of
+ * acg_ldpc_decoder_create_layered_streamed (fp32 LLRs), acg_ldpc_decoder_create_quantized and
+ * acg_ldpc_decoder_create_quantized_streamed (int16 channel values).  Device noise only.
+ * Per global frame g and variable v, with bit the bit of codewords[g % n_codewords] (0 for NULL codewords):
+ *   symbol   y = fma(sigma32, z, bit ? -1 : +1), z the Philox / Box-Muller sample of (seed, g, quad v >> 2, element v & 3) and
+ *            sigma32 as in acg_ldpc_awgn_dev: bit for bit the float that call writes for the position.  A position that is
+ *            not sent consumes its sample and discards it, so the noise of the sent positions does not depend on the pattern.
+ *   float handle      sent: (float) ((double) y * (2 / sigma^2)), the symbol entrance's own formula for float symbols;
+ *                     punctured: +0.0f; shortened: +1048576.0f for bit 0, -1048576.0f for bit 1 (the LLR entrance's clamp).
+ *   quantized handle  sent: clamp(rne(llr32 * (float) (1 / llr_step)), +-Cmax) with llr32 as above, NaN -> 0: what
+ *                     acg_ldpc_quantize_dev gives for y; punctured: 0; shortened: +Cmax for bit 0, -Cmax for bit 1.
+ *   raw errors        of a frame: the SENT positions with (bit == 0 && y <= 0) or (bit == 1 && y > 0).
+ *   decode            the handle's channel-value entrance on its ordinary launch path.
+ *   classification    correct <=> ok and the word equals the sent word on all n positions (punctured bits must be recovered,
+ *                     shortened ones kept); pseudo <=> ok and they differ.  The seven counters of acg_ldpc_mc_result are
+ *                     formed as by acg_ldpc_mc_run, with the raw-error count in place of the Hamming figure.
+ * snr is Es/N0 of a TRANSMITTED symbol and is not rescaled by the pattern: the energy per information bit of the
+ * rate-matched code is the caller's arithmetic.
+ * Refused, in this order, with nothing launched: a null dec, cfg or res; a bad cfg (as acg_ldpc_mc_run);
+ * cfg->noise == ACG_LDPC_NOISE_HOST_MT19937; a pattern byte above 2; a handle of any other create call.  frames == 0 zeroes
+ * res and returns 0.  The frames go in the chunks of acg_ldpc_mc_run's route for engines without a generator of their own;
+ * the counters are the same for any chunking and any sharding by first_frame, and acg_ldpc_mc_merge combines shards.
+ * Not provided: host (mt19937) noise; a detail run; cascade and OSD stages; the grid, quants and codes forms; engines without
+ * a channel-value entrance (every handle of acg_ldpc_decoder_create); repetition or bit selection beyond the three states. */
+int acg_ldpc_mc_run_rm(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res);
+/* device-side channel values only, the counterpart of acg_ldpc_awgn_dev: frames*n floats (float handle) or int16 (quantized
+ * handles) into out_dev, and, if raw_dev != NULL, frames int32 raw-error counts.  The same rules and refusals (out_dev in the
+ * place of res). */
+int acg_ldpc_rm_channel_dev(acg_ldpc_decoder *dec, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, void *out_dev,
+                            int32_t *raw_dev, void *stream);
+
 /* diagnostics (used by tests/): evaluates the device phi(x) = -log(tanh(x/2)) (bp.h:34) of the BP kernels
  * on n host values; f64 selects the double variant. */
 int acg_ldpc_debug_phi(const void *x_host, void *out_host, int32_t n, int32_t f64);

@@ -373,6 +373,15 @@ public:
             Base::check(acg_ldpc_decode_batch_llr_dev(d, llr_dev, frames, bits_dev, ok_dev, iters_dev, post_dev, stream));
         });
     }
+    // acg_ldpc_mc_run_rm: a Monte-Carlo run of a punctured / shortened code.  pattern: n bytes of ACG_LDPC_RM_*, empty = all sent
+    acg_ldpc_mc_result run_rate_matched(const TMatrix &H, const acg_ldpc_mc_cfg &cfg, const std::vector<uint8_t> &pattern = {}) {
+        acg_ldpc_mc_result r{};
+        this->with_handle(H, [&](acg_ldpc_decoder *d) {
+            assert(pattern.empty() || pattern.size() == H[0].size());
+            Base::check(acg_ldpc_mc_run_rm(d, &cfg, pattern.empty() ? nullptr : pattern.data(), &r));
+        });
+        return r;
+    }
 
 protected:
     int create(const acg_ldpc_code *code, const acg_ldpc_params &p, acg_ldpc_decoder **out) const override {
@@ -439,6 +448,15 @@ public:
     void quantize_dev(const TMatrix &H, const void *y_dev, bool y_is_f64, int64_t count, double snr, int16_t *c_dev,
                       void *stream = nullptr) {
         with_handle(H, [&](acg_ldpc_decoder *d) { check(acg_ldpc_quantize_dev(d, y_dev, y_is_f64 ? 1 : 0, count, snr, c_dev, stream)); });
+    }
+    // acg_ldpc_mc_run_rm: a Monte-Carlo run of a punctured / shortened code.  pattern: n bytes of ACG_LDPC_RM_*, empty = all sent
+    acg_ldpc_mc_result run_rate_matched(const TMatrix &H, const acg_ldpc_mc_cfg &cfg, const std::vector<uint8_t> &pattern = {}) {
+        acg_ldpc_mc_result r{};
+        with_handle(H, [&](acg_ldpc_decoder *d) {
+            assert(pattern.empty() || pattern.size() == H[0].size());
+            check(acg_ldpc_mc_run_rm(d, &cfg, pattern.empty() ? nullptr : pattern.data(), &r));
+        });
+        return r;
     }
 
 protected:

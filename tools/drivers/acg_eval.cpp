@@ -28,6 +28,13 @@
 //                         min-sum (--minsum-iters, --ms-scale) on the streamed float layered engine,
 //                         acg_ldpc_decoder_create_layered_streamed (fp32 state in device memory: any code size, any check
 //                         degree).  One more block each, Method = BP / MS, behind the others.
+//            [--puncture LIST] [--shorten LIST]   LIST = comma-separated variable indices and a-b ranges: a rate-matched run
+//                         (acg_ldpc_mc_run_rm) — the listed positions are not transmitted; a punctured one reaches the decoder
+//                         as an erasure, a shortened one as a known bit; FER counts all n positions, the Hamming figures the
+//                         sent ones; --snrs stay Es/N0 of a transmitted symbol.  Only together with --qms-engine and / or
+//                         --qms-iters (alone: the LDS engine) and / or --layered-streamed, and with --noise device: those blocks alone are evaluated
+//                         (no BP, QP-ADMM or flooding min-sum block); every other combination is refused before a device is
+//                         looked for.  The output line format is unchanged.
 // Defaults are main.cpp's (OPTIMAL build): optimalH, BP(100), QP-ADMM(1.2, 0.55, 10000, 1e-5), 10000 codewords from
 // mt19937(239'239'239), SNRs -5..0 step 0.5.  --noise host reproduces the reference's frames bit for bit
 // (frame i <- mt19937(i+1)); --noise device keeps generation, decoding and classification on the GPU.
@@ -78,10 +85,45 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    // rate matching: checked before anything is loaded or a device is looked for
+    const bool rm = a.has("--puncture") || a.has("--shorten");
+    std::vector<long> punctured, shortened;
+    if (rm) {
+        if ((a.has("--puncture") && !drv::parse_index_list(a.get("--puncture", ""), punctured)) ||
+            (a.has("--shorten") && !drv::parse_index_list(a.get("--shorten", ""), shortened))) {
+            std::fprintf(stderr, "acg_eval: --puncture LIST / --shorten LIST with LIST of comma-separated indices and a-b ranges\n");
+            return 2;
+        }
+        if (!a.has("--qms-engine") && !a.has("--qms-iters") && layered_streamed.empty()) {
+            std::fprintf(stderr, "acg_eval: --puncture / --shorten need an engine with a channel-value entrance: --qms-engine lds|streamed "
+                                 "[--qms-iters N] or --layered-streamed bp|minsum|bp,minsum\n");
+            return 2;
+        }
+        if (a.has("--cascade") || a.has("--osd-order") || detail) {
+            std::fprintf(stderr, "acg_eval: --puncture / --shorten do not go with --cascade, --osd-order or a detail run\n");
+            return 2;
+        }
+        if (noise == ACG_LDPC_NOISE_HOST_MT19937) {
+            std::fprintf(stderr, "acg_eval: --puncture / --shorten run with device noise only: pass --noise device\n");
+            return 2;
+        }
+    }
     acg_ldpc_code *code = nullptr;
     if (acg_ldpc_code_load_txt(hpath, &code)) drv::die("read_pcm");
     int m, n, E;
     acg_ldpc_code_dims(code, &m, &n, &E);
+    std::vector<uint8_t> pattern;
+    if (rm) {
+        pattern.assign((size_t) n, (uint8_t) ACG_LDPC_RM_SENT);
+        for (int pass = 0; pass < 2; pass++)
+            for (long v : pass ? shortened : punctured) {
+                if (v >= n || pattern[(size_t) v] != ACG_LDPC_RM_SENT) {
+                    std::fprintf(stderr, "acg_eval: --puncture / --shorten index %ld is %s\n", v, v >= n ? "outside the code" : "listed twice");
+                    return 2;
+                }
+                pattern[(size_t) v] = (uint8_t) (pass ? ACG_LDPC_RM_SHORTENED : ACG_LDPC_RM_PUNCTURED);
+            }
+    }
     bool ok;
     std::vector<uint8_t> cws = drv::make_codewords(code, a.get("--G"), 239239239u, tests, &ok);  // main.cpp:63-64
     if (!ok) {
@@ -122,18 +164,19 @@ int main(int argc, char **argv) {
             return false;
         return true;
     };
+    // (a rate-matched run evaluates the engines with a channel-value entrance only: no BP, QP-ADMM or flooding min-sum block)
     acg_ldpc_params p;
-    if (!a.has("--no-bp")) {
+    if (!rm && !a.has("--no-bp")) {
         params_of("bp", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
-    if (!a.has("--no-admm")) {
+    if (!rm && !a.has("--no-admm")) {
         params_of("admm", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
-    if (a.has("--minsum-iters")) {
+    if (!rm && a.has("--minsum-iters")) {
         params_of("minsum", p);
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
@@ -143,7 +186,7 @@ int main(int argc, char **argv) {
         decs.emplace_back();
         decs.back().create(code, p, gpus, ndev);
     }
-    if (a.has("--qms-engine")) {
+    if (a.has("--qms-engine") || (rm && a.has("--qms-iters"))) {   // (rate-matched: --qms-iters alone means the LDS engine)
         params_of("qms", p);
         acg_ldpc_quant q;
         acg_ldpc_quant_default(&q);
@@ -198,7 +241,7 @@ int main(int argc, char **argv) {
                     fevents << d.name() << "," << snr << "," << e.frame << "," << drv::event_kind_name(e.kind) << "," << e.iters << ","
                             << e.raw_errors << "," << e.bit_errors << "," << e.syndrome_weight << std::endl;
             } else
-                r = d.run(cws, n, snr, tests, noise, (uint64_t) a.integer("--seed", 1));
+                r = d.run(cws, n, snr, tests, noise, (uint64_t) a.integer("--seed", 1), rm ? &pattern : nullptr);
             std::cout << "\tSNR: " << snr << ", FER: " << r.fer() << ", (time=" << r.avg_time() << "s)" << std::endl;
             std::cerr << "\t\tAverage hamming distance: " << r.mean_hamming() << std::endl;
             fdata << d.name() << "," << snr << "," << std::sqrt(acg_ldpc_llr_variance(snr)) << "," << r.fer() << ","

@@ -57,6 +57,31 @@ inline std::vector<double> parse_list(const char *s) {
     return out;
 }
 
+// "3,10-12,40" -> 3 10 11 12 40 (comma-separated indices and a-b ranges, a <= b); false for anything else
+inline bool parse_index_list(const char *s, std::vector<long> &out) {
+    const char *p = s;
+    while (*p) {
+        char *end = nullptr;
+        if (*p < '0' || *p > '9') return false;
+        const long a = std::strtol(p, &end, 10);
+        long b = a;
+        p = end;
+        if (*p == '-') {
+            ++p;
+            if (*p < '0' || *p > '9') return false;
+            b = std::strtol(p, &end, 10);
+            p = end;
+        }
+        if (b < a || b - a > (1L << 24)) return false;
+        for (long v = a; v <= b; v++) out.push_back(v);
+        if (*p == ',') {
+            if (!*++p) return false;
+        } else if (*p)
+            return false;
+    }
+    return !out.empty();
+}
+
 struct McOut {
     acg_ldpc_mc_result r;
     double fer() const { return (double) (r.total - r.correct) / (double) r.total; }            // experiment.h:59
@@ -182,7 +207,10 @@ struct MultiGpu {
     }
     const char *name() const { return acg_ldpc_decoder_name(dec[0]); }
 
-    McOut run(const std::vector<uint8_t> &codewords, int n, double snr, int64_t frames, int noise, uint64_t seed) const {
+    // rm != null: a rate-matched run (acg_ldpc_mc_run_rm) with that pattern of n bytes
+    McOut run(const std::vector<uint8_t> &codewords, int n, double snr, int64_t frames, int noise, uint64_t seed,
+              const std::vector<uint8_t> *rm = nullptr) const {
+        const char *call = rm ? "acg_ldpc_mc_run_rm" : "acg_ldpc_mc_run";
         const int W = (int) dec.size();
         std::vector<McOut> part((size_t) W);
         std::vector<std::string> err((size_t) W);
@@ -199,7 +227,9 @@ struct MultiGpu {
                 cfg.noise = noise;
                 cfg.codewords = codewords.empty() ? nullptr : codewords.data();
                 cfg.n_codewords = codewords.empty() ? 0 : (int64_t) (codewords.size() / (size_t) n);
-                if (acg_ldpc_mc_run(dec[(size_t) r], &cfg, &part[(size_t) r].r)) err[(size_t) r] = acg_ldpc_last_error();
+                const int rc = rm ? acg_ldpc_mc_run_rm(dec[(size_t) r], &cfg, rm->data(), &part[(size_t) r].r)
+                                  : acg_ldpc_mc_run(dec[(size_t) r], &cfg, &part[(size_t) r].r);
+                if (rc) err[(size_t) r] = acg_ldpc_last_error();
             });
         for (auto &t : th) t.join();
         McOut tot;
@@ -207,7 +237,7 @@ struct MultiGpu {
         double wall = 0;
         for (int r = 0; r < W; r++) {
             if (!err[(size_t) r].empty()) {
-                std::fprintf(stderr, "acg_ldpc_mc_run (shard %d): %s\n", r, err[(size_t) r].c_str());
+                std::fprintf(stderr, "%s (shard %d): %s\n", call, r, err[(size_t) r].c_str());
                 std::exit(1);
             }
             wall = wall > part[(size_t) r].r.time_sec ? wall : part[(size_t) r].r.time_sec;
