@@ -15,9 +15,8 @@ using namespace acg;
 // ACG_CASCADE_CHUNK=<frames>: developer / test switch that lowers the chunk of a cascade call (README, developer variables)
 int64_t acg::cascade_chunk_frames(int64_t frames, size_t row_bytes) {
     const int64_t chunk = host_chunk_frames(std::max<int64_t>(frames, 1), row_bytes);
-    const char *e = getenv("ACG_CASCADE_CHUNK");
-    const int64_t v = e ? atoll(e) : 0;
-    return v > 0 ? std::min(chunk, v) : chunk;
+    const int64_t v = env_frames("ACG_CASCADE_CHUNK");
+    return v ? std::min(chunk, v) : chunk;
 }
 
 // the hand-over buffers for chunks of up to `frames` frames whose symbol rows have row_bytes
@@ -111,7 +110,7 @@ int acg::cascade_chunk_dev(acg_ldpc_cascade *c, const void *y, int y_is_f64, int
     b.out_ok = c->c_ok.as<uint8_t>();
     b.out_iters = c->c_iters.as<int32_t>();
     const QuantIo io1{c->c_y.as<int16_t>(), nullptr};
-    if (int rc = launch_decode(d1, b, s, c->post_handover ? &io1 : nullptr)) return rc;
+    if (int rc = launch_decode(d1, b, s, c->post_handover ? DecodeIo(&io1) : DecodeIo())) return rc;
     c->pending_slot = d1->last_slot;
     if (hooks && hooks->second_done)
         if (int rc = hooks->second_done(K)) return rc;

@@ -105,7 +105,10 @@ static hipError_t launch_streamed_layered(acg_ldpc_decoder *d, const DecodeArgs 
 }
 
 // launch on stream s (events recorded around the kernel on that stream).  Caller holds d->mu.
-int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio, const QuantGridArgs *qgrid, const StreamLayIo *lio) {
+int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const DecodeIo &io) {
+    const QuantIo *qio = io.q;
+    const QuantGridArgs *qgrid = io.grid;
+    const StreamLayIo *lio = io.llr;
     if (lio && (qio || qgrid || !d->streaml || !lio->llr_in)) {
         set_error("internal: LLRs handed to a launch that cannot take them");
         return 11;
@@ -279,13 +282,18 @@ int acg::launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const 
     return 0;
 }
 
-// outputs of `frames` frames, and room for their symbols as doubles
-int acg::ensure_staging(acg_ldpc_decoder *d, int64_t frames) {
+// the staged outputs (stage_outputs) of `frames` frames
+int acg::reserve_outputs(acg_ldpc_decoder *d, int64_t frames) {
     const size_t f = (size_t) frames, nwords = (size_t) (d->c.n + 31) / 32;
-    if (int rc = d->st_y.reserve(f * d->c.n * sizeof(double))) return rc;
     if (int rc = d->st_bits.reserve(f * nwords * sizeof(uint32_t))) return rc;
     if (int rc = d->st_ok.reserve(f)) return rc;
     return d->st_iters.reserve(f * sizeof(int32_t));
+}
+
+// outputs of `frames` frames, and room for their symbols as doubles
+int acg::ensure_staging(acg_ldpc_decoder *d, int64_t frames) {
+    if (int rc = d->st_y.reserve((size_t) frames * d->c.n * sizeof(double))) return rc;
+    return reserve_outputs(d, frames);
 }
 
 // the decode outputs of a launch into the staging buffers
@@ -306,12 +314,13 @@ DecodeArgs acg::decode_args(const void *y, int y_is_f64, int64_t frames, double 
 }
 
 // One decode chunk on the handle's stream: symbols already on the device in, outputs in the staging buffers (which the
-// caller reserved).  qgrid: `frames` virtual frames of a quantiser grid over the qgrid->fc frames at y (launch_decode).
+// caller reserved).  io: the entrance (launch_decode) — with io.grid, `frames` virtual frames of a quantiser grid over the
+// io.grid->fc frames at y; with io.q or io.llr, channel values in place of y and snr (null and 0: neither is read).
 // Caller holds d->mu, so c.slot is this launch's own event pair.
-int acg::decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const QuantGridArgs *qgrid) {
+int acg::decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const DecodeIo &io) {
     c.a = decode_args(y, y_is_f64, frames, snr);
     stage_outputs(d, c.a);
-    const int rc = launch_decode(d, c.a, d->stream, nullptr, qgrid);
+    const int rc = launch_decode(d, c.a, d->stream, io);
     c.slot = d->last_slot;
     return rc;
 }
@@ -456,7 +465,7 @@ static int decode_batch_host(acg_ldpc_decoder *d, const void *y, int elem, int64
         a.out_bits = reinterpret_cast<uint32_t *>(dev_out);
         a.out_iters = reinterpret_cast<int32_t *>(dev_out + (size_t) fc * nwords * 4);
         a.out_ok = dev_out + (size_t) fc * (nwords * 4 + 4);
-        if (int rc = launch_decode(d, a, s, elem == 2 ? &io : nullptr, nullptr, llr ? &lio : nullptr)) return rc;
+        if (int rc = launch_decode(d, a, s, llr ? DecodeIo(&lio) : elem == 2 ? DecodeIo(&io) : DecodeIo())) return rc;
         HIP_OK(hipMemcpyAsync(P.pin_out[b].p, dev_out, post ? post_off(fc) + (size_t) fc * post_bytes : (size_t) fc * row, hipMemcpyDeviceToHost, s));
         HIP_OK(hipEventRecord(P.done[b], s));
         return 0;
@@ -631,7 +640,7 @@ static int decode_batch_llr_dev_impl(acg_ldpc_decoder *d, const float *llr_dev, 
     a.out_ok = ok_dev;
     a.out_iters = iters_dev;
     const StreamLayIo io{llr_dev, post_dev};
-    return launch_decode(d, a, stream ? (hipStream_t) stream : d->stream, nullptr, nullptr, &io);
+    return launch_decode(d, a, stream ? (hipStream_t) stream : d->stream, &io);
 }
 
 static int decode_batch_llr_impl(acg_ldpc_decoder *d, const float *llr, int64_t frames, uint8_t *bits, uint8_t *ok, int32_t *iters, float *post) {

@@ -1,6 +1,6 @@
 // The handles behind include/acg_ldpc.h and what the host files of the library share: the types a decoder handle holds, the
 // guard of the extern "C" boundary, and one declaration of every host function that one of api.hip / decode.hip / mc.hip /
-// debug.hip defines and another calls.  As with launchers.hpp, the defining file includes it too, so a definition that
+// mc_codes.hip / cascade.hip / debug.hip defines and another calls.  As with launchers.hpp, the defining file includes it too, so a definition that
 // drifts from its declaration does not compile.  Not part of the ABI.
 #pragma once
 
@@ -308,12 +308,23 @@ QuantArgs quant_args(const acg_ldpc_quant &q);
 // ---- decode.hip ----
 double channel_sigma(double snr);
 void fill_channel(DecodeArgs &a, double snr);
-// qio != null: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for; of an
-// OSD handle — soft values instead of a.y (post_out null)
-// qgrid != null: the grid form of a quantized handle — a.frames virtual frames, a quantiser per point instead of the handle's
-// lio != null: the LLR entrance of a streamed float layered handle — LLRs instead of a.y, posteriors where asked for
-int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const QuantIo *qio = nullptr, const QuantGridArgs *qgrid = nullptr,
-                  const StreamLayIo *lio = nullptr);
+// What a launch takes besides the symbols at a.y; none set: the symbol entrance.  A pointer of one of the three types converts,
+// so a call site passes &io of the entrance it means.
+// q: the integer entrance of a quantized handle — channel values instead of a.y, posteriors where asked for; of an OSD handle —
+//    soft values instead of a.y (post_out null)
+// grid: the grid form of a quantized handle — a.frames virtual frames, a quantiser per point instead of the handle's
+// llr: the LLR entrance of a streamed float layered handle — LLRs instead of a.y, posteriors where asked for
+struct DecodeIo {
+    const QuantIo *q = nullptr;
+    const QuantGridArgs *grid = nullptr;
+    const StreamLayIo *llr = nullptr;
+    DecodeIo() = default;
+    DecodeIo(const QuantIo *q_) : q(q_) {}
+    DecodeIo(const QuantGridArgs *grid_) : grid(grid_) {}
+    DecodeIo(const StreamLayIo *llr_) : llr(llr_) {}
+};
+int launch_decode(acg_ldpc_decoder *d, DecodeArgs &a, hipStream_t s, const DecodeIo &io = {});
+int reserve_outputs(acg_ldpc_decoder *d, int64_t frames);
 int ensure_staging(acg_ldpc_decoder *d, int64_t frames);
 void stage_outputs(const acg_ldpc_decoder *d, DecodeArgs &a);
 DecodeArgs decode_args(const void *y, int y_is_f64, int64_t frames, double snr);
@@ -321,10 +332,26 @@ struct Chunk {  // one decode on the handle's stream: its arguments and its even
     DecodeArgs a;
     int slot;
 };
-int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const QuantGridArgs *qgrid = nullptr);
+int decode_chunk(acg_ldpc_decoder *d, const void *y, int y_is_f64, int64_t frames, double snr, Chunk &c, const DecodeIo &io = {});
 float chunk_ms(const acg_ldpc_decoder *d, const Chunk &c);
 // frames per chunk of the pipelined host path for symbol rows of y_bytes: at most 65536 frames / 256 MiB of symbols
 int64_t host_chunk_frames(int64_t frames, size_t y_bytes);
+
+// ---- mc.hip (what mc_codes.hip and cascade.hip call) ----
+int check_mc_cfg(const acg_ldpc_mc_cfg *cfg);
+void pack_codewords(const uint8_t *codewords, int64_t n_codewords, int n, uint32_t *out);
+void noise_host(int n, int64_t first, int64_t fc, double snr, double *out);
+void counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *r);
+int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res);
+// the frames a developer / test variable holds (README, developer variables); 0: not set, or not a positive count
+int64_t env_frames(const char *name);
+int64_t mc_grid_budget();
+// `points` points over `frames` > 0 frames in launches of at most `budget` virtual frames: frames in blocks of fb, points in
+// chunks of npc >= 1, npc * fb <= budget (or one point's fb frames)
+struct PointChunks {
+    int64_t fb, npc;
+};
+PointChunks point_chunks(int64_t budget, int64_t frames, int64_t points);
 
 // ---- cascade.hip ----
 // frames per chunk of a cascade call over `frames` frames of symbol rows of row_bytes (host_chunk_frames; ACG_CASCADE_CHUNK lowers it)

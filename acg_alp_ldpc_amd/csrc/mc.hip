@@ -1,10 +1,10 @@
-// C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo.  acg_ldpc_mc_run, the detail run, the QP-ADMM
-// parameter grid, the quantiser grid of the fixed-point engine, the run through a cascade (cascade.hip), the evaluator of a batch
-// of codes, the generators (device AWGN, host codewords and transmit), and the run for punctured and shortened codes.
+// C ABI of libacg_ldpc_hip.so (include/acg_ldpc.h), part 3: Monte-Carlo on a decoder handle.  The two host loops the runs share
+// — frames in chunks (mc_frames), points x frame blocks (mc_points) — and their callers: acg_ldpc_mc_run, the detail run, the run
+// for punctured and shortened codes; the QP-ADMM parameter grid and the quantiser grid of the fixed-point engine.  Then the run
+// through a cascade (cascade.hip) and the generators (device AWGN, host codewords and transmit).  The evaluator: mc_codes.hip.
 #include <algorithm>
 #include <chrono>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
@@ -13,17 +13,20 @@
 
 using namespace acg;
 
-extern "C" {
-
 // ---------------------------------------------------------------- Monte-Carlo
-static int check_mc_cfg(const acg_ldpc_mc_cfg *cfg) {
+int acg::check_mc_cfg(const acg_ldpc_mc_cfg *cfg) {
     if (!(cfg->frames < 0 || (cfg->codewords && cfg->n_codewords <= 0))) return 0;
     set_error("bad mc cfg");
     return 1;
 }
 
+int64_t acg::env_frames(const char *name) {
+    const char *e = getenv(name);
+    return std::max<int64_t>(0, e ? atoll(e) : 0);
+}
+
 // one byte per bit -> packed words, ORed into out[n_codewords][(n + 31) / 32] (the caller zeroes it)
-static void pack_codewords(const uint8_t *codewords, int64_t n_codewords, int n, uint32_t *out) {
+void acg::pack_codewords(const uint8_t *codewords, int64_t n_codewords, int n, uint32_t *out) {
     const int nwords = (n + 31) / 32;
     for (int64_t f = 0; f < n_codewords; f++)
         for (int v = 0; v < n; v++)
@@ -78,7 +81,7 @@ static SentWords sent_words(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cf
     return {d->cw_dev.as<uint32_t>(), cfg->n_codewords};
 }
 
-static void counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *r) {
+void acg::counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *r) {
     r->correct = (int64_t) c[MC_CORRECT];
     r->pseudo = (int64_t) c[MC_PSEUDO];
     r->total = (int64_t) c[MC_TOTAL];
@@ -90,7 +93,7 @@ static void counters_to_result(const unsigned long long *c, acg_ldpc_mc_result *
 
 // The noise of experiment.h:90-99 (single-threaded order): frame g (0-based global index) is seeded mt19937(g+1) and draws its
 // n deviates from libstdc++ normal_distribution(0, sigma) in index order (channel.h:18-26)
-static void noise_host(int n, int64_t first, int64_t fc, double snr, double *out) {
+void acg::noise_host(int n, int64_t first, int64_t fc, double snr, double *out) {
     const double sigma = channel_sigma(snr);
     for (int64_t f = 0; f < fc; f++) {
         std::mt19937 rnd((uint32_t) (first + f + 1));
@@ -101,8 +104,7 @@ static void noise_host(int n, int64_t first, int64_t fc, double snr, double *out
 
 // Bit-exact transmit of experiment.h:90-99: that noise, and per symbol the single IEEE addition (+-1.0) + deviate
 // (channel.h:24); codewords == null sends the all-zero word
-static void transmit_host(const uint8_t *codewords, int64_t n_codewords, int n, int64_t first_frame, int64_t frames, double snr,
-                          double *y) {
+static void transmit_host(const uint8_t *codewords, int64_t n_codewords, int n, int64_t first_frame, int64_t frames, double snr, double *y) {
     noise_host(n, first_frame, frames, snr, y);
     for (int64_t f = 0; f < frames; f++) {
         const uint8_t *cw = codewords ? codewords + (size_t) ((first_frame + f) % n_codewords) * n : nullptr;
@@ -110,7 +112,25 @@ static void transmit_host(const uint8_t *codewords, int64_t n_codewords, int n, 
     }
 }
 
-void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
+// the device generator's symbols of frames [first, first + fc) of cfg, the sent words from the handle's copy.  Caller holds d->mu.
+static int awgn_frames(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, float *dst, hipStream_t s) {
+    const SentWords cw = sent_words(d, cfg);
+    HIP_OK(awgn_launch(dst, fc, d->c.n, (d->c.n + 31) / 32, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), s));
+    return 0;
+}
+
+// Channel symbols of frames [first, first + fc) of cfg into the device buffer dst, on stream s: doubles from mt19937
+// (experiment.h:90-99, as mc_run_host_noise; yh is the host image, which the copy reads until s is synchronised) or floats from
+// the device generator (awgn_frames, which the loops that run device noise only call directly).  Caller holds d->mu.
+static int mc_symbols(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, void *dst, hipStream_t s, std::vector<double> &yh) {
+    if (cfg->noise != ACG_LDPC_NOISE_HOST_MT19937) return awgn_frames(d, cfg, first, fc, static_cast<float *>(dst), s);
+    yh.resize((size_t) fc * d->c.n);
+    transmit_host(cfg->codewords, cfg->n_codewords, d->c.n, first, fc, cfg->snr, yh.data());
+    HIP_OK(hipMemcpyAsync(dst, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+extern "C" void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
     // merge_exp_results, experiment.h:70-78
     a->correct += b->correct;
     a->pseudo += b->pseudo;
@@ -123,11 +143,10 @@ void acg_ldpc_mc_merge(acg_ldpc_mc_result *a, const acg_ldpc_mc_result *b) {
     a->kernel_ms += b->kernel_ms;
 }
 
-// ACG_MC_DETAIL_CHUNK=<frames>: developer / test switch that lowers the chunk of a detail run (README, developer variables)
-static int64_t mc_detail_chunk(int64_t chunk) {
-    const char *e = getenv("ACG_MC_DETAIL_CHUNK");
-    const int64_t v = e ? atoll(e) : 0;
-    return v > 0 ? std::min(chunk, v) : chunk;
+// `chunk` frames as a developer / test variable lowers them: ACG_MC_CHUNK, ACG_MC_DETAIL_CHUNK, ACG_MC_RM_CHUNK (README)
+static int64_t lowered_chunk(int64_t chunk, const char *name) {
+    const int64_t v = env_frames(name);
+    return v ? std::min(chunk, v) : chunk;
 }
 
 // where a detail run (acg_ldpc_mc_run_detail) collects what goes beyond the seven counters
@@ -150,7 +169,7 @@ static void detail_min_pseudo(acg_ldpc_mc_detail *o, int32_t w, int64_t frame) {
 static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res, DetailSink *ds = nullptr) {
     // Bit-exact experiment.h:80-123: transmit_host, decoded on the device, classified on the host.
     const int n = d->c.n;
-    const int64_t chunk_max = ds ? mc_detail_chunk(1 << 16) : 1 << 16;
+    const int64_t chunk_max = ds ? lowered_chunk(1 << 16, "ACG_MC_DETAIL_CHUNK") : 1 << 16;
     std::vector<double> y;
     std::vector<uint8_t> bits, ok;
     std::vector<int32_t> iters;
@@ -234,7 +253,55 @@ static int mc_run_host_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, ac
     return 0;
 }
 
-static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
+// ---------------------------------------------------------------- frames in chunks on one handle
+// The host loop of the device-noise runs that decode through the handle's ordinary launch: the unfused route of acg_ldpc_mc_run,
+// the detail run, the rate-matched run.  It owns the lock, the codewords, the chunk size — max(256, min(frames, 2^31 /
+// (4 n))) frames, lowered by the developer variable chunk_env — the chunk's channel elements (elem bytes each) in d->mc_y, its
+// three staged outputs, the loop, the synchronisation that ends a chunk, and the chunks' kernel times (res->kernel_ms).  The caller's:
+//   prepare(rows)          its own buffers for chunks of up to `rows` frames: all is reserved before the first enqueue
+//   enqueue(first, fc, c)  frames [first, first + fc) on d->stream: generator -> decode_chunk into c -> classifier (-> its copies)
+//   done(first, fc, c)     host work behind the chunk's synchronisation (the detail run's), or no_chunk_work
+// counted: the classifier counts into d->counters, zeroed here and read into res behind the last chunk; else the caller's own.
+// frames == 0 returns at once: nothing is locked, the device is not touched, and the results stay as the caller zeroed them.
+template <class Prepare, class Enqueue, class Done>
+static int mc_frames(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, size_t elem, const char *chunk_env, acg_ldpc_mc_result *res, bool counted,
+                     Prepare prepare, Enqueue enqueue, Done done) {
+    if (cfg->frames == 0) return 0;
+    std::lock_guard<std::recursive_mutex> lk(d->mu);
+    HIP_OK(hipSetDevice(d->device));
+    if (int rc = ensure_codewords(d, cfg)) return rc;
+    const int64_t cap = (int64_t) (1ull << 31) / ((int64_t) d->c.n * 4);
+    const int64_t chunk = lowered_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, cap)), chunk_env), rows = std::min(chunk, cfg->frames);
+    int rc = 0;
+    if ((rc = d->mc_y.reserve((size_t) rows * d->c.n * elem)) || (rc = reserve_outputs(d, rows)) || (rc = prepare(rows))) return rc;
+    if (counted) HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
+    float kms = 0;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
+        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+        Chunk c;
+        if ((rc = enqueue(first, fc, c))) return rc;
+        HIP_OK(hipStreamSynchronize(d->stream));
+        kms += chunk_ms(d, c);
+        if ((rc = done(first, fc, c))) return rc;
+    }
+    res->kernel_ms = kms;
+    if (!counted) return 0;
+    unsigned long long h[MC_NCOUNTERS];
+    HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
+    counters_to_result(h, res);
+    return 0;
+}
+static int no_chunk_work(int64_t, int64_t, const Chunk &) { return 0; }
+
+// The handles whose acg_ldpc_mc_run takes the unfused route (AWGN kernel -> decode -> classify kernel in the chunks of mc_frames, all
+// on the device) instead of one fused launch: the engines without an in-kernel generator, and the workgroup-per-frame QP-ADMM kernel,
+// whose fused Monte-Carlo variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
+static bool mc_unfused(const acg_ldpc_decoder *d) {
+    return d->streamed || d->streaml || d->pair || d->osd || d->layered_wg != acg_ldpc_decoder::LayeredWg::none ||
+           (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr));
+}
+
+int acg::acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
     if (!d || !cfg || !res) {
         set_error("null argument");
         return 1;
@@ -245,37 +312,20 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
     int rc = 0;
     if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
         rc = mc_run_host_noise(d, cfg, res);
-    } else if (d->streamed || d->streaml || d->pair || d->osd || d->layered_wg != acg_ldpc_decoder::LayeredWg::none || (d->layered && getenv("ACG_LAY_UNFUSED_MC")) || (d->admm && admm_device_unfused_mc(d->admm.get(), nullptr, nullptr))) {
-        // AWGN kernel -> decode -> classify kernel, in bounded chunks, all on the device.  Used by the streamed BP
-        // engine and the workgroup-per-frame layered engine (no in-kernel generator) and by the workgroup-per-frame QP-ADMM kernel, whose fused Monte-Carlo
-        // variant needs 156 VGPRs (3 waves/SIMD) against 117 (4) for the plain decode: 1.6 M vs 2.7 M frames/s.
+    } else if (mc_unfused(d)) {
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
         if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
-        std::lock_guard<std::recursive_mutex> lk(d->mu);
-        HIP_OK(hipSetDevice(d->device));
-        if ((rc = ensure_codewords(d, cfg))) return rc;
         const int n = d->c.n, nwords = (n + 31) / 32;
-        int64_t chunk = std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4)));
-        if ((rc = d->mc_y.reserve((size_t) chunk * n * sizeof(float)))) return rc;
-        if ((rc = ensure_staging(d, std::min<int64_t>(chunk, std::max<int64_t>(cfg->frames, 1))))) return rc;
-        HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
-        const SentWords cw = sent_words(d, cfg);
-        float *mc_y = d->mc_y.as<float>();
-        float kms = 0;
-        for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
-            const int64_t fc = std::min(chunk, cfg->frames - f0);
-            HIP_OK(awgn_launch(mc_y, fc, n, nwords, cfg->first_frame + f0, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
-            Chunk c;
-            if ((rc = decode_chunk(d, mc_y, 0, fc, cfg->snr, c))) return rc;
-            HIP_OK(classify_grid_launch(mc_y, 0, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, 1, n, nwords, cfg->first_frame + f0, cw.dev,
-                                        cw.n, d->counters_dev(), csr_row, csr_col, d->c.m, d->stream));
-            HIP_OK(hipStreamSynchronize(d->stream));
-            kms += chunk_ms(d, c);
-        }
-        unsigned long long h[MC_NCOUNTERS];
-        HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
-        counters_to_result(h, res);
-        res->kernel_ms = kms;
+        auto enqueue = [&](int64_t first, int64_t fc, Chunk &c) {
+            float *mc_y = d->mc_y.as<float>();
+            if (int e = awgn_frames(d, cfg, first, fc, mc_y, d->stream)) return e;
+            if (int e = decode_chunk(d, mc_y, 0, fc, cfg->snr, c)) return e;
+            const SentWords cw = sent_words(d, cfg);
+            HIP_OK(classify_grid_launch(mc_y, 0, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, 1, n, nwords, first, cw.dev, cw.n, d->counters_dev(),
+                                        csr_row, csr_col, d->c.m, d->stream));
+            return 0;
+        };
+        rc = mc_frames(d, cfg, sizeof(float), "ACG_MC_CHUNK", res, true, [](int64_t) { return 0; }, enqueue, no_chunk_work);
     } else {
         std::lock_guard<std::recursive_mutex> lk(d->mu);
         HIP_OK(hipSetDevice(d->device));
@@ -301,95 +351,84 @@ static int acg_ldpc_mc_run_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg,
     return rc;
 }
 
-int acg_ldpc_mc_run(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
+extern "C" int acg_ldpc_mc_run(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_impl(d, cfg, res); });
 }
 
 // ---------------------------------------------------------------- Monte-Carlo detail run
-// Device noise: per chunk AWGN kernel -> plain decode (launch_decode with a.y set: every engine has it) -> classify_detail_kernel,
-// the chunks of the unfused branch of acg_ldpc_mc_run.  Events: the kernel leaves one kind byte per frame; while fewer than
-// cap events are stored the host reads those bytes, takes the lowest non-correct frames of the chunk, and gather_events_kernel
-// writes their records and XOR rows from the chunk's still-resident symbols and outputs.  Chunks run in ascending frame
-// order, so the stored events are the cap lowest frames whatever the chunk size.  Caller holds nothing; d->mu is taken here.
+// Device noise: mc_frames, a chunk being AWGN kernel -> plain decode (launch_decode with a.y set: every engine has it) ->
+// classify_detail_kernel, with the counters copied to pinned memory behind it.  Events: the kernel leaves one kind byte per
+// frame; while fewer than cap events are stored the host reads those bytes, takes the lowest non-correct frames of the chunk,
+// and gather_events_kernel writes their records and XOR rows from the chunk's still-resident symbols and outputs — the one
+// second synchronisation a chunk can have.  Chunks run in ascending frame order, so the stored events are the cap lowest
+// frames whatever the chunk size.  Caller holds nothing.
 static int mc_run_detail_device(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, DetailSink &ds) {
     acg_ldpc_mc_detail *o = ds.out;
     const int32_t *csr_row = nullptr, *csr_col = nullptr;
     if (d->admm) (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
-    std::lock_guard<std::recursive_mutex> lk(d->mu);
-    HIP_OK(hipSetDevice(d->device));
-    int rc = 0;
-    if ((rc = ensure_codewords(d, cfg))) return rc;
     const int n = d->c.n, nwords = (n + 31) / 32;
-    const int64_t chunk = mc_detail_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4))));
-    const size_t fcap = (size_t) chunk;
-    if ((rc = d->mc_y.reserve(fcap * n * sizeof(float)))) return rc;
-    if ((rc = d->st_bits.reserve(fcap * nwords * sizeof(uint32_t)))) return rc;
-    if ((rc = d->st_ok.reserve(fcap))) return rc;
-    if ((rc = d->st_iters.reserve(fcap * sizeof(int32_t)))) return rc;
-    if ((rc = d->det_counters.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
-    if ((rc = d->det_counters_h.reserve(DET_NCOUNTERS * sizeof(unsigned long long)))) return rc;
-    if ((rc = d->det_kind.reserve(fcap))) return rc;
-    if (ds.cap > 0) {
-        const size_t ecap = (size_t) std::min<int64_t>(ds.cap, chunk);   // events one chunk can add
-        if ((rc = d->det_kind_h.reserve(fcap))) return rc;
-        if ((rc = d->det_sel.reserve(ecap * sizeof(int32_t)))) return rc;
-        if ((rc = d->det_sel_h.reserve(ecap * sizeof(int32_t)))) return rc;
-        if ((rc = d->det_events.reserve(ecap * sizeof(acg_ldpc_mc_event)))) return rc;
-        if (ds.words && (rc = d->det_words.reserve(ecap * nwords * sizeof(uint32_t)))) return rc;
-    }
-    unsigned long long *cnt = d->det_counters.as<unsigned long long>(), *cnt_h = d->det_counters_h.as<unsigned long long>();
-    HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DET_NCOUNTERS, d->stream));
-    const SentWords cw = sent_words(d, cfg);
-    float *mc_y = d->mc_y.as<float>();
-    uint8_t *kind = d->det_kind.as<uint8_t>();
-    float kms = 0;
-    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
-        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
+    unsigned long long *cnt = nullptr, *cnt_h = nullptr;
+    uint8_t *kind = nullptr;
+    bool want_events = false;
+    auto prepare = [&](int64_t rows) {
+        const size_t fcap = (size_t) rows, ecap = (size_t) std::min<int64_t>(ds.cap, rows);   // ecap: events one chunk can add
+        int e = 0;
+        if ((e = d->det_counters.reserve(DET_NCOUNTERS * sizeof(unsigned long long))) ||
+            (e = d->det_counters_h.reserve(DET_NCOUNTERS * sizeof(unsigned long long))) || (e = d->det_kind.reserve(fcap)))
+            return e;
+        if (ds.cap > 0 && ((e = d->det_kind_h.reserve(fcap)) || (e = d->det_sel.reserve(ecap * sizeof(int32_t))) ||
+                           (e = d->det_sel_h.reserve(ecap * sizeof(int32_t))) || (e = d->det_events.reserve(ecap * sizeof(acg_ldpc_mc_event))) ||
+                           (ds.words && (e = d->det_words.reserve(ecap * nwords * sizeof(uint32_t))))))
+            return e;
+        cnt = d->det_counters.as<unsigned long long>();
+        cnt_h = d->det_counters_h.as<unsigned long long>();
+        kind = d->det_kind.as<uint8_t>();
+        HIP_OK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * DET_NCOUNTERS, d->stream));
+        return 0;
+    };
+    auto enqueue = [&](int64_t first, int64_t fc, Chunk &c) {
+        float *mc_y = d->mc_y.as<float>();
         HIP_OK(hipMemsetAsync(cnt + DET_MIN_PSEUDO, 0xFF, sizeof(unsigned long long), d->stream));
-        HIP_OK(awgn_launch(mc_y, fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
-        Chunk c;
-        if ((rc = decode_chunk(d, mc_y, 0, fc, cfg->snr, c))) return rc;
-        const DecodeArgs &a = c.a;
-        HIP_OK(classify_detail_launch(mc_y, a.out_bits, a.out_ok, a.out_iters, fc, n, nwords, first, cw.dev, cw.n, cnt, kind, csr_row,
-                                      csr_col, d->c.m, d->stream));
-        const bool want_events = o->n_stored < ds.cap;
+        if (int e = awgn_frames(d, cfg, first, fc, mc_y, d->stream)) return e;
+        if (int e = decode_chunk(d, mc_y, 0, fc, cfg->snr, c)) return e;
+        const SentWords cw = sent_words(d, cfg);
+        HIP_OK(classify_detail_launch(mc_y, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, n, nwords, first, cw.dev, cw.n, cnt, kind, csr_row, csr_col,
+                                      d->c.m, d->stream));
+        want_events = o->n_stored < ds.cap;
         if (want_events) HIP_OK(hipMemcpyAsync(d->det_kind_h.p, kind, (size_t) fc, hipMemcpyDeviceToHost, d->stream));
         HIP_OK(hipMemcpyAsync(cnt_h, cnt, sizeof(unsigned long long) * DET_NCOUNTERS, hipMemcpyDeviceToHost, d->stream));
-        HIP_OK(hipStreamSynchronize(d->stream));
-        kms += chunk_ms(d, c);
-        if (cnt_h[DET_MIN_PSEUDO] != ~0ull)
-            detail_min_pseudo(o, (int32_t) (cnt_h[DET_MIN_PSEUDO] >> 32), first + (int64_t) (cnt_h[DET_MIN_PSEUDO] & 0xFFFFFFFFull));
-        if (want_events) {
-            const uint8_t *kh = d->det_kind_h.as<uint8_t>();
-            int32_t *sel = d->det_sel_h.as<int32_t>();
-            const int64_t room = ds.cap - o->n_stored;
-            int n_sel = 0;
-            for (int64_t f = 0; f < fc && n_sel < room; f++)
-                if (kh[f]) sel[n_sel++] = (int32_t) f;
-            if (n_sel > 0) {
-                HIP_OK(hipMemcpyAsync(d->det_sel.p, sel, (size_t) n_sel * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-                HIP_OK(gather_events_launch(d->det_sel.as<int32_t>(), n_sel, mc_y, a.out_bits, a.out_ok, a.out_iters, kind, n, nwords, first,
-                                            cw.dev, cw.n, csr_row, csr_col, d->c.m, d->det_events.as<acg_ldpc_mc_event>(),
-                                            ds.words ? d->det_words.as<uint32_t>() : nullptr, d->stream));
-                HIP_OK(hipMemcpyAsync(ds.events + o->n_stored, d->det_events.p, (size_t) n_sel * sizeof(acg_ldpc_mc_event),
-                                      hipMemcpyDeviceToHost, d->stream));
-                if (ds.words)
-                    HIP_OK(hipMemcpyAsync(ds.words + (size_t) o->n_stored * nwords, d->det_words.p, (size_t) n_sel * nwords * sizeof(uint32_t),
-                                          hipMemcpyDeviceToHost, d->stream));
-                HIP_OK(hipStreamSynchronize(d->stream));
-                o->n_stored += n_sel;
-            }
-        }
-    }
-    if (cfg->frames > 0) {
-        counters_to_result(cnt_h, &o->base);
+        return 0;
+    };
+    auto done = [&](int64_t first, int64_t fc, const Chunk &c) {
+        counters_to_result(cnt_h, &o->base);   // (the running sums: the last chunk's stand)
         o->word_frames = (int64_t) cnt_h[DET_WORD_FRAMES];
         o->bit_errors = (int64_t) cnt_h[DET_BIT_ERRORS];
         o->noncodeword_frames = (int64_t) cnt_h[DET_NONCODEWORD];
         o->sum_syndrome_weight = (int64_t) cnt_h[DET_SYNDROME];
-    }
-    o->base.kernel_ms = kms;
-    return 0;
+        if (cnt_h[DET_MIN_PSEUDO] != ~0ull)
+            detail_min_pseudo(o, (int32_t) (cnt_h[DET_MIN_PSEUDO] >> 32), first + (int64_t) (cnt_h[DET_MIN_PSEUDO] & 0xFFFFFFFFull));
+        if (!want_events) return 0;
+        const uint8_t *kh = d->det_kind_h.as<uint8_t>();
+        int32_t *sel = d->det_sel_h.as<int32_t>();
+        const int64_t room = ds.cap - o->n_stored;
+        int n_sel = 0;
+        for (int64_t f = 0; f < fc && n_sel < room; f++)
+            if (kh[f]) sel[n_sel++] = (int32_t) f;
+        if (n_sel == 0) return 0;
+        const SentWords cw = sent_words(d, cfg);
+        HIP_OK(hipMemcpyAsync(d->det_sel.p, sel, (size_t) n_sel * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+        HIP_OK(gather_events_launch(d->det_sel.as<int32_t>(), n_sel, d->mc_y.as<float>(), c.a.out_bits, c.a.out_ok, c.a.out_iters, kind, n, nwords,
+                                    first, cw.dev, cw.n, csr_row, csr_col, d->c.m, d->det_events.as<acg_ldpc_mc_event>(),
+                                    ds.words ? d->det_words.as<uint32_t>() : nullptr, d->stream));
+        HIP_OK(hipMemcpyAsync(ds.events + o->n_stored, d->det_events.p, (size_t) n_sel * sizeof(acg_ldpc_mc_event), hipMemcpyDeviceToHost, d->stream));
+        if (ds.words)
+            HIP_OK(hipMemcpyAsync(ds.words + (size_t) o->n_stored * nwords, d->det_words.p, (size_t) n_sel * nwords * sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, d->stream));
+        HIP_OK(hipStreamSynchronize(d->stream));
+        o->n_stored += n_sel;
+        return 0;
+    };
+    return mc_frames(d, cfg, sizeof(float), "ACG_MC_DETAIL_CHUNK", &o->base, false, prepare, enqueue, done);
 }
 
 static int acg_ldpc_mc_run_detail_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out,
@@ -416,12 +455,12 @@ static int acg_ldpc_mc_run_detail_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cf
     return rc;
 }
 
-int acg_ldpc_mc_run_detail(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out, acg_ldpc_mc_event *events,
-                           uint32_t *words, int64_t cap) {
+extern "C" int acg_ldpc_mc_run_detail(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, acg_ldpc_mc_detail *out, acg_ldpc_mc_event *events,
+                                      uint32_t *words, int64_t cap) {
     return guarded([&] { return acg_ldpc_mc_run_detail_impl(d, cfg, out, events, words, cap); });
 }
 
-void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b) {
+extern "C" void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b) {
     acg_ldpc_mc_merge(&a->base, &b->base);
     a->word_frames += b->word_frames;
     a->bit_errors += b->bit_errors;
@@ -432,30 +471,70 @@ void acg_ldpc_mc_detail_merge(acg_ldpc_mc_detail *a, const acg_ldpc_mc_detail *b
     if (a->min_pseudo_weight <= 0) a->min_pseudo_weight = -1, a->min_pseudo_frame = -1;
 }
 
-// ---------------------------------------------------------------- Monte-Carlo over a QP-ADMM parameter grid
-// virtual frames (points x frames) one launch of the grid path covers, and so the size of its per-frame outputs: the
-// staging of a 65536-frame decode.  ACG_MC_GRID_BUDGET: developer / test override (README, developer variables).
-static int64_t mc_grid_budget() {
-    const char *e = getenv("ACG_MC_GRID_BUDGET");
-    const int64_t v = e ? atoll(e) : 0;
-    return v > 0 ? std::min<int64_t>(v, (int64_t) 1 << 30) : 65536;
+// ---------------------------------------------------------------- points x frame blocks on one handle
+// virtual frames (points x frames) one launch of a grid covers, and so the size of its per-frame outputs: the staging of a
+// 65536-frame decode.  ACG_MC_GRID_BUDGET: developer / test override (README, developer variables).
+int64_t acg::mc_grid_budget() {
+    const int64_t v = env_frames("ACG_MC_GRID_BUDGET");
+    return v ? std::min<int64_t>(v, (int64_t) 1 << 30) : 65536;
 }
 
-// channel symbols of global frames [first, first + fc) into d->st_y: doubles from mt19937 (experiment.h:90-99, as
-// mc_run_host_noise) or floats from the device generator (as the unfused path of acg_ldpc_mc_run).  Caller holds d->mu.
-static int mc_grid_noise(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, int64_t first, int64_t fc, std::vector<double> &yh) {
+PointChunks acg::point_chunks(int64_t budget, int64_t frames, int64_t points) {
+    const int64_t fb = std::min(frames, budget);
+    return {fb, std::max<int64_t>(1, std::min(budget / fb, points))};
+}
+
+// The host loop of the grids that decode `points` points from the same frames in shared launches: the single-launch path of the
+// QP-ADMM parameter grid, and the quantiser grid.  Frames in blocks of fb, points in chunks of npc: a block's symbols
+// are drawn once, into d->st_y; a launch decodes np * fc virtual frames into the staged outputs, and classify_grid_kernel adds
+// them to rows [c0, c0 + np) of d->grid_counters.  `rows` >= points rows are zeroed before and read into h behind the loop, the
+// points' into res[res_of[j]] (null: res[j]) with their share of each chunk's kernel time; the others are the caller's.  The caller's:
+//   block(first, fc, counters)  what it enqueues once per block behind the symbols (the parameter grid's guard row)
+//   decode(c0, np, fc, c)       points [c0, c0 + np) over the block's fc frames: what their launch needs, and decode_chunk into c
+// Caller holds d->mu and has set the device; cfg->frames > 0.
+struct PointsRun {
+    int64_t budget, points, rows;
+    const int32_t *res_of, *csr_row, *csr_col;   // (csr: for QP-ADMM, whose flag is not IsCodeword; or null)
+};
+template <class Block, class Decode>
+static int mc_points(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const PointsRun &run, acg_ldpc_mc_result *res,
+                     std::vector<unsigned long long> &h, Block block, Decode decode) {
+    int rc = ensure_codewords(d, cfg);
+    if (rc) return rc;
     const int n = d->c.n, nwords = (n + 31) / 32;
-    if (cfg->noise == ACG_LDPC_NOISE_HOST_MT19937) {
-        yh.resize((size_t) fc * n);
-        transmit_host(cfg->codewords, cfg->n_codewords, n, first, fc, cfg->snr, yh.data());
-        HIP_OK(hipMemcpyAsync(d->st_y.p, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    } else {
-        const SentWords cw = sent_words(d, cfg);
-        HIP_OK(awgn_launch(d->st_y.as<float>(), fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), d->stream));
+    const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
+    const SentWords cw = sent_words(d, cfg);
+    const auto [fb, npc] = point_chunks(run.budget, cfg->frames, run.points);
+    if ((rc = d->st_y.reserve((size_t) fb * n * sizeof(double))) || (rc = reserve_outputs(d, npc * fb))) return rc;
+    const size_t counter_bytes = (size_t) run.rows * MC_NCOUNTERS * sizeof(unsigned long long);
+    if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
+    unsigned long long *counters = d->grid_counters.as<unsigned long long>();
+    HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
+    auto res_of = [&](int64_t j) -> acg_ldpc_mc_result & { return res[run.res_of ? run.res_of[j] : j]; };
+    std::vector<double> yh;
+    for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
+        const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
+        if ((rc = mc_symbols(d, cfg, first, fc, d->st_y.p, d->stream, yh))) return rc;
+        if ((rc = block(first, fc, counters))) return rc;
+        for (int64_t c0 = 0; c0 < run.points; c0 += npc) {
+            const int64_t np = std::min(npc, run.points - c0);
+            Chunk c;
+            if ((rc = decode(c0, np, fc, c))) return rc;
+            HIP_OK(classify_grid_launch(d->st_y.p, host, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
+                                        counters + (size_t) c0 * MC_NCOUNTERS, run.csr_row, run.csr_col, d->c.m, d->stream));
+            HIP_OK(hipStreamSynchronize(d->stream));
+            const float ms = chunk_ms(d, c);
+            for (int64_t j = 0; j < np; j++) res_of(c0 + j).kernel_ms += (double) ms / (double) np;
+        }
+        HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
     }
+    h.resize((size_t) run.rows * MC_NCOUNTERS);
+    HIP_OK(hipMemcpy(h.data(), counters, counter_bytes, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < run.points; j++) counters_to_result(&h[(size_t) j * MC_NCOUNTERS], &res_of(j));
     return 0;
 }
 
+// ---------------------------------------------------------------- Monte-Carlo over a QP-ADMM parameter grid
 static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu,
                                      int32_t n_points, acg_ldpc_mc_result *res) {
     if (!d || !cfg) {
@@ -480,76 +559,52 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     const double e_min = admm_device_e_min(d->admm.get());
-    std::vector<int32_t> run;  // the points that decode; the others are guard points (qp_admm.h:108-114)
-    for (int32_t k = 0; k < n_points; k++)
-        if (!(e_min * mu[k] <= alpha[k])) run.push_back(k);
+    std::vector<int32_t> run, guard;  // the points that decode, and the guard points (qp_admm.h:108-114)
+    for (int32_t k = 0; k < n_points; k++) (e_min * mu[k] <= alpha[k] ? guard : run).push_back(k);
     const int64_t n_run = (int64_t) run.size();
-    const bool any_guard = n_run < n_points;
+    const bool any_guard = !guard.empty();
     const bool single_launch = admm_device_has_grid_kernel(d->admm.get());
     int rc = 0;
     if (cfg->frames > 0 && (any_guard || (single_launch && n_run > 0))) {
-        if ((rc = ensure_codewords(d, cfg))) return rc;
+        // mc_points over the points that decode in shared launches (none without the grid kernel: they follow below), with
+        // one more counter row, n_run, that every guard point shares: a block's raw symbols classified once, without outputs
         const int n = d->c.n, nwords = (n + 31) / 32;
         const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
         const int32_t *csr_row = nullptr, *csr_col = nullptr;
         (void) admm_device_unfused_mc(d->admm.get(), &csr_row, &csr_col);
-        const SentWords cw = sent_words(d, cfg);
-        // frames in blocks of fb, points in chunks of npc: one launch covers npc * fb <= budget virtual frames (or one
-        // point's fb frames); its outputs use the handle's staging buffers
-        const int64_t budget = mc_grid_budget();
-        const int64_t fb = std::min<int64_t>(cfg->frames, budget);
-        const int64_t npc = single_launch ? std::max<int64_t>(1, std::min<int64_t>(budget / fb, std::max<int64_t>(n_run, 1))) : 1;
-        if ((rc = ensure_staging(d, npc * fb))) return rc;
-        // counters: row j < n_run = point run[j], row n_run = every guard point
-        const size_t counter_bytes = (size_t) (n_run + 1) * MC_NCOUNTERS * sizeof(unsigned long long);
-        if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
-        unsigned long long *counters = d->grid_counters.as<unsigned long long>();
-        HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
-        std::vector<double> yh, ca, cm;
+        const PointsRun pr{mc_grid_budget(), single_launch ? n_run : 0, n_run + 1, run.data(), csr_row, csr_col};
+        std::vector<unsigned long long> h;
+        std::vector<double> ca, cm;
         std::vector<unsigned char> pt, inv;
-        for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
-            const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
-            if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
+        auto guard_row = [&](int64_t first, int64_t fc, unsigned long long *counters) {
+            const SentWords cw = sent_words(d, cfg);
             if (any_guard)
                 HIP_OK(classify_grid_launch(d->st_y.p, host, nullptr, nullptr, nullptr, fc, 1, n, nwords, first, cw.dev, cw.n,
                                             counters + (size_t) n_run * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
-            for (int64_t c0 = 0; single_launch && c0 < n_run; c0 += npc) {
-                const int64_t np = std::min(npc, n_run - c0);
-                ca.resize((size_t) np);
-                cm.resize((size_t) np);
-                for (int64_t j = 0; j < np; j++) {
-                    ca[(size_t) j] = alpha[run[(size_t) (c0 + j)]];
-                    cm[(size_t) j] = mu[run[(size_t) (c0 + j)]];
-                }
-                admm_grid_tables(d->admm.get(), ca.data(), cm.data(), (int) np, pt, inv);
-                const size_t pt_bytes = (pt.size() + 255) & ~(size_t) 255;
-                if ((rc = d->grid_tab.reserve(pt_bytes + inv.size()))) return rc;
-                unsigned char *tab = d->grid_tab.as<unsigned char>();
-                // (the stream is idle here: the previous chunk ended with a synchronisation, so pt / inv may be rewritten)
-                HIP_OK(hipMemcpyAsync(tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
-                HIP_OK(hipMemcpyAsync(tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
-                Chunk c;
-                admm_grid_bind(d->admm.get(), tab, tab + pt_bytes, (uint32_t) fc);
-                rc = decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c);
-                admm_grid_bind(d->admm.get(), nullptr, nullptr, 0);
-                if (rc) return rc;
-                HIP_OK(classify_grid_launch(d->st_y.p, host, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
-                                            counters + (size_t) c0 * MC_NCOUNTERS, csr_row, csr_col, d->c.m, d->stream));
-                HIP_OK(hipStreamSynchronize(d->stream));
-                const float ms = chunk_ms(d, c);
-                for (int64_t j = 0; j < np; j++) res[run[(size_t) (c0 + j)]].kernel_ms += (double) ms / (double) np;
+            return 0;
+        };
+        // the chunk's per-point tables, bound to the handle for the one launch that reads them
+        auto decode = [&](int64_t c0, int64_t np, int64_t fc, Chunk &c) {
+            ca.resize((size_t) np);
+            cm.resize((size_t) np);
+            for (int64_t j = 0; j < np; j++) {
+                ca[(size_t) j] = alpha[run[(size_t) (c0 + j)]];
+                cm[(size_t) j] = mu[run[(size_t) (c0 + j)]];
             }
-            HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
-        }
-        std::vector<unsigned long long> h((size_t) (n_run + 1) * MC_NCOUNTERS);
-        HIP_OK(hipMemcpy(h.data(), counters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        std::vector<char> is_run((size_t) n_points, 0);
-        for (int64_t j = 0; j < n_run; j++) {
-            is_run[(size_t) run[(size_t) j]] = 1;
-            if (single_launch) counters_to_result(&h[(size_t) j * MC_NCOUNTERS], &res[run[(size_t) j]]);
-        }
-        for (int32_t k = 0; k < n_points; k++)
-            if (!is_run[(size_t) k]) counters_to_result(&h[(size_t) n_run * MC_NCOUNTERS], &res[k]);
+            admm_grid_tables(d->admm.get(), ca.data(), cm.data(), (int) np, pt, inv);
+            const size_t pt_bytes = (pt.size() + 255) & ~(size_t) 255;
+            if (int e = d->grid_tab.reserve(pt_bytes + inv.size())) return e;
+            unsigned char *tab = d->grid_tab.as<unsigned char>();
+            // (the stream is idle here: the previous chunk ended with a synchronisation, so pt / inv may be rewritten)
+            HIP_OK(hipMemcpyAsync(tab, pt.data(), pt.size(), hipMemcpyHostToDevice, d->stream));
+            HIP_OK(hipMemcpyAsync(tab + pt_bytes, inv.data(), inv.size(), hipMemcpyHostToDevice, d->stream));
+            admm_grid_bind(d->admm.get(), tab, tab + pt_bytes, (uint32_t) fc);
+            const int e = decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c);
+            admm_grid_bind(d->admm.get(), nullptr, nullptr, 0);   // (released on the error path too)
+            return e;
+        };
+        if ((rc = mc_points(d, cfg, pr, res, h, guard_row, decode))) return rc;
+        for (int32_t k : guard) counters_to_result(&h[(size_t) n_run * MC_NCOUNTERS], &res[k]);
     }
     if (!single_launch && n_run > 0) {
         // one point after another on this handle: acg_ldpc_mc_run with the handle re-parameterised in place
@@ -578,17 +633,16 @@ static int acg_ldpc_mc_run_grid_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg 
     return rc;
 }
 
-int acg_ldpc_mc_run_grid(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu, int32_t n_points,
-                         acg_ldpc_mc_result *res) {
+extern "C" int acg_ldpc_mc_run_grid(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const double *alpha, const double *mu, int32_t n_points,
+                                    acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_grid_impl(d, cfg, alpha, mu, n_points, res); });
 }
 
 // ---------------------------------------------------------------- Monte-Carlo over a grid of quantisers
-// The fixed-point layered min-sum engine's counterpart of the parameter grid above: the chunk loop of its single-launch path
-// (frames in blocks of fb, points in chunks of npc, npc * fb <= the budget virtual frames per launch; the noise of a block drawn
-// once), with bp_layered_q_kernel's grid form reading point k's quantiser from row k of a 32-byte-per-point device table.  The
-// table of the whole call is written once; a chunk's launch points at its first row.  No guard points: every quantiser is
-// checked before anything is launched.  The arguments are checked before the handle is read.
+// The fixed-point layered min-sum engine's counterpart of the parameter grid above: mc_points, with bp_layered_q_kernel's grid
+// form reading point k's quantiser from row k of a 32-byte-per-point device table.  The table of the whole call is written
+// once; a chunk's launch points at its first row.  No guard points: every quantiser is checked before anything is launched.
+// The arguments are checked before the handle is read.
 static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
                                        acg_ldpc_mc_result *res) {
     if (!d || !cfg || !quants || !res) {
@@ -618,23 +672,7 @@ static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cf
     if (cfg->frames == 0) return 0;
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
-    int rc = 0;
-    if ((rc = ensure_codewords(d, cfg))) return rc;
-    const int n = d->c.n, nwords = (n + 31) / 32;
     const int host = cfg->noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
-    const SentWords cw = sent_words(d, cfg);
-    const int64_t budget = std::min<int64_t>(mc_grid_budget(), ((int64_t) 1 << 30) - 1);   // (the kernel's 32-bit virtual frame)
-    const int64_t fb = std::min<int64_t>(cfg->frames, budget);
-    const int64_t npc = std::max<int64_t>(1, std::min<int64_t>(budget / fb, n_points));
-    // the symbols of one block of frames serve every point; the per-frame outputs are those of npc * fb virtual frames
-    if ((rc = ensure_staging(d, fb))) return rc;
-    if ((rc = d->st_bits.reserve((size_t) (npc * fb) * nwords * sizeof(uint32_t))) || (rc = d->st_ok.reserve((size_t) (npc * fb))) ||
-        (rc = d->st_iters.reserve((size_t) (npc * fb) * sizeof(int32_t))))
-        return rc;
-    const size_t counter_bytes = (size_t) n_points * MC_NCOUNTERS * sizeof(unsigned long long);
-    if ((rc = d->grid_counters.reserve(counter_bytes))) return rc;
-    unsigned long long *counters = d->grid_counters.as<unsigned long long>();
-    HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, d->stream));
     constexpr size_t ROW = 8 * sizeof(int32_t);   // inv_step ... offset: QuantArgs without the two pointers of the integer entrance
     static_assert(offsetof(QuantArgs, c_in) == ROW, "the quantiser table holds the head of QuantArgs");
     std::vector<unsigned char> tab_h((size_t) n_points * ROW);
@@ -642,38 +680,24 @@ static int acg_ldpc_mc_run_quants_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cf
         const QuantArgs qa = quant_args(quants[k]);
         std::memcpy(&tab_h[(size_t) k * ROW], &qa, ROW);
     }
-    if ((rc = d->grid_tab.reserve(tab_h.size()))) return rc;
+    if (int rc = d->grid_tab.reserve(tab_h.size())) return rc;
     // (the stream is idle: every call on this handle ends with a synchronisation, so the table may be rewritten)
     HIP_OK(hipMemcpy(d->grid_tab.p, tab_h.data(), tab_h.size(), hipMemcpyHostToDevice));
-    std::vector<double> yh;
-    for (int64_t f0 = 0; f0 < cfg->frames; f0 += fb) {
-        const int64_t fc = std::min(fb, cfg->frames - f0), first = cfg->first_frame + f0;
-        if ((rc = mc_grid_noise(d, cfg, first, fc, yh))) return rc;
-        for (int64_t c0 = 0; c0 < n_points; c0 += npc) {
-            const int64_t np = std::min<int64_t>(npc, n_points - c0);
-            const QuantGridArgs g{d->grid_tab.as<const int32_t>() + (size_t) c0 * 8, (uint32_t) fc};
-            Chunk c;
-            if ((rc = decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c, &g))) return rc;
-            HIP_OK(classify_grid_launch(d->st_y.p, host, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, np, n, nwords, first, cw.dev, cw.n,
-                                        counters + (size_t) c0 * MC_NCOUNTERS, nullptr, nullptr, d->c.m, d->stream));
-            HIP_OK(hipStreamSynchronize(d->stream));
-            const float ms = chunk_ms(d, c);
-            for (int64_t j = 0; j < np; j++) res[c0 + j].kernel_ms += (double) ms / (double) np;
-        }
-        HIP_OK(hipStreamSynchronize(d->stream));  // (yh is rewritten by the next block)
-    }
-    std::vector<unsigned long long> h((size_t) n_points * MC_NCOUNTERS);
-    HIP_OK(hipMemcpy(h.data(), counters, counter_bytes, hipMemcpyDeviceToHost));
+    // a counter row per point, row k into res[k]; the budget stays within the kernel's 32-bit virtual frame
+    const PointsRun pr{std::min<int64_t>(mc_grid_budget(), ((int64_t) 1 << 30) - 1), n_points, n_points, nullptr, nullptr, nullptr};
+    std::vector<unsigned long long> h;
+    auto decode = [&](int64_t c0, int64_t np, int64_t fc, Chunk &c) {
+        const QuantGridArgs g{d->grid_tab.as<const int32_t>() + (size_t) c0 * 8, (uint32_t) fc};
+        return decode_chunk(d, d->st_y.p, host, np * fc, cfg->snr, c, &g);
+    };
+    if (int rc = mc_points(d, cfg, pr, res, h, [](int64_t, int64_t, unsigned long long *) { return 0; }, decode)) return rc;
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int32_t k = 0; k < n_points; k++) {
-        counters_to_result(&h[(size_t) k * MC_NCOUNTERS], &res[k]);
-        res[k].time_sec = wall;
-    }
+    for (int32_t k = 0; k < n_points; k++) res[k].time_sec = wall;
     return 0;
 }
 
-int acg_ldpc_mc_run_quants(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
-                           acg_ldpc_mc_result *res) {
+extern "C" int acg_ldpc_mc_run_quants(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const acg_ldpc_quant *quants, int32_t n_points,
+                                      acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_quants_impl(d, cfg, quants, n_points, res); });
 }
 
@@ -728,13 +752,7 @@ static int cascade_mc_run_impl(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, 
     std::vector<double> yh;
     for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
         const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
-        if (host) {
-            yh.resize((size_t) fc * n);
-            transmit_host(cfg->codewords, cfg->n_codewords, n, first, fc, cfg->snr, yh.data());
-            HIP_OK(hipMemcpyAsync(c->mc_y.p, yh.data(), yh.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        } else {
-            HIP_OK(awgn_launch(c->mc_y.as<float>(), fc, n, nwords, first, cfg->seed, cw.dev, cw.n, (float) channel_sigma(cfg->snr), s));
-        }
+        if ((rc = mc_symbols(d0, cfg, first, fc, c->mc_y.p, s, yh))) return rc;
         CascadeHooks hooks;
         hooks.first_done = [&] {
             HIP_OK(classify_grid_launch(c->mc_y.p, host, bits, ok, iters, fc, 1, n, nwords, first, cw.dev, cw.n, counters, row0, col0, d0->c.m, s));
@@ -765,11 +783,11 @@ static int cascade_mc_run_impl(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, 
     return 0;
 }
 
-int acg_ldpc_cascade_mc_run(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, acg_ldpc_cascade_result *res) {
+extern "C" int acg_ldpc_cascade_mc_run(acg_ldpc_cascade *c, const acg_ldpc_mc_cfg *cfg, acg_ldpc_cascade_result *res) {
     return guarded([&] { return cascade_mc_run_impl(c, cfg, res); });
 }
 
-void acg_ldpc_cascade_merge(acg_ldpc_cascade_result *a, const acg_ldpc_cascade_result *b) {
+extern "C" void acg_ldpc_cascade_merge(acg_ldpc_cascade_result *a, const acg_ldpc_cascade_result *b) {
     acg_ldpc_mc_merge(&a->total, &b->total);
     acg_ldpc_mc_merge(&a->first, &b->first);
     a->second_frames += b->second_frames;
@@ -777,337 +795,6 @@ void acg_ldpc_cascade_merge(acg_ldpc_cascade_result *a, const acg_ldpc_cascade_r
     a->second_pseudo += b->second_pseudo;
     a->second_sum_iters += b->second_sum_iters;
     a->second_kernel_ms += b->second_kernel_ms;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- Monte-Carlo over a batch of parity-check matrices
-// The local search of optimize_H.cpp:89-104 scores a fresh H per proposal.  An evaluator scores a batch of them in one
-// call: the codes that the workgroup-per-frame QP-ADMM kernel accepts decode in ONE launch per launch shape (codes
-// instance of admm_block_kernel, virtual frame g = code * frames + f), with their tables in one device buffer written by
-// one copy; nothing is allocated, created or destroyed per code.
-struct acg_ldpc_evaluator {
-    acg_ldpc_params p;
-    int device = 0;
-    int cu_count = 256;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the decode launch of the chunk in flight
-    mutable std::mutex mu;  // (mutable: acg_ldpc_evaluator_describe reads `last` under it)
-    static constexpr int WORK_RING = 32;  // per-launch work counters, as acg_ldpc_decoder::work_ring
-    DeviceBuf work_ring;
-    uint64_t launch_seq = 0;
-    DeviceBuf st_y, st_bits, st_ok, st_iters;  // symbols [code][frame][n] and decode outputs of the chunk in flight
-    DeviceBuf noise;     // host-noise mode: the deviates [frame][n] of the frame block in flight, shared by every code
-    PinnedBuf pin_tab;   // host image of tab
-    DeviceBuf tab;       // the chunk in flight: AdmmDevTables[codes] | CodeRef[codes] | per code: its tables, its sent words
-    DeviceBuf counters;  // [codes of the call][MC_NCOUNTERS]
-    std::string last = "qpadmm mc_codes=none";  // what the last run did (acg_ldpc_evaluator_describe)
-};
-
-static int acg_ldpc_evaluator_create_impl(const acg_ldpc_params *params, acg_ldpc_evaluator **out) {
-    if (!params || !out) {
-        set_error("null argument");
-        return 1;
-    }
-    if (params->algo != ACG_LDPC_QPADMM) {
-        set_error("acg_ldpc_evaluator_create needs QP-ADMM parameters");
-        return 1;
-    }
-    if (params->max_iter < 0) {
-        set_error("max_iter must be >= 0");
-        return 1;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available: libacg_ldpc_hip has no CPU fallback");
-        return 20;
-    }
-    int dev = params->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev >= ndev) {
-        set_error("device ordinal out of range");
-        return 1;
-    }
-    struct Drop { void operator()(acg_ldpc_evaluator *x) const { acg_ldpc_evaluator_destroy(x); } };
-    std::unique_ptr<acg_ldpc_evaluator, Drop> own(new acg_ldpc_evaluator());
-    acg_ldpc_evaluator *ev = own.get();
-    ev->p = *params;
-    ev->p.fast_setup = 1;  // (the contract: every code as on a decoder created with fast_setup = 1)
-    ev->device = dev;
-    HIP_OK(hipSetDevice(dev));
-    hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, dev));
-    ev->cu_count = prop.multiProcessorCount;
-    HIP_OK(hipStreamCreateWithFlags(&ev->stream, hipStreamNonBlocking));
-    HIP_OK(hipEventCreate(&ev->ev0));
-    HIP_OK(hipEventCreate(&ev->ev1));
-    if (int rc = ev->work_ring.reserve(sizeof(unsigned long long) * acg_ldpc_evaluator::WORK_RING)) return rc;
-    *out = own.release();
-    return 0;
-}
-
-static int acg_ldpc_mc_run_codes_impl(acg_ldpc_evaluator *ev, const acg_ldpc_code *const *codes, int32_t n_codes,
-                                      const acg_ldpc_mc_cfg *cfgs, acg_ldpc_mc_result *res) {
-    if (n_codes < 1) {
-        set_error("acg_ldpc_mc_run_codes: n_codes must be >= 1");
-        return 1;
-    }
-    if (!ev || !codes || !cfgs || !res) {
-        set_error("null argument");
-        return 1;
-    }
-    for (int32_t k = 0; k < n_codes; k++) {
-        if (!codes[k]) {
-            set_error("null argument");
-            return 1;
-        }
-        if (codes[k]->c.m != codes[0]->c.m || codes[k]->c.n != codes[0]->c.n) {
-            set_error("acg_ldpc_mc_run_codes: codes of different m or n");
-            return 1;
-        }
-        if (check_mc_cfg(&cfgs[k])) return 1;
-        if (cfgs[k].frames != cfgs[0].frames || cfgs[k].first_frame != cfgs[0].first_frame || !(cfgs[k].snr == cfgs[0].snr) ||
-            cfgs[k].seed != cfgs[0].seed || cfgs[k].noise != cfgs[0].noise) {
-            set_error("acg_ldpc_mc_run_codes: frames, first_frame, snr, seed and noise must be equal in every cfg");
-            return 1;
-        }
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    std::memset(res, 0, sizeof(*res) * (size_t) n_codes);
-    std::lock_guard<std::mutex> lk(ev->mu);
-    HIP_OK(hipSetDevice(ev->device));
-    const acg_ldpc_params &p = ev->p;
-    const acg_ldpc_mc_cfg &cfg = cfgs[0];
-    const int n = codes[0]->c.n, m = codes[0]->c.m, nwords = (n + 31) / 32;
-    const int host = cfg.noise == ACG_LDPC_NOISE_HOST_MT19937 ? 1 : 0;
-    // parameters whose decoder handle runs the workgroup-per-frame kernel on the codes that kernel accepts
-    const bool eligible = p.engine != ACG_LDPC_ENGINE_STREAMED && (p.lanes_per_frame == 0 || p.lanes_per_frame == 256) && p.max_iter > 0 &&
-                          p.precision != ACG_LDPC_PREC_F16;
-    struct Item {
-        int32_t k;
-        std::unique_ptr<AdmmDevice, acg_ldpc_decoder::AdmmDrop> plan;
-        std::vector<unsigned char> blob;
-    };
-    std::vector<Item> items;                 // the codes that decode in shared launches
-    std::vector<int32_t> guard, per_code;    // guard codes (qp_admm.h:108-114); codes that take a decoder handle of their own
-    for (int32_t k = 0; k < n_codes && cfg.frames > 0; k++) {
-        const Code &c = codes[k]->c;
-        double e_min = 1e9;
-        for (double e : c.admm.e) e_min = std::min(e_min, e);
-        if (e_min * p.mu <= p.alpha) {
-            guard.push_back(k);
-            continue;
-        }
-        Item it;
-        it.k = k;
-        std::string why;
-        if (eligible) it.plan.reset(admm_codes_plan(c, p, it.blob, why));
-        if (it.plan) items.push_back(std::move(it));
-        else per_code.push_back(k);
-    }
-    // launch groups: the codes of one launch shape, in the order given; group -1 = the guard codes (classified, never decoded)
-    std::vector<std::pair<int, std::vector<const Item *>>> groups;
-    for (const Item &it : items) {
-        const int shape = admm_codes_shape(it.plan.get());
-        size_t g = 0;
-        while (g < groups.size() && groups[g].first != shape) g++;
-        if (g == groups.size()) groups.push_back({shape, {}});
-        groups[g].second.push_back(&it);
-    }
-    const int n_groups = (int) groups.size();
-    std::vector<Item> guard_items(guard.size());
-    if (!guard.empty()) {
-        groups.push_back({-1, {}});
-        for (size_t j = 0; j < guard.size(); j++) {
-            guard_items[j].k = guard[j];
-            groups.back().second.push_back(&guard_items[j]);
-        }
-    }
-    int rc = 0, n_chunks = 0;
-    if (!groups.empty()) {
-        const int64_t budget = mc_grid_budget();
-        const int64_t fb = std::min<int64_t>(cfg.frames, budget);
-        const size_t counter_bytes = (size_t) n_codes * MC_NCOUNTERS * sizeof(unsigned long long);
-        if ((rc = ev->counters.reserve(counter_bytes))) return rc;
-        unsigned long long *counters = ev->counters.as<unsigned long long>();
-        HIP_OK(hipMemsetAsync(counters, 0, counter_bytes, ev->stream));
-        const size_t TB = admm_codes_tables_bytes();
-        auto up = [](size_t x) { return (x + 255) & ~(size_t) 255; };
-        // (one block is kept: with frames <= budget — the search's 1000 — it is drawn and uploaded once per call.  With more
-        // frames than the budget a chunk is one code and every code redraws the blocks: correct, and not the case this serves)
-        std::vector<double> nz;          // host noise of the frame block [nz_first, nz_first + nz_fc)
-        int64_t nz_first = -1, nz_fc = 0;
-        bool nz_on_device = false;
-        std::vector<size_t> blob_off, cw_off;
-        for (const auto &grp : groups) {
-            const bool decode = grp.first >= 0;
-            const int64_t n_grp = (int64_t) grp.second.size();
-            const int64_t npc = std::max<int64_t>(1, std::min<int64_t>(budget / fb, n_grp));
-            for (int64_t c0 = 0; c0 < n_grp; c0 += npc) {
-                const int64_t np = std::min(npc, n_grp - c0);
-                const Item *const *chunk = grp.second.data() + c0;
-                // ---- the chunk's tables: one host image, one copy (the stream is idle here: every chunk ends with a synchronisation)
-                size_t total = up((size_t) np * TB) + up((size_t) np * sizeof(CodeRef)), lds = 0;
-                blob_off.assign((size_t) np, 0);
-                cw_off.assign((size_t) np, 0);
-                for (int64_t j = 0; j < np; j++) {
-                    const acg_ldpc_mc_cfg &cj = cfgs[chunk[j]->k];
-                    blob_off[(size_t) j] = total;
-                    total += up(chunk[j]->blob.size());
-                    cw_off[(size_t) j] = total;
-                    if (cj.codewords) total += up((size_t) cj.n_codewords * nwords * sizeof(uint32_t));
-                    if (decode) lds = std::max(lds, admm_codes_lds(chunk[j]->plan.get()));
-                }
-                if ((rc = ev->tab.reserve(total)) || (rc = ev->pin_tab.reserve(total))) return rc;
-                unsigned char *hp = ev->pin_tab.as<unsigned char>(), *dp = ev->tab.as<unsigned char>();
-                std::memset(hp, 0, total);
-                CodeRef *refs_h = reinterpret_cast<CodeRef *>(hp + up((size_t) np * TB));
-                const CodeRef *refs = reinterpret_cast<const CodeRef *>(dp + up((size_t) np * TB));
-                for (int64_t j = 0; j < np; j++) {
-                    const Item &it = *chunk[j];
-                    const acg_ldpc_mc_cfg &cj = cfgs[it.k];
-                    CodeRef &r = refs_h[j];
-                    r.cw_packed = nullptr;
-                    r.n_cw = 1;
-                    r.row_ptr = r.edge_var = nullptr;
-                    r.counters = counters + (size_t) it.k * MC_NCOUNTERS;
-                    if (decode) {
-                        std::memcpy(hp + blob_off[(size_t) j], it.blob.data(), it.blob.size());
-                        admm_codes_tables(it.plan.get(), (uintptr_t) (dp + blob_off[(size_t) j]), hp + (size_t) j * TB);
-                        size_t rp = 0, evr = 0;
-                        admm_codes_csr(it.plan.get(), &rp, &evr);
-                        r.row_ptr = reinterpret_cast<const int32_t *>(dp + blob_off[(size_t) j] + rp);
-                        r.edge_var = reinterpret_cast<const int32_t *>(dp + blob_off[(size_t) j] + evr);
-                    }
-                    if (cj.codewords) {
-                        pack_codewords(cj.codewords, cj.n_codewords, n, reinterpret_cast<uint32_t *>(hp + cw_off[(size_t) j]));
-                        r.cw_packed = reinterpret_cast<const uint32_t *>(dp + cw_off[(size_t) j]);
-                        r.n_cw = cj.n_codewords;
-                    }
-                }
-                HIP_OK(hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, ev->stream));
-                int grid_cap = 0;
-                if (decode) {
-                    std::string why;
-                    grid_cap = admm_codes_grid_cap(chunk[0]->plan.get(), lds, ev->cu_count, why);
-                    if (grid_cap <= 0) {
-                        set_error(why);
-                        return 10;
-                    }
-                    n_chunks++;
-                }
-                const size_t vf = (size_t) (np * fb);
-                if ((rc = ev->st_y.reserve(vf * n * (host ? sizeof(double) : sizeof(float))))) return rc;
-                if (decode && ((rc = ev->st_bits.reserve(vf * nwords * sizeof(uint32_t))) || (rc = ev->st_ok.reserve(vf)) ||
-                               (rc = ev->st_iters.reserve(vf * sizeof(int32_t)))))
-                    return rc;
-                for (int64_t f0 = 0; f0 < cfg.frames; f0 += fb) {
-                    const int64_t fc = std::min(fb, cfg.frames - f0), first = cfg.first_frame + f0;
-                    // ---- symbols [code][frame][n]: one noise block serves every code
-                    if (host) {
-                        if (nz_first != first || nz_fc != fc) {
-                            nz.resize((size_t) fc * n);
-                            noise_host(n, first, fc, cfg.snr, nz.data());
-                            nz_first = first;
-                            nz_fc = fc;
-                            nz_on_device = false;
-                        }
-                        if (!nz_on_device) {
-                            if ((rc = ev->noise.reserve(nz.size() * sizeof(double)))) return rc;
-                            HIP_OK(hipMemcpyAsync(ev->noise.p, nz.data(), nz.size() * sizeof(double), hipMemcpyHostToDevice, ev->stream));
-                            nz_on_device = true;
-                        }
-                        HIP_OK(codes_symbols_launch(ev->noise.as<double>(), ev->st_y.as<double>(), fc, np, n, nwords, first, refs, ev->stream));
-                    } else {
-                        for (int64_t j = 0; j < np; j++)
-                            HIP_OK(awgn_launch(ev->st_y.as<float>() + (size_t) j * fc * n, fc, n, nwords, first, cfg.seed, refs_h[j].cw_packed,
-                                               refs_h[j].n_cw, (float) channel_sigma(cfg.snr), ev->stream));
-                    }
-                    if (!decode) {
-                        HIP_OK(classify_codes_launch(ev->st_y.p, host, nullptr, nullptr, nullptr, fc, np, n, nwords, first, refs, m, ev->stream));
-                        HIP_OK(hipStreamSynchronize(ev->stream));
-                        continue;
-                    }
-                    DecodeArgs a = decode_args(ev->st_y.p, host, np * fc, cfg.snr);
-                    a.out_bits = ev->st_bits.as<uint32_t>();
-                    a.out_ok = ev->st_ok.as<uint8_t>();
-                    a.out_iters = ev->st_iters.as<int32_t>();
-                    a.max_iter = p.max_iter;
-                    a.early_exit = p.early_exit;
-                    a.ms_scale = (float) p.ms_scale;
-                    a.work_counter = ev->work_ring.as<unsigned long long>() + (ev->launch_seq++ % acg_ldpc_evaluator::WORK_RING);
-                    HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned long long), ev->stream));
-                    HIP_OK(hipEventRecord(ev->ev0, ev->stream));
-                    HIP_OK(admm_codes_launch(chunk[0]->plan.get(), dp, (uint32_t) fc, lds, grid_cap, a, ev->stream));
-                    HIP_OK(hipEventRecord(ev->ev1, ev->stream));
-                    HIP_OK(classify_codes_launch(ev->st_y.p, host, a.out_bits, a.out_ok, a.out_iters, fc, np, n, nwords, first, refs, m, ev->stream));
-                    HIP_OK(hipStreamSynchronize(ev->stream));
-                    float ms = 0;
-                    if (hipEventElapsedTime(&ms, ev->ev0, ev->ev1) == hipSuccess)
-                        for (int64_t j = 0; j < np; j++) res[chunk[j]->k].kernel_ms += (double) ms / (double) np;
-                }
-            }
-        }
-        std::vector<unsigned long long> h((size_t) n_codes * MC_NCOUNTERS);
-        HIP_OK(hipMemcpy(h.data(), counters, counter_bytes, hipMemcpyDeviceToHost));
-        for (const auto &grp : groups)
-            for (const Item *it : grp.second) {
-                const double kms = res[it->k].kernel_ms;
-                counters_to_result(&h[(size_t) it->k * MC_NCOUNTERS], &res[it->k]);
-                res[it->k].kernel_ms = kms;
-            }
-    }
-    // codes the shared launches do not take: a decoder handle of their own, on this evaluator's stream
-    for (size_t j = 0; j < per_code.size() && !rc; j++) {
-        const int32_t k = per_code[j];
-        acg_ldpc_decoder *d = nullptr;
-        if ((rc = acg_ldpc_decoder_create_impl(codes[k], &p, &d, ev->stream))) break;
-        rc = acg_ldpc_mc_run_impl(d, &cfgs[k], &res[k]);
-        const std::string keep = rc ? last_error() : std::string();
-        acg_ldpc_decoder_destroy(d);
-        if (rc) set_error(keep);
-    }
-    char b[256];
-    if (n_groups > 0 || (eligible && per_code.empty()))
-        snprintf(b, sizeof b, "qpadmm mc_codes=single-launch groups=%d chunks=%d codes=%d guard=%d per_code=%d", n_groups, n_chunks, (int) n_codes,
-                 (int) guard.size(), (int) per_code.size());
-    else
-        snprintf(b, sizeof b, "qpadmm mc_codes=per-code codes=%d guard=%d per_code=%d", (int) n_codes, (int) guard.size(), (int) per_code.size());
-    ev->last = b;
-    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int32_t k = 0; k < n_codes; k++) res[k].time_sec = wall;
-    return rc;
-}
-
-extern "C" {
-
-int acg_ldpc_evaluator_create(const acg_ldpc_params *params, acg_ldpc_evaluator **out) {
-    return guarded([&] { return acg_ldpc_evaluator_create_impl(params, out); });
-}
-
-void acg_ldpc_evaluator_destroy(acg_ldpc_evaluator *ev) {
-    if (!ev) return;
-    (void) hipSetDevice(ev->device);
-    if (ev->stream) (void) hipStreamSynchronize(ev->stream);
-    if (ev->ev0) (void) hipEventDestroy(ev->ev0);
-    if (ev->ev1) (void) hipEventDestroy(ev->ev1);
-    if (ev->stream) (void) hipStreamDestroy(ev->stream);
-    delete ev;  // (the buffers belong to its members)
-}
-
-int acg_ldpc_mc_run_codes(acg_ldpc_evaluator *ev, const acg_ldpc_code *const *codes, int32_t n_codes, const acg_ldpc_mc_cfg *cfgs,
-                          acg_ldpc_mc_result *res) {
-    return guarded([&] { return acg_ldpc_mc_run_codes_impl(ev, codes, n_codes, cfgs, res); });
-}
-
-int32_t acg_ldpc_evaluator_describe(const acg_ldpc_evaluator *ev, char *buf, int32_t cap) {
-    if (!ev) return 0;
-    std::string s;
-    {
-        std::lock_guard<std::mutex> lk(ev->mu);  // (a run on another thread writes it)
-        s = ev->last;
-    }
-    return copy_text(s, buf, cap);
 }
 
 static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
@@ -1118,24 +805,14 @@ static int acg_ldpc_awgn_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cf
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     HIP_OK(hipSetDevice(d->device));
     if (int rc = ensure_codewords(d, cfg)) return rc;
-    const SentWords cw = sent_words(d, cfg);
-    HIP_OK(awgn_launch(y_dev, cfg->frames, d->c.n, (d->c.n + 31) / 32, cfg->first_frame, cfg->seed, cw.dev, cw.n,
-                       (float) channel_sigma(cfg->snr), stream ? (hipStream_t) stream : d->stream));
-    return 0;
+    return awgn_frames(d, cfg, cfg->first_frame, cfg->frames, y_dev, stream ? (hipStream_t) stream : d->stream);
 }
 
-int acg_ldpc_awgn_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
+extern "C" int acg_ldpc_awgn_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, float *y_dev, void *stream) {
     return guarded([&] { return acg_ldpc_awgn_dev_impl(d, cfg, y_dev, stream); });
 }
 
 // ---------------------------------------------------------------- Monte-Carlo for punctured and shortened codes
-// ACG_MC_RM_CHUNK=<frames>: developer / test switch that lowers the chunk of a rate-matched run (README, developer variables)
-static int64_t mc_rm_chunk(int64_t chunk) {
-    const char *e = getenv("ACG_MC_RM_CHUNK");
-    const int64_t v = e ? atoll(e) : 0;
-    return v > 0 ? std::min(chunk, v) : chunk;
-}
-
 // What the two calls refuse, in the order the header states; `sink` is res or out_dev.  0: the handle takes channel values.
 static int rm_check(const acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, const void *sink, const char *call) {
     if (!d || !cfg || !sink) {
@@ -1197,60 +874,40 @@ static int acg_ldpc_rm_channel_dev_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_c
     return rm_channel(d, cfg, pat_dev, cfg->first_frame, cfg->frames, out_dev, raw_dev, s);
 }
 
-int acg_ldpc_rm_channel_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, void *out_dev, int32_t *raw_dev,
-                            void *stream) {
+extern "C" int acg_ldpc_rm_channel_dev(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, void *out_dev, int32_t *raw_dev,
+                                       void *stream) {
     return guarded([&] { return acg_ldpc_rm_channel_dev_impl(d, cfg, pattern, out_dev, raw_dev, stream); });
 }
 
-// Per chunk: rm_channel_kernel (channel values into mc_y, raw-error counts) -> the handle's channel-value entrance on its
-// ordinary launch path -> classify_rm_kernel; the chunks, the timing and the counters' read-back of the unfused branch of
-// acg_ldpc_mc_run.
+// mc_frames, a chunk being rm_channel_kernel (channel values into mc_y, raw-error counts) -> the handle's channel-value
+// entrance on its ordinary launch path -> classify_rm_kernel.
 static int acg_ldpc_mc_run_rm_impl(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res) {
     if (int rc = rm_check(d, cfg, pattern, res, "acg_ldpc_mc_run_rm")) return rc;
     std::memset(res, 0, sizeof(*res));
-    if (cfg->frames == 0) return 0;
     const auto t0 = std::chrono::steady_clock::now();
-    std::lock_guard<std::recursive_mutex> lk(d->mu);
-    HIP_OK(hipSetDevice(d->device));
-    int rc = 0;
-    if ((rc = ensure_codewords(d, cfg))) return rc;
-    const uint8_t *pat_dev = nullptr;
-    if ((rc = rm_pattern_dev(d, pattern, d->stream, &pat_dev))) return rc;
     const int n = d->c.n, nwords = (n + 31) / 32;
-    const size_t elem = d->streaml ? sizeof(float) : sizeof(int16_t);
-    const int64_t chunk = mc_rm_chunk(std::max<int64_t>(256, std::min<int64_t>(cfg->frames, (int64_t) (1ull << 31) / ((int64_t) n * 4))));
-    const size_t fcap = (size_t) std::min<int64_t>(chunk, cfg->frames);
-    if ((rc = d->mc_y.reserve(fcap * n * elem)) || (rc = d->rm_raw.reserve(fcap * sizeof(int32_t))) ||
-        (rc = d->st_bits.reserve(fcap * nwords * sizeof(uint32_t))) || (rc = d->st_ok.reserve(fcap)) ||
-        (rc = d->st_iters.reserve(fcap * sizeof(int32_t))))
-        return rc;
-    HIP_OK(hipMemsetAsync(d->counters.p, 0, sizeof(unsigned long long) * MC_NCOUNTERS, d->stream));
-    const SentWords cw = sent_words(d, cfg);
-    int32_t *raw = d->rm_raw.as<int32_t>();
-    float kms = 0;
-    for (int64_t f0 = 0; f0 < cfg->frames; f0 += chunk) {
-        const int64_t fc = std::min(chunk, cfg->frames - f0), first = cfg->first_frame + f0;
-        if ((rc = rm_channel(d, cfg, pat_dev, first, fc, d->mc_y.p, raw, d->stream))) return rc;
-        Chunk c;
-        c.a = decode_args(nullptr, 0, fc, 0.0);   // (no symbols, no channel: the channel-value entrances read neither)
-        stage_outputs(d, c.a);
+    const uint8_t *pat_dev = nullptr;
+    auto prepare = [&](int64_t rows) {
+        if (int e = rm_pattern_dev(d, pattern, d->stream, &pat_dev)) return e;
+        return d->rm_raw.reserve((size_t) rows * sizeof(int32_t));
+    };
+    auto enqueue = [&](int64_t first, int64_t fc, Chunk &c) {
+        int32_t *raw = d->rm_raw.as<int32_t>();
+        if (int e = rm_channel(d, cfg, pat_dev, first, fc, d->mc_y.p, raw, d->stream)) return e;
         const QuantIo qio{d->mc_y.as<int16_t>(), nullptr};
         const StreamLayIo lio{d->mc_y.as<float>(), nullptr};
-        if ((rc = launch_decode(d, c.a, d->stream, d->streaml ? nullptr : &qio, nullptr, d->streaml ? &lio : nullptr))) return rc;
-        c.slot = d->last_slot;
+        // (no symbols, no channel: the channel-value entrances read neither)
+        if (int e = decode_chunk(d, nullptr, 0, fc, 0.0, c, d->streaml ? DecodeIo(&lio) : DecodeIo(&qio))) return e;
+        const SentWords cw = sent_words(d, cfg);
         HIP_OK(classify_rm_launch(raw, c.a.out_bits, c.a.out_ok, c.a.out_iters, fc, n, nwords, first, cw.dev, cw.n, d->counters_dev(), d->stream));
-        HIP_OK(hipStreamSynchronize(d->stream));
-        kms += chunk_ms(d, c);
-    }
-    unsigned long long h[MC_NCOUNTERS];
-    HIP_OK(hipMemcpy(h, d->counters.p, sizeof(h), hipMemcpyDeviceToHost));
-    counters_to_result(h, res);
-    res->kernel_ms = kms;
+        return 0;
+    };
+    if (int rc = mc_frames(d, cfg, d->streaml ? sizeof(float) : sizeof(int16_t), "ACG_MC_RM_CHUNK", res, true, prepare, enqueue, no_chunk_work)) return rc;
     res->time_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 
-int acg_ldpc_mc_run_rm(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res) {
+extern "C" int acg_ldpc_mc_run_rm(acg_ldpc_decoder *d, const acg_ldpc_mc_cfg *cfg, const uint8_t *pattern, acg_ldpc_mc_result *res) {
     return guarded([&] { return acg_ldpc_mc_run_rm_impl(d, cfg, pattern, res); });
 }
 
@@ -1273,7 +930,7 @@ static int acg_ldpc_gen_codewords_impl(const uint8_t *G, int32_t k, int32_t n, u
     return 0;
 }
 
-int acg_ldpc_gen_codewords(const uint8_t *G, int32_t k, int32_t n, uint32_t seed, int64_t count, uint8_t *out) {
+extern "C" int acg_ldpc_gen_codewords(const uint8_t *G, int32_t k, int32_t n, uint32_t seed, int64_t count, uint8_t *out) {
     return guarded([&] { return acg_ldpc_gen_codewords_impl(G, k, n, seed, count, out); });
 }
 
@@ -1287,9 +944,8 @@ static int acg_ldpc_transmit_host_impl(const uint8_t *codewords, int64_t n_codew
     return 0;
 }
 
-int acg_ldpc_transmit_host(const uint8_t *codewords, int64_t n_codewords, int32_t n, int64_t first_frame,
-                           int64_t frames, double snr, double *y) {
+extern "C" int acg_ldpc_transmit_host(const uint8_t *codewords, int64_t n_codewords, int32_t n, int64_t first_frame,
+                                      int64_t frames, double snr, double *y) {
     return guarded([&] { return acg_ldpc_transmit_host_impl(codewords, n_codewords, n, first_frame, frames, snr, y); });
 }
 
-}  // extern "C"
